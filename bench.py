@@ -23,6 +23,8 @@ Workloads (--workload):
   ntt24 [--ntt-field bn254]: 16 columns x 2^24-point NTT (BASELINE.json configs[4]'s transform), over Goldilocks or BN254 Fr.
   msm24: one BN254 G1 multi-scalar multiplication of 2^24 points (the recursive wrap's KZG commitment).
 
+A plain run of the sync workload sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is
+given and prints the line; everything below is measured only with --full:
 roofline: the dominant kernel is the Poseidon leaf hashing of the LDE tables (k_hash_lde_leaves); its algorithmic bytes
   per launch are 8*c*L + 32*L and its average duration is measured live with HIP events on the launch
   stream; roofline_valu is the bound that binds (integer-VALU issue).
@@ -135,7 +137,28 @@ def parse():
     ap.add_argument("--reduce-log-n", type=int, default=13)
     ap.add_argument("--map-starks", action="store_true", help="verify128 workload: also prove the map jobs' SHA-256 work (1 444 "
                     "compression blocks of 4 inclusion proofs -> 2^11 blocks per job), one STARK per rank over the jobs it owns")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="sync workload: after the timed steps also measure and check everything beyond the headline - kernel events "
+                         "in the timed region, the roofline, one proof at a time, the plonky2-only 2^16 figures, the CPU baseline with "
+                         "its byte-for-byte parity check and the verify128 record (--no-cpu-baseline / --no-extra drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="sync workload: write what the last timed step computed - the four proofs and the two public digests, as "
+                         "bytes - to DIR/<name>.npy (float32, exact for bytes)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload != "sync":
+        ap.error("--dump-outputs is implemented for --workload sync only")
+    return args
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: each named byte string as DIR/<name>.npy, one float32 per byte (exact), at most 64 MB in all"""
+    import numpy as np
+    total = sum(4 * len(v) for v in outputs.values())
+    if total > 64 << 20:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs exceed the 64 MB limit" % total)
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in outputs.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.frombuffer(v, dtype=np.uint8).astype(np.float32))
 
 
 def dist_setup(n_gpus):
@@ -777,13 +800,18 @@ def run_sync(args, nlx, torch, rank, world, local, dist):
     scratch = [0.0] * 4
     if args.warmup:
         run_steps(args.warmup, True, scratch)
-    for c in ctxs:
-        c.kernel_timing(True)
+    if args.full:
+        for c in ctxs:
+            c.kernel_timing(True)
     barrier(dist, torch)
     t0 = time.perf_counter()
     (a, b, c_proof), outer_len = run_steps(args.steps, True, [0.0] * 4)
     barrier(dist, torch)
     dt = reduce_max(dist, torch, time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sha256_proof": a[0], "sha256_digest": np.asarray(a[1]).astype(">u4").tobytes(),
+                                         "sha512_proof": b[0], "sha512_digest": np.asarray(b[1]).astype(">u8").tobytes(),
+                                         "ed25519_proof": c_proof, "outer_proof": outer_buf[:outer_len].tobytes()})
     names = ("intt", "lde", "hash_lde_leaves", "merkle_levels", "quotient", "air_quotient", "fri_combine")
 
     def collect(which=None):
@@ -796,16 +824,46 @@ def run_sync(args, nlx, torch, rank, world, local, dist):
                 ks[k][2] += b_
                 ks[k][3] += c.kernel_units(k)
         return ks
-    kstats = collect()
-    kouter = collect(ctxs[3:4])   # the outer proof's launches: the dominant kernel's dominant shape (2^21 leaves x 135 / 20 / 16 columns)
-    for c in ctxs:
-        c.kernel_timing(False)
+    if args.full:
+        kstats = collect()
+        kouter = collect(ctxs[3:4])   # the outer proof's launches: the dominant kernel's dominant shape (2^21 leaves x 135 / 20 / 16 columns)
+        for c in ctxs:
+            c.kernel_timing(False)
     out = None
     if rank == 0:
         import hashlib
+        rows = stark_verifier_rows(st)
+        out = {
+            "metric": "Sync/Verify proofs/sec at 1/2/4/8 MI355X + achieved HBM GB/s vs roofline",
+            "value": world * args.steps / dt, "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u64 (Goldilocks field, integer)",
+            "data": "synthetic outer circuit of SyncCircuit's static shape; the three STARK statements are the real mainnet Sync step main_1 -> main_2 (the reference's fixtures), traces generated on the GPU",
+            "config": {"workload": "one full Sync proof = SHA-256 STARK of %d header / next_bps messages (2^%d blocks, 2^%d x %d trace) + "
+                                   "SHA-512 STARK of %d approval hashes (2^%d blocks) + Ed25519 STARK of %d validator slots, %d of them active = "
+                                   "signed approvals, D mod L reduced in the AIR (2^%d slots, 2^%d rows) + outer plonky2 proof (standard_recursion_config, 2^%d rows, 135 wires, %d gate "
+                                   "kinds); the outer proof of a request starts when its three STARKs are done (and the previous request's outer proof, "
+                                   "which shares its context); the next requests' STARKs overlap it, at most two outer proofs outstanding; replicas only"
+                                   % (len(st["sha_msgs"]), st["lb256"], st["lb256"] + 2, p256.stark.desc.n_cols, st["n_sigs"], st["lb512"],
+                                      st["n_validators"], st["n_sigs"], st["log_slots"], ped.stark.desc.degree_bits, args.log_n, st["syn"].num_gates),
+                       "log_n_outer": args.log_n, "gate_mix_pct": GATE_MIXES[args.gate_mix],
+                       # the STARK protocol of the three sub-proofs: "starky" = the reference's (whole-row hash_or_noop leaves,
+                       # every opening observed); 0 / 0 below is the only setting an unpatched starky-style verifier accepts
+                       "stark_variant": st["stark_variant"],
+                       "leaf_group_cols": max(int(pr.stark.desc.leaf_group_cols) for pr in (p256, p512, ped)),
+                       "openings_group": max(int(pr.stark.desc.openings_group) for pr in (p256, p512, ped)),
+                       # a commitment round of more columns than this is several PolynomialBatches (each with whole-row
+                       # hash_or_noop leaves, its own cap and FRI oracle): plonky2's own batching, more Merkle paths for the verifier
+                       "stark_batch_cols": st["stark_batch_cols"],
+                       "outer_rows_floor_from_stark_verification": rows,
+                       "public_inputs": "64 bytes of real Sync I/O (fixtures/main_2.json): new head hash 0x%s" % st["sync_out"].hex(),
+                       "proof_bytes": {"sha256": len(a[0]), "sha512": len(b[0]), "ed25519": len(c_proof), "outer": outer_len},
+                       "parallelism": "replicas x%d" % world},
+            "outer_proof_sha256": hashlib.sha256(outer_buf[:outer_len].tobytes()).hexdigest(),
+        }
+    if rank == 0 and args.full:
         import struct
         io = nlx.nearx_io
-        outer_proof = outer_buf[:outer_len].tobytes()
         # the public digests are the real ones: next_bp_hash of the header, hashlib's SHA-512 of the last approval
         assert b"".join(struct.pack(">I", int(x)) for x in a[1]) == io.b58decode32(st["nxt"]["inner_lite"]["next_bp_hash"])
         assert [int(x) for x in b[1]] == list(struct.unpack(">8Q", hashlib.sha512(st["sig_msgs"][-1]).digest()))
@@ -843,33 +901,7 @@ def run_sync(args, nlx, torch, rank, world, local, dist):
                            "integer-VALU bound, so the HBM fraction is low by construction - see roofline_valu; with several "
                            "proofs in flight the event-timed duration includes time shared with the other streams' kernels "
                            "(roofline_single_stream: one proof at a time)")
-        rows = stark_verifier_rows(st)
-        out = {
-            "metric": "Sync/Verify proofs/sec at 1/2/4/8 MI355X + achieved HBM GB/s vs roofline",
-            "value": world * args.steps / dt, "unit": "proofs/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u64 (Goldilocks field, integer)",
-            "data": "synthetic outer circuit of SyncCircuit's static shape; the three STARK statements are the real mainnet Sync step main_1 -> main_2 (the reference's fixtures), traces generated on the GPU",
-            "config": {"workload": "one full Sync proof = SHA-256 STARK of %d header / next_bps messages (2^%d blocks, 2^%d x %d trace) + "
-                                   "SHA-512 STARK of %d approval hashes (2^%d blocks) + Ed25519 STARK of %d validator slots, %d of them active = "
-                                   "signed approvals, D mod L reduced in the AIR (2^%d slots, 2^%d rows) + outer plonky2 proof (standard_recursion_config, 2^%d rows, 135 wires, %d gate "
-                                   "kinds); the outer proof of a request starts when its three STARKs are done (and the previous request's outer proof, "
-                                   "which shares its context); the next requests' STARKs overlap it, at most two outer proofs outstanding; replicas only"
-                                   % (len(st["sha_msgs"]), st["lb256"], st["lb256"] + 2, p256.stark.desc.n_cols, st["n_sigs"], st["lb512"],
-                                      st["n_validators"], st["n_sigs"], st["log_slots"], ped.stark.desc.degree_bits, args.log_n, st["syn"].num_gates),
-                       "log_n_outer": args.log_n, "gate_mix_pct": GATE_MIXES[args.gate_mix],
-                       # the STARK protocol of the three sub-proofs: "starky" = the reference's (whole-row hash_or_noop leaves,
-                       # every opening observed); 0 / 0 below is the only setting an unpatched starky-style verifier accepts
-                       "stark_variant": st["stark_variant"],
-                       "leaf_group_cols": max(int(pr.stark.desc.leaf_group_cols) for pr in (p256, p512, ped)),
-                       "openings_group": max(int(pr.stark.desc.openings_group) for pr in (p256, p512, ped)),
-                       # a commitment round of more columns than this is several PolynomialBatches (each with whole-row
-                       # hash_or_noop leaves, its own cap and FRI oracle): plonky2's own batching, more Merkle paths for the verifier
-                       "stark_batch_cols": st["stark_batch_cols"],
-                       "outer_rows_floor_from_stark_verification": rows,
-                       "public_inputs": "64 bytes of real Sync I/O (fixtures/main_2.json): new head hash 0x%s" % st["sync_out"].hex(),
-                       "proof_bytes": {"sha256": len(a[0]), "sha512": len(b[0]), "ed25519": len(c_proof), "outer": outer_len},
-                       "parallelism": "replicas x%d" % world},
+        out.update({
             "roofline": hbm, "roofline_valu": valu,
             "roofline_all_launches": {"hbm_frac": hbm_all["frac"] if hbm_all else None, "valu_frac": valu_all["frac"] if valu_all else None,
                                       "launches": hbm_all["launches"] if hbm_all else None,
@@ -886,7 +918,7 @@ def run_sync(args, nlx, torch, rank, world, local, dist):
             "kernel_ms_per_step": {k: round(v[1] / 2, 3) for k, v in ks1.items()},
             "kernel_event_ms_overlapping": {k: round(v[1] / args.steps, 3) for k, v in kstats.items()},
             "outer_stage_ms_last_proof": {k: round(v, 3) for k, v in cd.stage_times()},
-        }
+        })
         # the plonky2 proof alone at 2^16 rows (round 1's headline shape), same code, one proof at a time and three in flight
         out["plonky2_only"] = {"log_n_%d_ms_single_stream" % args.log_n: round(parts[3], 2)}
         if not args.no_extra:
@@ -895,17 +927,16 @@ def run_sync(args, nlx, torch, rank, world, local, dist):
             out["cpu_baseline"], out["parity_checked"] = cpu_baseline_sync(args, nlx, st, a, b, c_proof, seq_ms)
         else:
             out["cpu_baseline"] = None
-        out["outer_proof_sha256"] = hashlib.sha256(outer_proof).hexdigest()
     pool.shutdown()
     for pr in (p256, p512, ped):
         pr.close()
     cd.close()
     for c_ in ctxs:
         c_.close()
-    # BASELINE.json configs[3] in the same line, so that the driver's N = 1, 2, 4, 8 runs of this command carry the STRONG-scaling
+    # BASELINE.json configs[3] in the same line, so that --full runs of this command at N = 1, 2, 4, 8 carry the STRONG-scaling
     # figure north_star asks for next to the Sync replicas: the 128 x 4 Verify job (32 map + 31 reduce + 1 outer proofs, sharded
     # round-robin, one RCCL all-gather of the children's blobs per level), 1 warm-up + 2 timed jobs.  Every rank takes part.
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         import copy
         va = copy.copy(args)
         va.steps, va.warmup, va.map_starks = 2, 1, True   # the map jobs' SHA-256 STARKs are part of the recorded job (builder.rs:344-363, merkle.rs:43-50)

@@ -1,5 +1,5 @@
-"""bench.py prints ONE JSON line with the driver's contract fields (plus roofline and cpu_baseline); checked on a small
-instance of the default workload and of the secondary ones."""
+"""bench.py prints ONE JSON line with the driver's contract fields (with --full also roofline and cpu_baseline); checked on a
+small instance of the default workload and of the secondary ones."""
 import json
 import os
 import subprocess
@@ -24,6 +24,14 @@ def run_bench(*args, timeout=300):
 def test_bench_parses_its_flags():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
     assert r.returncode == 0 and "--gpus" in r.stdout and "--steps" in r.stdout and "--warmup" in r.stdout
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_of_another_workload_is_an_error():
+    """--dump-outputs is written by the sync workload only: any other workload refuses it at parse time, before any GPU call"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "outer", "--dump-outputs", "unused"],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr and r.stdout.strip() == ""
 
 
 def test_gpus_flag_disagreeing_with_world_size_is_an_error():
@@ -48,8 +56,9 @@ def test_gpus_flag_without_launcher_starts_the_ranks_itself():
 
 @pytest.mark.gpu
 def test_default_workload_line():
-    """the default job = one full Sync proof (three STARKs of the mainnet step + the outer plonky2 proof, here at 2^12 rows)"""
-    d = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "12", timeout=600)
+    """the default job = one full Sync proof (three STARKs of the mainnet step + the outer plonky2 proof, here at 2^12 rows), with
+    everything --full adds to the line"""
+    d = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--log-n", "12", "--full", timeout=600)
     for k in REQUIRED:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
@@ -71,6 +80,35 @@ def test_default_workload_line():
     assert d["config"]["outer_rows_floor_from_stark_verification"]["total"] > 1 << 16
     # the headline runs the reference's STARK protocol: whole-row hash_or_noop leaves, every opening observed
     assert d["config"]["stark_variant"] == "starky" and d["config"]["leaf_group_cols"] == 0 and d["config"]["openings_group"] == 0
+
+
+@pytest.mark.gpu
+def test_plain_default_line_and_dumped_outputs(nlx, tmp_path):
+    """without --full the line carries the headline alone, and --dump-outputs writes the last timed step's four proofs and two
+    public digests: float32 bytes, the outer proof the one the line's outer_proof_sha256 names, the SHA-256 digest the header's
+    next_bp_hash"""
+    import hashlib
+    import numpy as np
+    d = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--log-n", "12", "--dump-outputs", str(tmp_path), timeout=600)
+    for k in REQUIRED:
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    for k in ("roofline", "roofline_valu", "cpu_baseline", "parity_checked", "verify128", "ms_one_proof_at_a_time"):
+        assert k not in d, k
+    names = ("sha256_proof", "sha256_digest", "sha512_proof", "sha512_digest", "ed25519_proof", "outer_proof")
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in names)
+    got = {}
+    for n in names:
+        a = np.load(tmp_path / (n + ".npy"))
+        assert a.dtype == np.float32 and a.ndim == 1 and np.all((a >= 0) & (a <= 255) & (a == np.floor(a))), n
+        got[n] = a.astype(np.uint8).tobytes()
+    assert sum(4 * len(v) for v in got.values()) <= 64 << 20
+    pb = d["config"]["proof_bytes"]
+    assert [len(got[k + "_proof"]) for k in ("sha256", "sha512", "ed25519", "outer")] == [pb[k] for k in ("sha256", "sha512", "ed25519", "outer")]
+    assert hashlib.sha256(got["outer_proof"]).hexdigest() == d["outer_proof_sha256"]
+    with open(os.path.join(ROOT, "tests", "golden", "near", "main_2.json")) as f:
+        nxt = json.load(f)["body"]
+    assert got["sha256_digest"] == nlx.nearx_io.b58decode32(nxt["inner_lite"]["next_bp_hash"]) and len(got["sha512_digest"]) == 64
 
 
 @pytest.mark.gpu
@@ -156,9 +194,9 @@ def test_one_ntt_split_over_two_ranks_equals_the_one_rank_transform():
 
 @pytest.mark.gpu
 def test_default_line_carries_the_verify_record_on_two_ranks():
-    """The driver's N > 1 command WITHOUT --no-extra (small sizes): after the Sync replicas every rank runs the 128 x 4 Verify job
+    """The driver's N > 1 command with --full and WITHOUT --no-extra (small sizes): after the Sync replicas every rank runs the 128 x 4 Verify job
     and rank 0's line carries its record - the strong-scaling figure of BASELINE.json configs[3] (gloo rehearsal on one GPU)."""
-    d = _launch_two_ranks(("--log-n", "12", "--map-log-n", "11", "--reduce-log-n", "10"), {"NLX_BENCH_REHEARSAL": "1"}, 29644)
+    d = _launch_two_ranks(("--log-n", "12", "--map-log-n", "11", "--reduce-log-n", "10", "--full"), {"NLX_BENCH_REHEARSAL": "1"}, 29644)
     v = d["verify128"]
     assert "error" not in v, v
     assert v["n_gpus"] == 2 and v["scaling"] == "strong" and v["output_ok"] is True and v["proofs_per_s"] > 0

@@ -9,9 +9,9 @@ OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/profiles_$TAG
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
 mkdir -p "$OUT"
 cd "$ROOT"
-python bench.py --steps 24 --warmup 3 > "$OUT/r01_bench_default_$TAG.json"
-python bench.py --steps 12 --warmup 3 --inflight 1 --no-cpu-baseline > "$OUT/r01_bench_single_stream_$TAG.json"
-python bench.py --steps 24 --warmup 3 --gate-mix basic --no-cpu-baseline > "$OUT/r01_bench_basic_mix_$TAG.json"
+python bench.py --full --steps 24 --warmup 3 > "$OUT/r01_bench_default_$TAG.json"
+python bench.py --full --steps 12 --warmup 3 --inflight 1 --no-cpu-baseline > "$OUT/r01_bench_single_stream_$TAG.json"
+python bench.py --full --steps 24 --warmup 3 --gate-mix basic --no-cpu-baseline > "$OUT/r01_bench_basic_mix_$TAG.json"
 python bench.py --workload verify128 --steps 3 --warmup 1 > "$OUT/r01_verify128_1gpu_$TAG.json"
 python bench.py --workload stark --steps 18 --warmup 2 --no-cpu-baseline > "$OUT/r01_stark_256x2p16_$TAG.json"
 python bench.py --workload sha256 --log-blocks 14 --steps 4 --warmup 1 > "$OUT/r01_sha256_2p14_blocks_$TAG.json"
