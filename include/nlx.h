@@ -127,6 +127,19 @@ size_t nlx_merkle_digest_words(size_t n_leaves, uint32_t cap_height);
 int32_t nlx_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, size_t n_leaves, size_t leaf_len,
                          uint32_t cap_height, uint64_t* digests_out, uint64_t* cap_out);
 
+/* ---- PoseidonBN128: Poseidon over BN254's scalar field r (circomlib t = 4, x^5, 8 full + 56 partial rounds), the hash of
+ * plonky2x's PoseidonBN128GoldilocksConfig (the permutation is pinned by known answers, the hash family is
+ * recalled).  A digest is ONE Fr element, written as 4 little-endian u64 words, canonical (not Montgomery): the shape of a
+ * Goldilocks HashOut, so digest, cap and path buffers keep their sizes.
+ * permute_batch: states n x 16 words (4 elements x 4 words), permuted in place; an element >= r -> NLX_E_RANGE.
+ * hash_rows: hash_or_noop of every row (inputs taken mod p): <= 4 elements are the digest sum x_i 2^(64 i) itself (NLX_E_RANGE
+ * if that is >= r), longer rows hash_no_pad (9 elements per permutation, three per slot 1..3, the slots overwritten).
+ * merkle_build: nlx_merkle_build with these leaves and two_to_one(a, b) = permute([0, 0, a, b])[0] for the nodes. */
+int32_t nlx_poseidon_bn128_permute_batch(nlx_ctx* ctx, uint64_t* states, size_t n);
+int32_t nlx_poseidon_bn128_hash_rows(nlx_ctx* ctx, const uint64_t* rows, size_t n_rows, size_t row_len, uint64_t* digests_out);
+int32_t nlx_poseidon_bn128_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, size_t n_leaves, size_t leaf_len, uint32_t cap_height,
+                                        uint64_t* digests_out, uint64_t* cap_out);
+
 /* ---- a2: plonky2_field::fft::{fft, ifft}, PolynomialCoeffs::coset_fft, PolynomialValues::coset_ifft ----
  * cols: n_cols x 2^log_n, column-major, transformed in place, natural order in and out.
  * inverse = 0: coefficients -> values on shift*<w>;  inverse = 1: values on shift*<w> -> coefficients.
@@ -256,6 +269,19 @@ int32_t nlx_commit_from_values(nlx_ctx* ctx, const uint64_t* values, size_t n_co
                                uint32_t rate_bits, uint32_t cap_height, uint64_t* cap_out, nlx_commit** out);
 int32_t nlx_commit_from_coeffs(nlx_ctx* ctx, const uint64_t* coeffs, size_t n_cols, uint32_t log_n,
                                uint32_t rate_bits, uint32_t cap_height, uint64_t* cap_out, nlx_commit** out);
+/* The same with the Merkle tree's hasher chosen: NLX_HASHER_POSEIDON_GOLDILOCKS is exactly the entries above,
+ * NLX_HASHER_POSEIDON_BN128 hashes leaves (hash_or_noop of the LDE row) and nodes with PoseidonBN128; its digests have the
+ * Goldilocks layout, so nlx_commit_get_* / open_rows / eval_at work unchanged.  Any other value: NLX_E_RANGE.  A BN128
+ * commitment cannot feed a Goldilocks transcript: nlx_quotient_eval and nlx_fri_prove return NLX_E_UNSUPPORTED for it.
+ * Kernel-timing names: "hash_lde_leaves_bn128" and "merkle_levels_bn128", units BN128 permutations. */
+#define NLX_HASHER_POSEIDON_GOLDILOCKS 0
+#define NLX_HASHER_POSEIDON_BN128 1
+int32_t nlx_commit_from_values_hasher(nlx_ctx* ctx, const uint64_t* values, size_t n_cols, uint32_t log_n, uint32_t rate_bits,
+                                      uint32_t cap_height, uint32_t hasher, uint64_t* cap_out, nlx_commit** out);
+int32_t nlx_commit_from_coeffs_hasher(nlx_ctx* ctx, const uint64_t* coeffs, size_t n_cols, uint32_t log_n, uint32_t rate_bits,
+                                      uint32_t cap_height, uint32_t hasher, uint64_t* cap_out, nlx_commit** out);
+/* the commitment's NLX_HASHER_* (NLX_E_INVAL for NULL) */
+int32_t nlx_commit_hasher(const nlx_commit* c);
 void nlx_commit_destroy(nlx_commit* c);
 
 /* PolynomialBatch.polynomials: coefficients, natural order, n_cols x n column-major. */

@@ -68,6 +68,11 @@ SIGNATURES = {
     "nlx_merkle_digest_words": (ctypes.c_size_t, [ctypes.c_size_t, ctypes.c_uint32]),
     "nlx_merkle_build": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_poseidon_bn128_permute_batch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
+    "nlx_poseidon_bn128_hash_rows": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                      ctypes.c_void_p]),
+    "nlx_poseidon_bn128_merkle_build": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_ntt_batch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
                                        ctypes.c_int, ctypes.c_uint64]),
     "nlx_ntt_split_level": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
@@ -93,6 +98,11 @@ SIGNATURES = {
                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, c_void_pp]),
     "nlx_commit_from_coeffs": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, c_void_pp]),
+    "nlx_commit_from_values_hasher": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
+                                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, c_void_pp]),
+    "nlx_commit_from_coeffs_hasher": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
+                                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, c_void_pp]),
+    "nlx_commit_hasher": (ctypes.c_int32, [ctypes.c_void_p]),
     "nlx_commit_destroy": (None, [ctypes.c_void_p]),
     "nlx_commit_get_coeffs": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_commit_get_cap": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),

@@ -48,20 +48,32 @@ def ntt(ctx, cols, inverse=False, coset_shift=1):
     return c
 
 
-class MerkleTree:
-    """MerkleTree::new(leaves, cap_height): leaves (n_leaves, leaf_len) row-major."""
+# Merkle hashers (include/nlx.h NLX_HASHER_*): plonky2's Goldilocks Poseidon, or PoseidonBN128 (plonky2x's wrapper config)
+HASHERS = {"poseidon_goldilocks": 0, "poseidon_bn128": 1}
 
-    def __init__(self, ctx, leaves, cap_height):
+
+def _hasher_id(hasher):
+    if hasher not in HASHERS:
+        raise ValueError("hasher must be one of %s" % ", ".join(sorted(HASHERS)))
+    return HASHERS[hasher]
+
+
+class MerkleTree:
+    """MerkleTree::new(leaves, cap_height): leaves (n_leaves, leaf_len) row-major.  hasher="poseidon_bn128": leaves
+    hash_or_noop and nodes two_to_one of PoseidonBN128, digests one Fr element each as 4 canonical words (same shapes)."""
+
+    def __init__(self, ctx, leaves, cap_height, hasher="poseidon_goldilocks"):
+        build = (dll.nlx_merkle_build, dll.nlx_poseidon_bn128_merkle_build)[_hasher_id(hasher)]
         lv = np.ascontiguousarray(leaves, dtype=np.uint64)
         self.n_leaves, self.leaf_len = lv.shape
         self.cap_height = cap_height
+        self.hasher = hasher
         words = dll.nlx_merkle_digest_words(self.n_leaves, cap_height)
         if words == 0:
             raise ValueError("n_leaves must be a power of two")
         self.digests = np.zeros(words, dtype=np.uint64)
         self.cap = np.zeros((1 << cap_height, 4), dtype=np.uint64)
-        ctx.check(dll.nlx_merkle_build(ctx.handle, ptr(lv), self.n_leaves, self.leaf_len, cap_height,
-                                       ptr(self.digests), ptr(self.cap)))
+        ctx.check(build(ctx.handle, ptr(lv), self.n_leaves, self.leaf_len, cap_height, ptr(self.digests), ptr(self.cap)))
         self.leaves = lv
 
     def prove(self, leaf_index):
@@ -81,13 +93,16 @@ class PolynomialBatch:
 
     def __init__(self, ctx, handle, n_cols, log_n, rate_bits, cap_height, cap):
         self.ctx, self.handle = ctx, handle
+        hid = dll.nlx_commit_hasher(handle)
+        ctx.check(min(hid, 0))
+        self._hasher = {v: k for k, v in HASHERS.items()}[hid]
         self.n_cols, self.log_n, self.rate_bits, self.cap_height = n_cols, log_n, rate_bits, cap_height
         self.cap = cap
         self._borrowed = False
         ctx._adopt(self)
 
     @classmethod
-    def _make(cls, fn, ctx, data, rate_bits, cap_height):
+    def _make(cls, fn, ctx, data, rate_bits, cap_height, hasher="poseidon_goldilocks", fn_hasher=None):
         if isinstance(data, np.ndarray):
             data = np.ascontiguousarray(data, dtype=np.uint64)
         n_cols, n = data.shape
@@ -96,7 +111,11 @@ class PolynomialBatch:
             raise ValueError("polynomial length must be a power of two")
         cap = np.zeros((1 << cap_height, 4), dtype=np.uint64)
         h = ctypes.c_void_p()
-        ctx.check(fn(ctx.handle, ptr(data), n_cols, log_n, rate_bits, cap_height, ptr(cap), ctypes.byref(h)))
+        hid = _hasher_id(hasher)
+        if hid == 0:   # today's entries, exactly
+            ctx.check(fn(ctx.handle, ptr(data), n_cols, log_n, rate_bits, cap_height, ptr(cap), ctypes.byref(h)))
+        else:
+            ctx.check(fn_hasher(ctx.handle, ptr(data), n_cols, log_n, rate_bits, cap_height, hid, ptr(cap), ctypes.byref(h)))
         return cls(ctx, h, n_cols, log_n, rate_bits, cap_height, cap)
 
     @classmethod
@@ -107,13 +126,19 @@ class PolynomialBatch:
         return cls(ctx, handle, n_cols, log_n, rate_bits, cap_height, cap)
 
     @classmethod
-    def from_values(cls, ctx, values, rate_bits, cap_height):
-        """values: (n_cols, n) — one polynomial's subgroup evaluations per row."""
-        return cls._make(dll.nlx_commit_from_values, ctx, values, rate_bits, cap_height)
+    def from_values(cls, ctx, values, rate_bits, cap_height, hasher="poseidon_goldilocks"):
+        """values: (n_cols, n) — one polynomial's subgroup evaluations per row.  hasher: the Merkle tree's hash
+        ("poseidon_goldilocks": plonky2's PoseidonGoldilocksConfig; "poseidon_bn128": plonky2x's PoseidonBN128GoldilocksConfig)."""
+        return cls._make(dll.nlx_commit_from_values, ctx, values, rate_bits, cap_height, hasher, dll.nlx_commit_from_values_hasher)
 
     @classmethod
-    def from_coeffs(cls, ctx, coeffs, rate_bits, cap_height):
-        return cls._make(dll.nlx_commit_from_coeffs, ctx, coeffs, rate_bits, cap_height)
+    def from_coeffs(cls, ctx, coeffs, rate_bits, cap_height, hasher="poseidon_goldilocks"):
+        return cls._make(dll.nlx_commit_from_coeffs, ctx, coeffs, rate_bits, cap_height, hasher, dll.nlx_commit_from_coeffs_hasher)
+
+    @property
+    def hasher(self):
+        """"poseidon_goldilocks" or "poseidon_bn128" (nlx_commit_hasher)"""
+        return self._hasher
 
     @property
     def lde_size(self):
@@ -416,3 +441,26 @@ def bn254_g2_sum(points):
     if dll.nlx_bn254_g2_sum(a.ctypes.data if len(a) else None, len(a), out.ctypes.data) != 0:
         raise ValueError("nlx_bn254_g2_sum failed")
     return out
+
+
+# ---- PoseidonBN128 (csrc/poseidon_bn128.hip): the hash of plonky2x's wrapper config, digests one BN254 Fr element ----
+def poseidon_bn128_permute(ctx, states):
+    """the PoseidonBN128 permutation of a batch of states.  states: n lists of 4 Python ints (< r; returns the same form) or an
+    (n, 4, 4) uint64 array of little-endian words (returns a new array)."""
+    ints = not isinstance(states, np.ndarray)
+    s = bn254_pack(states) if ints else np.ascontiguousarray(states, dtype=np.uint64).copy()
+    if s.ndim != 3 or s.shape[1:] != (4, 4):
+        raise ValueError("states must be n x 4 field elements")
+    ctx.check(dll.nlx_poseidon_bn128_permute_batch(ctx.handle, ptr(s), s.shape[0]))
+    return bn254_unpack(s) if ints else s
+
+
+def poseidon_bn128_hash_rows(ctx, rows, as_ints=False):
+    """PoseidonBN128 hash_or_noop of every row of a row-major (n_rows, row_len) Goldilocks matrix (values taken mod p):
+    (n_rows, 4) uint64 canonical little-endian words, or a list of Python ints with as_ints"""
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    if r.ndim != 2:
+        raise ValueError("rows must be a 2-D matrix")
+    out = np.zeros((r.shape[0], 4), dtype=np.uint64)
+    ctx.check(dll.nlx_poseidon_bn128_hash_rows(ctx.handle, ptr(r), r.shape[0], r.shape[1], ptr(out)))
+    return bn254_unpack(out[None])[0] if as_ints else out

@@ -41,8 +41,12 @@ nlx_commit commit_view(const nlx_commit* c, uint32_t k) {
 
 int32_t commit_build(nlx_ctx* ctx, const uint64_t* d_in, size_t in_stride, CommitInput kind, uint32_t n_cols,
                      uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, nlx_commit** out, uint32_t leaf_group,
-                     uint32_t batch_cols) {
+                     uint32_t batch_cols, uint32_t hasher, uint32_t* d_bad) {
     *out = nullptr;
+    const bool bn128 = hasher == NLX_HASHER_POSEIDON_BN128;
+    if (!bn128 && hasher != NLX_HASHER_POSEIDON_GOLDILOCKS) return ctx->fail(NLX_E_RANGE, "unknown hasher %u", hasher);
+    if (bn128 && (leaf_group || batch_cols || !d_bad))
+        return ctx->fail(NLX_E_UNSUPPORTED, "PoseidonBN128 commitments have neither grouped leaves nor batches");
     if (n_cols == 0 || n_cols > 65535) return ctx->fail(NLX_E_RANGE, "n_cols %u out of range [1, 65535]", n_cols);
     if (log_n + rate_bits > 32) return ctx->fail(NLX_E_RANGE, "log_n + rate_bits > 32");
     if (cap_height > log_n + rate_bits) return ctx->fail(NLX_E_RANGE, "cap_height exceeds tree height");
@@ -59,6 +63,7 @@ int32_t commit_build(nlx_ctx* ctx, const uint64_t* d_in, size_t in_stride, Commi
     c->log_n = log_n;
     c->rate_bits = rate_bits;
     c->cap_height = cap_height;
+    c->hasher = hasher;
     const size_t n = c->n(), L = c->L();
     c->coeffs_br = (uint64_t*)ctx->alloc((size_t)n_cols * n * 8);
     c->lde = (uint64_t*)ctx->alloc((size_t)n_cols * L * 8);
@@ -110,7 +115,16 @@ int32_t commit_build(nlx_ctx* ctx, const uint64_t* d_in, size_t in_stride, Commi
     launch_lde_dit(st, ctx->tables, c->coeffs_br, n, c->lde, L, n_cols, log_n, rate_bits, scale);
     ctx->end_kernel();
     // units: Poseidon permutations (hash_or_noop: none for rows of <= 4 elements, else one per 8 absorbed)
-    if (grouped) {
+    if (bn128) {
+        // PoseidonBN128 (poseidon_bn128.hip): one permutation per 9 absorbed elements, n_cols <= 4 none; the digests have the
+        // same level-major layout, so every nlx_commit_get_* / open_rows works on the handle unchanged
+        ctx->begin_kernel("hash_lde_leaves_bn128", 8.0 * n_cols * L + 32.0 * L, n_cols <= 4 ? 0.0 : (double)L * ((n_cols + 8) / 9));
+        launch_pbn_hash_lde_leaves(st, c->lde, L, n_cols, log_n, rate_bits, c->digests, d_bad);
+        ctx->end_kernel();
+        ctx->begin_kernel("merkle_levels_bn128", 64.0 * L, (double)L - (double)((size_t)1 << cap_height));
+        c->cap = launch_pbn_merkle_levels(st, c->digests, L, cap_height);
+        ctx->end_kernel();
+    } else if (grouped) {
         // permutations: every run's ceil(len / 8), then ceil(4 K / 8) per leaf over the runs' digests
         const uint32_t last = n_cols - (n_groups - 1) * leaf_group;
         const double perms = (double)L * ((double)(n_groups - 1) * ((leaf_group + 7) / 8) + (last + 7) / 8 + (4 * n_groups + 7) / 8);
@@ -128,9 +142,11 @@ int32_t commit_build(nlx_ctx* ctx, const uint64_t* d_in, size_t in_stride, Commi
         launch_hash_lde_leaves(st, c->lde, L, n_cols, log_n, rate_bits, c->digests);
         ctx->end_kernel();
     }
-    ctx->begin_kernel("merkle_levels", 64.0 * L * c->n_trees, ((double)L - (double)((size_t)1 << cap_height)) * c->n_trees);
-    c->cap = launch_merkle_levels(st, c->digests, L, cap_height, c->n_trees, c->tree_words);
-    ctx->end_kernel();
+    if (!bn128) {
+        ctx->begin_kernel("merkle_levels", 64.0 * L * c->n_trees, ((double)L - (double)((size_t)1 << cap_height)) * c->n_trees);
+        c->cap = launch_merkle_levels(st, c->digests, L, cap_height, c->n_trees, c->tree_words);
+        ctx->end_kernel();
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         ctx->release(c->coeffs_br);
@@ -328,20 +344,36 @@ int32_t nlx_ntt_split_level(nlx_ctx* ctx, uint64_t* mine, const uint64_t* theirs
 } NLX_CATCH(ctx)
 
 static int32_t commit_api(nlx_ctx* ctx, const uint64_t* data, size_t n_cols, uint32_t log_n, uint32_t rate_bits,
-                          uint32_t cap_height, uint64_t* cap_out, nlx_commit** out, CommitInput kind) {
+                          uint32_t cap_height, uint64_t* cap_out, nlx_commit** out, CommitInput kind,
+                          uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS) {
     if (!ctx) return NLX_E_INVAL;
     if (!out) return ctx->fail(NLX_E_INVAL, "out is NULL");
     *out = nullptr;
     if (!data) return ctx->fail(NLX_E_INVAL, "input is NULL");
     if (n_cols == 0 || n_cols > 65535) return ctx->fail(NLX_E_RANGE, "n_cols out of range");
     if (log_n > 32) return ctx->fail(NLX_E_RANGE, "log_n > 32");
+    if (hasher != NLX_HASHER_POSEIDON_GOLDILOCKS && hasher != NLX_HASHER_POSEIDON_BN128)
+        return ctx->fail(NLX_E_RANGE, "unknown hasher %u", hasher);
     (void)hipSetDevice(ctx->device);
     const size_t n = (size_t)1 << log_n;
     Staged in(ctx, data, n_cols * n * 8, true, false);
     if (in.status) return in.status;
     nlx_commit* c = nullptr;
-    int32_t rc = commit_build(ctx, in.as<uint64_t>(), n, kind, (uint32_t)n_cols, log_n, rate_bits, cap_height, &c);
-    if (rc) return rc;
+    int32_t rc;
+    if (hasher == NLX_HASHER_POSEIDON_BN128) {
+        RangeFlag bad(ctx);
+        if (!bad.d) return NLX_E_NOMEM;
+        rc = commit_build(ctx, in.as<uint64_t>(), n, kind, (uint32_t)n_cols, log_n, rate_bits, cap_height, &c, 0, 0, hasher, bad.d);
+        if (rc) return rc;
+        rc = bad.check("PoseidonBN128 commitment");   // synchronises
+        if (rc) {
+            nlx_commit_destroy(c);
+            return rc;
+        }
+    } else {
+        rc = commit_build(ctx, in.as<uint64_t>(), n, kind, (uint32_t)n_cols, log_n, rate_bits, cap_height, &c);
+        if (rc) return rc;
+    }
     if (cap_out) rc = copy_out(ctx, cap_out, c->cap, ((size_t)32) << cap_height);
     hipError_t e = hipStreamSynchronize(ctx->stream);
     if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
@@ -362,6 +394,21 @@ int32_t nlx_commit_from_coeffs(nlx_ctx* ctx, const uint64_t* coeffs, size_t n_co
                                uint32_t rate_bits, uint32_t cap_height, uint64_t* cap_out, nlx_commit** out) NLX_TRY {
     return commit_api(ctx, coeffs, n_cols, log_n, rate_bits, cap_height, cap_out, out, CommitInput::CoeffsNatural);
 } NLX_CATCH(ctx)
+
+int32_t nlx_commit_from_values_hasher(nlx_ctx* ctx, const uint64_t* values, size_t n_cols, uint32_t log_n, uint32_t rate_bits,
+                                      uint32_t cap_height, uint32_t hasher, uint64_t* cap_out, nlx_commit** out) NLX_TRY {
+    return commit_api(ctx, values, n_cols, log_n, rate_bits, cap_height, cap_out, out, CommitInput::ValuesNatural, hasher);
+} NLX_CATCH(ctx)
+
+int32_t nlx_commit_from_coeffs_hasher(nlx_ctx* ctx, const uint64_t* coeffs, size_t n_cols, uint32_t log_n, uint32_t rate_bits,
+                                      uint32_t cap_height, uint32_t hasher, uint64_t* cap_out, nlx_commit** out) NLX_TRY {
+    return commit_api(ctx, coeffs, n_cols, log_n, rate_bits, cap_height, cap_out, out, CommitInput::CoeffsNatural, hasher);
+} NLX_CATCH(ctx)
+
+int32_t nlx_commit_hasher(const nlx_commit* c) NLX_TRY {
+    if (!c) return NLX_E_INVAL;
+    return (int32_t)c->hasher;
+} NLX_CATCH(nullptr)
 
 void nlx_commit_destroy(nlx_commit* c) NLX_TRY {
     if (!c) return;

@@ -19,6 +19,7 @@ struct nlx_commit {
     uint32_t n_trees = 1, batch_cols = 0;
     size_t tree_words = 0;
     bool owner = true;                  // false: a view of one batch (commit_view), nothing to free
+    uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS;   // the Merkle tree's hash (include/nlx.h NLX_HASHER_*)
     size_t n() const { return (size_t)1 << log_n; }
     size_t L() const { return (size_t)1 << (log_n + rate_bits); }
     unsigned log_L() const { return log_n + rate_bits; }
@@ -32,9 +33,39 @@ enum class CommitInput { ValuesNatural, CoeffsNatural, CoeffsBitrev };
 // no synchronisation.  On success *out owns coeffs_br / lde / digests.
 // leaf_group: 0 = plonky2 leaves (hash_or_noop of the whole LDE row); G > 0 and n_cols > G: grouped leaves (launch.hpp)
 // batch_cols: 0 = one batch; B > 0 and n_cols > B: ceil(n_cols / B) batches with a tree each (see nlx_commit)
+// hasher: NLX_HASHER_POSEIDON_BN128 hashes leaves and nodes with PoseidonBN128 (poseidon_bn128.hip; no grouped leaves, no
+// batches); d_bad then is a zeroed device word the leaf kernel sets when a <= 4-column row packs to a value >= r (RangeFlag)
 int32_t commit_build(nlx_ctx* ctx, const uint64_t* d_in, size_t in_stride, CommitInput kind, uint32_t n_cols,
                      uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, nlx_commit** out, uint32_t leaf_group = 0,
-                     uint32_t batch_cols = 0);
+                     uint32_t batch_cols = 0, uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS, uint32_t* d_bad = nullptr);
 // batch k of a commitment as a commitment of its own (non-owning): its columns of the shared tables, its tree, its cap
 nlx_commit commit_view(const nlx_commit* c, uint32_t k);
+
+// ---- PoseidonBN128 (poseidon_bn128.hip) ----
+// leaf digests of an LDE table (the row -> tree position map of launch_hash_lde_leaves), hash_or_noop over BN254 Fr
+void launch_pbn_hash_lde_leaves(hipStream_t st, const uint64_t* d_lde, size_t col_stride, uint32_t n_cols, unsigned log_n,
+                                unsigned rate_bits, uint64_t* d_digests, uint32_t* d_bad);
+// levels down to the cap with two_to_one; returns the cap level inside d_digests
+const uint64_t* launch_pbn_merkle_levels(hipStream_t st, uint64_t* d_digests, size_t n_leaves, unsigned cap_height);
+// a zeroed device word for the BN128 kernels' range flag, and its read-back once the stream has run (synchronises)
+struct RangeFlag {
+    nlx_ctx* ctx;
+    uint32_t* d = nullptr;
+    explicit RangeFlag(nlx_ctx* c) : ctx(c) {
+        d = (uint32_t*)ctx->alloc(256);
+        if (d) (void)hipMemsetAsync(d, 0, 4, ctx->stream);
+    }
+    ~RangeFlag() { ctx->release(d); }
+    RangeFlag(const RangeFlag&) = delete;
+    RangeFlag& operator=(const RangeFlag&) = delete;
+    // NLX_OK, NLX_E_RANGE (an input had no digest) or the synchronisation's error
+    int32_t check(const char* what) {
+        uint32_t h = 0;
+        hipError_t e = hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return ctx->hip_fail(e, what);
+        if (h) return ctx->fail(NLX_E_RANGE, "%s: an input is not a canonical BN254 Fr element, or a row of <= 4 elements packs to a value >= r", what);
+        return NLX_OK;
+    }
+};
 }  // namespace nlx

@@ -1,0 +1,262 @@
+// PoseidonBN128 kernels for gfx950 (the Merkle hash of plonky2x's PoseidonBN128GoldilocksConfig; spec: tools/gen_poseidon_bn128.py,
+// DESIGN.md §16): batched permutation, hash_or_noop of row-major rows and of the rows of a commitment's LDE table, Merkle levels
+// with two_to_one - and their C-ABI entry points.
+//
+// One state per lane: four Fr elements on nine 29-bit limbs in Montgomery form (36 VGPRs), the permutation of
+// poseidon_bn128.hpp (round constants by scalar loads, one loop over the 64 rounds).  Digests leave the kernels canonical, four
+// little-endian u64 words each, so cap / digest / path buffers have the shapes of the Goldilocks ones.
+// A <= 4-element input whose packed value is not below r has no digest (plonky2x's from_bytes fails there): the kernel sets
+// *bad and the entry point returns NLX_E_RANGE.
+#include <hip/hip_runtime.h>
+#include "commit.hpp"
+#include "gl.hpp"
+#include "poseidon_bn128.hpp"
+
+namespace nlx {
+
+using pbn::Fe;
+
+__device__ __forceinline__ void pbn_store(uint64_t* __restrict__ out, size_t idx, const Fe& d) {
+    uint64_t w[4];
+    pbn::to_words(d, w);
+    ulonglong2* dst = reinterpret_cast<ulonglong2*>(out + idx * 4);
+    dst[0] = make_ulonglong2(w[0], w[1]);
+    dst[1] = make_ulonglong2(w[2], w[3]);
+}
+
+// hash_or_noop's no-op branch: <= 4 canonical Goldilocks elements are the digest, sum e_i 2^(64 i), when that is below r
+__device__ __forceinline__ void pbn_noop(uint64_t* __restrict__ out, size_t idx, const uint64_t (&e)[4], uint32_t* bad) {
+    if (!pbn::lt_r(e[0], e[1], e[2], e[3])) {
+        atomicOr(bad, 1u);
+        return;
+    }
+    ulonglong2* dst = reinterpret_cast<ulonglong2*>(out + idx * 4);
+    dst[0] = make_ulonglong2(e[0], e[1]);
+    dst[1] = make_ulonglong2(e[2], e[3]);
+}
+
+// hash_no_pad's absorption of one chunk of `rem` (>= 1, wave-uniform) elements e[0..min(rem, 9)): group g of <= 3 elements
+// OVERWRITES slot g + 1; slots a short chunk does not reach keep their value
+__device__ __forceinline__ void pbn_absorb(Fe (&s)[pbn::T], const uint64_t (&e)[pbn::CHUNK], uint32_t rem) {
+#pragma unroll
+    for (int g = 0; g < 3; g++)
+        if ((uint32_t)(3 * g) < rem) s[g + 1] = pbn::from_gl3(e[3 * g], e[3 * g + 1], e[3 * g + 2]);
+}
+
+// states: n x 16 words (four canonical Fr elements of four words), permuted in place; a non-canonical state is left as it is
+__global__ __launch_bounds__(256) void k_pbn_permute_batch(uint64_t* __restrict__ states, size_t n, uint32_t* __restrict__ bad) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    uint64_t* p = states + t * 16;
+    uint64_t w[16];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const ulonglong2 v = reinterpret_cast<const ulonglong2*>(p)[i];
+        w[2 * i] = v.x;
+        w[2 * i + 1] = v.y;
+    }
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < pbn::T; i++) ok = ok && pbn::lt_r(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    if (!ok) {
+        atomicOr(bad, 1u);
+        return;
+    }
+    Fe s[pbn::T];
+#pragma unroll
+    for (int i = 0; i < pbn::T; i++) s[i] = pbn::from_words(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    pbn::permute(s);
+#pragma unroll
+    for (int i = 0; i < pbn::T; i++) pbn_store(p, i, s[i]);
+}
+
+// hash_or_noop of every row of a row-major matrix (inputs taken mod p)
+__global__ __launch_bounds__(256) void k_pbn_hash_rows(const uint64_t* __restrict__ rows, uint32_t row_len, size_t n_rows,
+                                                       uint64_t* __restrict__ digests, uint32_t* __restrict__ bad) {
+    const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n_rows) return;
+    const uint64_t* p = rows + row * (size_t)row_len;
+    if (row_len <= 4) {
+        uint64_t e[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if ((uint32_t)c < row_len) e[c] = gl::canon(p[c]);
+        pbn_noop(digests, row, e, bad);
+        return;
+    }
+    Fe s[pbn::T];
+#pragma unroll
+    for (int i = 0; i < pbn::T; i++) s[i] = f29::zero();
+#pragma unroll 1
+    for (uint32_t c = 0; c < row_len; c += pbn::CHUNK) {   // one call site of the permutation; the chunk length is wave-uniform
+        const uint32_t rem = row_len - c;
+        uint64_t e[pbn::CHUNK];
+#pragma unroll
+        for (int j = 0; j < pbn::CHUNK; j++) e[j] = (uint32_t)j < rem ? gl::canon(p[c + j]) : 0;
+        pbn_absorb(s, e, rem);
+        pbn::permute(s);
+    }
+    pbn_store(digests, row, s[0]);
+}
+
+// Leaf digests of a commitment's LDE table ([col][r][k], the value at g w_L^(8k + r)): the same row -> tree position map as
+// k_hash_lde_leaves (bitrev(r) n + bitrev(k)), hash_or_noop of the n_cols values of the row
+__global__ __launch_bounds__(256) void k_pbn_hash_lde_leaves(const uint64_t* __restrict__ lde, size_t col_stride, uint32_t n_cols,
+                                                             unsigned log_n, unsigned rate_bits, uint64_t* __restrict__ digests,
+                                                             uint32_t* __restrict__ bad) {
+    const size_t pos = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos >> (log_n + rate_bits)) return;
+    const uint64_t* p = lde + pos;
+    const uint32_t r = (uint32_t)(pos >> log_n), k = (uint32_t)(pos & (((size_t)1 << log_n) - 1));
+    const size_t leaf = ((size_t)gl::bitrev32(r, rate_bits) << log_n) + gl::bitrev32(k, log_n);
+    if (n_cols <= 4) {
+        uint64_t e[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if ((uint32_t)c < n_cols) e[c] = gl::canon(p[(size_t)c * col_stride]);
+        pbn_noop(digests, leaf, e, bad);
+        return;
+    }
+    Fe s[pbn::T];
+#pragma unroll
+    for (int i = 0; i < pbn::T; i++) s[i] = f29::zero();
+#pragma unroll 1
+    for (uint32_t c = 0; c < n_cols; c += pbn::CHUNK) {   // ceil(n_cols / 9) permutations, wave-uniform
+        const uint32_t rem = n_cols - c;
+        uint64_t e[pbn::CHUNK];
+#pragma unroll
+        for (int j = 0; j < pbn::CHUNK; j++) e[j] = (uint32_t)j < rem ? gl::canon(p[(size_t)(c + j) * col_stride]) : 0;
+        pbn_absorb(s, e, rem);
+        pbn::permute(s);
+    }
+    pbn_store(digests, leaf, s[0]);
+}
+
+// one interior level: parent[i] = two_to_one(child[2i], child[2i+1]) = permute([0, 0, a, b])[0]
+__global__ __launch_bounds__(256) void k_pbn_merkle_level(const uint64_t* __restrict__ children, uint64_t* __restrict__ parents,
+                                                          size_t n_parents) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_parents) return;
+    const ulonglong2* src = reinterpret_cast<const ulonglong2*>(children + i * 8);
+    const ulonglong2 a0 = src[0], a1 = src[1], b0 = src[2], b1 = src[3];
+    Fe s[pbn::T];
+    s[0] = f29::zero();
+    s[1] = f29::zero();
+    s[2] = pbn::from_words(a0.x, a0.y, a1.x, a1.y);
+    s[3] = pbn::from_words(b0.x, b0.y, b1.x, b1.y);
+    pbn::permute(s);
+    pbn_store(parents, i, s[0]);
+}
+
+// ---- host launchers (stream-ordered, no synchronisation); `bad`: a device word the caller zeroed ----
+static unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
+
+void launch_pbn_hash_lde_leaves(hipStream_t st, const uint64_t* d_lde, size_t col_stride, uint32_t n_cols, unsigned log_n,
+                                unsigned rate_bits, uint64_t* d_digests, uint32_t* d_bad) {
+    const size_t rows = (size_t)1 << (log_n + rate_bits);
+    hipLaunchKernelGGL(k_pbn_hash_lde_leaves, dim3(blocks_of(rows)), dim3(256), 0, st, d_lde, col_stride, n_cols, log_n, rate_bits,
+                       d_digests, d_bad);
+}
+
+// level-major digests from the leaf level down to the cap level; returns the cap inside d_digests.  Every level is one launch
+// with one lane per parent: below ~2^16 parents a level no longer fills the chip and costs one permutation's latency.
+const uint64_t* launch_pbn_merkle_levels(hipStream_t st, uint64_t* d_digests, size_t n_leaves, unsigned cap_height) {
+    const size_t cap = (size_t)1 << cap_height;
+    uint64_t* cur = d_digests;
+    size_t lvl = n_leaves;
+    while (lvl > cap) {
+        uint64_t* nxt = cur + lvl * 4;
+        const size_t half = lvl >> 1;
+        hipLaunchKernelGGL(k_pbn_merkle_level, dim3(blocks_of(half)), dim3(256), 0, st, cur, nxt, half);
+        cur = nxt;
+        lvl = half;
+    }
+    return cur;
+}
+
+}  // namespace nlx
+
+using namespace nlx;
+
+extern "C" {
+
+int32_t nlx_poseidon_bn128_permute_batch(nlx_ctx* ctx, uint64_t* states, size_t n) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (n == 0) return NLX_OK;
+    if (!states) return ctx->fail(NLX_E_INVAL, "states is NULL");
+    (void)hipSetDevice(ctx->device);
+    Staged s(ctx, states, n * 16 * 8, true, true);
+    if (s.status) return s.status;
+    RangeFlag bad(ctx);
+    if (!bad.d) return NLX_E_NOMEM;
+    hipLaunchKernelGGL(k_pbn_permute_batch, dim3(blocks_of(n)), dim3(256), 0, ctx->stream, s.as<uint64_t>(), n, bad.d);
+    NLX_HIP(ctx, hipGetLastError());
+    int32_t rc = bad.check("nlx_poseidon_bn128_permute_batch");
+    if (rc) return rc;
+    rc = s.finish();
+    if (rc) return rc;
+    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NLX_OK;
+} NLX_CATCH(ctx)
+
+int32_t nlx_poseidon_bn128_hash_rows(nlx_ctx* ctx, const uint64_t* rows, size_t n_rows, size_t row_len, uint64_t* digests_out) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (n_rows == 0) return NLX_OK;
+    if (!digests_out || (!rows && row_len)) return ctx->fail(NLX_E_INVAL, "NULL buffer");
+    if (row_len > 0xFFFFFFFFull) return ctx->fail(NLX_E_RANGE, "row_len too large");
+    (void)hipSetDevice(ctx->device);
+    Staged in(ctx, rows, n_rows * row_len * 8, true, false);
+    Staged out(ctx, digests_out, n_rows * 32, false, true);
+    if (in.status) return in.status;
+    if (out.status) return out.status;
+    RangeFlag bad(ctx);
+    if (!bad.d) return NLX_E_NOMEM;
+    hipLaunchKernelGGL(k_pbn_hash_rows, dim3(blocks_of(n_rows)), dim3(256), 0, ctx->stream, in.as<uint64_t>(), (uint32_t)row_len,
+                       n_rows, out.as<uint64_t>(), bad.d);
+    NLX_HIP(ctx, hipGetLastError());
+    int32_t rc = bad.check("nlx_poseidon_bn128_hash_rows");
+    if (rc) return rc;
+    rc = out.finish();
+    if (rc) return rc;
+    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NLX_OK;
+} NLX_CATCH(ctx)
+
+int32_t nlx_poseidon_bn128_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, size_t n_leaves, size_t leaf_len, uint32_t cap_height,
+                                        uint64_t* digests_out, uint64_t* cap_out) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (n_leaves == 0 || (n_leaves & (n_leaves - 1))) return ctx->fail(NLX_E_INVAL, "n_leaves must be a power of two");
+    if (cap_height > 63 || ((size_t)1 << cap_height) > n_leaves)
+        return ctx->fail(NLX_E_RANGE, "cap_height %u exceeds log2(n_leaves)", cap_height);
+    if (!cap_out || (!leaves && leaf_len)) return ctx->fail(NLX_E_INVAL, "NULL buffer");
+    if (leaf_len > 0xFFFFFFFFull) return ctx->fail(NLX_E_RANGE, "leaf_len too large");
+    (void)hipSetDevice(ctx->device);
+    const size_t words = merkle_digest_words(n_leaves, cap_height);
+    Staged in(ctx, leaves, n_leaves * leaf_len * 8, true, false);
+    if (in.status) return in.status;
+    Staged dig(ctx, digests_out ? (void*)digests_out : nullptr, words * 8, false, digests_out != nullptr);
+    if (dig.status) return dig.status;
+    uint64_t* d_dig = digests_out ? dig.as<uint64_t>() : (uint64_t*)ctx->alloc(words * 8);
+    if (!d_dig) return NLX_E_NOMEM;
+    RangeFlag bad(ctx);
+    int32_t rc = bad.d ? NLX_OK : NLX_E_NOMEM;
+    if (!rc) {
+        hipLaunchKernelGGL(k_pbn_hash_rows, dim3(blocks_of(n_leaves)), dim3(256), 0, ctx->stream, in.as<uint64_t>(),
+                           (uint32_t)leaf_len, n_leaves, d_dig, bad.d);
+        const uint64_t* d_cap = launch_pbn_merkle_levels(ctx->stream, d_dig, n_leaves, cap_height);
+        const hipError_t le = hipGetLastError();
+        rc = le != hipSuccess ? ctx->hip_fail(le, "kernel launch") : bad.check("nlx_poseidon_bn128_merkle_build");
+        if (!rc) {
+            hipError_t e = hipMemcpyAsync(cap_out, d_cap, ((size_t)32) << cap_height,
+                                          is_device_ptr(cap_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream);
+            if (e != hipSuccess) rc = ctx->hip_fail(e, "hipMemcpyAsync(cap)");
+        }
+        if (!rc && digests_out) rc = dig.finish();
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
+    }
+    if (!digests_out) ctx->release(d_dig);
+    return rc;
+} NLX_CATCH(ctx)
+
+}  // extern "C"

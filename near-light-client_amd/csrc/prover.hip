@@ -932,6 +932,8 @@ int32_t nlx_quotient_eval(nlx_circuit* c, const nlx_commit* wires, const nlx_com
     const nlx_circuit_desc& d = c->d;
     if (d.num_luts) return ctx->fail(NLX_E_UNSUPPORTED, "circuits with lookup tables are proved through nlx_prove (the stage calls carry no lookup challenges)");
     if (wires->ctx != ctx || zs->ctx != ctx) return ctx->fail(NLX_E_INVAL, "commitments belong to another context");
+    if (wires->hasher != NLX_HASHER_POSEIDON_GOLDILOCKS || zs->hasher != NLX_HASHER_POSEIDON_GOLDILOCKS)
+        return ctx->fail(NLX_E_UNSUPPORTED, "a PoseidonBN128 commitment cannot enter the Goldilocks transcript");
     if (wires->n_cols != d.num_wires || zs->n_cols != c->n_zs || wires->log_n != d.degree_bits || zs->log_n != d.degree_bits ||
         wires->rate_bits != d.rate_bits || zs->rate_bits != d.rate_bits)
         return ctx->fail(NLX_E_INVAL, "commitment shapes do not match the circuit");
@@ -955,6 +957,8 @@ int32_t nlx_fri_prove(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n
     if (n_oracles < 1 || n_oracles > 4) return ctx->fail(NLX_E_RANGE, "1..4 oracles");
     for (uint32_t o = 0; o < n_oracles; o++) {
         if (!oracles[o] || oracles[o]->ctx != ctx) return ctx->fail(NLX_E_INVAL, "oracle %u: NULL or from another context", o);
+        if (oracles[o]->hasher != NLX_HASHER_POSEIDON_GOLDILOCKS)
+            return ctx->fail(NLX_E_UNSUPPORTED, "oracle %u: a PoseidonBN128 commitment cannot enter the Goldilocks transcript", o);
         if (oracles[o]->log_n != oracles[0]->log_n || oracles[o]->rate_bits != oracles[0]->rate_bits ||
             oracles[o]->cap_height != oracles[0]->cap_height)
             return ctx->fail(NLX_E_INVAL, "oracles must share degree, rate and cap height");
