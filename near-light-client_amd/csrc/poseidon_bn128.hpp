@@ -103,19 +103,36 @@ F29_HD Fe load_rc(const uint32_t* rc, int round, int i) {
     return c;
 }
 
+// The points of a round at which permute() hands every value it has just produced to an observer: the host check
+// (tests/native/poseidon_bn128_check.cpp, `trace`) asserts the bounds of the header comment there, on this very schedule.  The
+// default observer does nothing and compiles to nothing.
+enum Stage { ON_ENTRY = 0, AFTER_CONSTANTS = 1, SBOX_OUT = 2, MDS_OUT = 3 };
+struct NoObserver {
+    F29_HD void operator()(int, const Fe&) const {}
+};
+
 // the permutation on Montgomery-form elements (each < 2^255 on entry and on exit).  ONE loop over the 64 rounds: whether the
 // other three elements pass the S-box is a wave-uniform branch, so the round's code exists once.
-F29_HD void permute(Fe (&s)[T]) {
+template <class Observer = NoObserver>
+F29_HD void permute(Fe (&s)[T], Observer obs = Observer{}) {
     const uint32_t* rc = rc_table();
 #pragma unroll 1
     for (int round = 0; round < ROUNDS; round++) {
 #pragma unroll
-        for (int i = 0; i < T; i++) s[i] = f29::add(s[i], load_rc(rc, round, i));
+        for (int i = 0; i < T; i++) {
+            obs(ON_ENTRY, s[i]);
+            s[i] = f29::add(s[i], load_rc(rc, round, i));
+            obs(AFTER_CONSTANTS, s[i]);
+        }
         s[0] = sbox(s[0]);
+        obs(SBOX_OUT, s[0]);
         if (round < RF / 2 || round >= RF / 2 + RP) {
             s[1] = sbox(s[1]);
             s[2] = sbox(s[2]);
             s[3] = sbox(s[3]);
+            obs(SBOX_OUT, s[1]);
+            obs(SBOX_OUT, s[2]);
+            obs(SBOX_OUT, s[3]);
         }
         // written out: as a loop the compiler leaves it rolled (too large to unroll) and indexes the rows through scratch
         const Fe t0 = dot4(0, s), t1 = dot4(1, s), t2 = dot4(2, s), t3 = dot4(3, s);
@@ -123,6 +140,8 @@ F29_HD void permute(Fe (&s)[T]) {
         s[1] = t1;
         s[2] = t2;
         s[3] = t3;
+#pragma unroll
+        for (int i = 0; i < T; i++) obs(MDS_OUT, s[i]);
     }
 }
 

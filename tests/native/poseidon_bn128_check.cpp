@@ -4,6 +4,9 @@
 //   dot4 I S0 S1 S2 S3   row I of the MDS product on raw limb values below 2^258 -> the raw result and whether it is < 2^255
 //   sbox X               x^5 (Montgomery) on a raw value below 2^257.5 -> the raw result and whether it is < 2^255
 //   conv A               integer below 2^256 -> Montgomery form -> canonical integer (A mod r)
+//   trace A0 A1 A2 A3    as perm, then the largest raw value over all 64 rounds at each point of a round (the state on entry,
+//                        after the constants, the S-box outputs, after the MDS rows: pbn::permute's observer stages) and
+//                        whether every limb 0..7 stayed below 2^29, so the header's bounds can be asserted mid-permutation
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -52,6 +55,31 @@ static void print_raw(const Fe& a, bool bound_ok) {   // sum v[i] 2^(29 i) as he
     printf("%s %d\n", s.c_str(), (int)(bound_ok && limbs_ok));
 }
 static bool below_2_255(const Fe& a) { return a.v[f29::NL - 1] < (1u << (255 - 29 * 8)); }   // limbs 0..7 < 2^29
+// the raw integer sum v[i] 2^(29 i) as five little-endian words, and a < b on that integer
+static void raw_words(const Fe& a, uint64_t (&w)[5]) {
+    for (int k = 0; k < 5; k++) w[k] = 0;
+    for (int i = 0; i < f29::NL; i++) {
+        const int pos = f29::LB * i, k = pos / 64, sh = pos % 64;
+        const uint64_t lo = (uint64_t)a.v[i] << sh, hi = sh ? (uint64_t)a.v[i] >> (64 - sh) : 0;
+        w[k] += lo;
+        uint64_t c = (w[k] < lo) + hi;
+        for (int j = k + 1; j < 5 && c; j++) {
+            w[j] += c;
+            c = w[j] < c;
+        }
+    }
+}
+static void keep_max(const Fe& a, uint64_t (&best)[5], bool& limbs_ok) {
+    uint64_t w[5];
+    raw_words(a, w);
+    for (int k = 4; k >= 0; k--)
+        if (w[k] != best[k]) {
+            if (w[k] > best[k])
+                for (int j = 0; j < 5; j++) best[j] = w[j];
+            break;
+        }
+    for (int i = 0; i < f29::NL - 1; i++) limbs_ok = limbs_ok && a.v[i] <= f29::MASK;
+}
 static void print_words(const uint64_t* w) {
     for (int k = 3; k >= 0; k--) printf("%016llx", (unsigned long long)w[k]);
 }
@@ -74,6 +102,28 @@ int main() {
                 print_words(w);
                 printf(i + 1 < pbn::T ? " " : "\n");
             }
+        } else if (!strcmp(op, "trace")) {
+            if (scanf("%127s %127s %127s %127s", a[0], a[1], a[2], a[3]) != 4) return 2;
+            Fe s[pbn::T];
+            for (int i = 0; i < pbn::T; i++) {
+                uint64_t w[4];
+                words_of(a[i], w);
+                s[i] = pbn::from_words(w[0], w[1], w[2], w[3]);
+            }
+            uint64_t mx[4][5] = {};
+            bool limbs_ok = true;
+            pbn::permute(s, [&](int stage, const Fe& v) { keep_max(v, mx[stage], limbs_ok); });
+            for (int i = 0; i < pbn::T; i++) {
+                uint64_t w[4];
+                pbn::to_words(s[i], w);
+                print_words(w);
+                printf(" ");
+            }
+            for (int p = 0; p < 4; p++) {
+                for (int k = 4; k >= 0; k--) printf("%016llx", (unsigned long long)mx[p][k]);
+                printf(" ");
+            }
+            printf("%d\n", (int)limbs_ok);
         } else if (!strcmp(op, "dot4")) {
             int row;
             if (scanf("%d %127s %127s %127s %127s", &row, a[0], a[1], a[2], a[3]) != 5) return 2;

@@ -117,9 +117,10 @@ def tables():
     return dict(A=A, gamma=gamma, M=M, Q=Q, rho=rho, digits=digits, seed=seed, E=E, dmax_main=dmax_main)
 
 
-def constants(tb):
+def constants(tb, deltas=None):
     """Per block: kappa_i (seed of S-box input i's recombination, i = 1 .. K-1) and kappa_0 (output 0's); then the twelve constants
-    of the layers the blocks do not cover (rcb: layer l's = what round l adds, with the carried offset settled at round 26)."""
+    of the layers the blocks do not cover (rcb: layer l's = what round l adds, with the carried offset settled at round 26).
+    `deltas` (a list, optional) receives the offset at the start of every block and, last, the one layer 26 settles."""
     rc = round_constants()
     c = [rc[i * T:(i + 1) * T] for i in range(NR)]
     M, Q, E = tb["M"], tb["Q"], tb["E"]
@@ -127,6 +128,8 @@ def constants(tb):
     blocks = []
     a = FIRST
     for _ in range(N_BLOCKS):
+        if deltas is not None:
+            deltas.append(list(delta))
         d = list(delta)
         kap = [0] * K
         for i in range(1, K):
@@ -142,6 +145,8 @@ def constants(tb):
     for l in range(1, NR):
         layer[l] = list(c[l])
     assert a == RF_HALF + RP - 1          # round 25 is the single partial round left: its layer settles delta
+    if deltas is not None:
+        deltas.append(list(delta))
     md = matvec(M, delta, P)
     layer[a + 1] = [(c[a + 1][j] + md[j]) % P for j in range(T)]
     return blocks, layer
