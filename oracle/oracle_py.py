@@ -75,6 +75,13 @@ def hash_or_noop(xs):
     return out
 
 
+def hash_no_pad(xs):
+    x = _u64(xs)
+    out = np.zeros(4, dtype=np.uint64)
+    dll().orc_hash_no_pad(_p(x) if x.size else None, ctypes.c_size_t(x.size), _p(out))
+    return out
+
+
 def two_to_one(l, r):
     out = np.zeros(4, dtype=np.uint64)
     dll().orc_two_to_one(_p(_u64(l)), _p(_u64(r)), _p(out))
@@ -271,6 +278,41 @@ class Circuit:
                 "zs_partial_values": zs, "quotient_chunk_coeffs": qc, "fri_final_values": fv,
                 "deltas": list(tr.deltas)[:4 * self.desc.num_challenges]}
         return buf[:ln].tobytes(), info
+
+    @staticmethod
+    def _challenges(xs):
+        out = np.zeros(4, dtype=np.uint64)
+        xs = [int(x) for x in xs]
+        out[:len(xs)] = xs
+        return out
+
+    def partial_products_and_zs(self, wires_values, betas, gammas):
+        """orc_partial_products_and_zs: the Zs and partial products on H, (num_challenges * (1 + num_partial_products), n)"""
+        d = self.desc
+        n = 1 << d.degree_bits
+        w = _u64(wires_values)
+        assert w.shape == (d.num_wires, n)
+        out = np.zeros((d.num_challenges * (1 + d.num_partial_products), n), dtype=np.uint64)
+        b, g = self._challenges(betas), self._challenges(gammas)   # named: the call reads them through raw pointers
+        dll().orc_partial_products_and_zs.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4
+        dll().orc_partial_products_and_zs(self.h, w.ctypes.data, b.ctypes.data, g.ctypes.data, out.ctypes.data)
+        return out
+
+    def quotient_polys(self, wires_coeffs, zs_coeffs, betas, gammas, alphas, public_inputs_hash):
+        """orc_quotient_polys: the quotient chunks' coefficients, (num_challenges * quotient_degree_factor, n)"""
+        d = self.desc
+        n = 1 << d.degree_bits
+        w, z, pih = _u64(wires_coeffs), _u64(zs_coeffs), _u64(public_inputs_hash)
+        assert w.shape == (d.num_wires, n) and z.shape == (d.num_challenges * (1 + d.num_partial_products), n) and pih.size == 4
+        out = np.zeros((d.num_challenges * d.quotient_degree_factor, n), dtype=np.uint64)
+        dll().orc_quotient_polys.restype = ctypes.c_int
+        dll().orc_quotient_polys.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 7
+        b, g, a = self._challenges(betas), self._challenges(gammas), self._challenges(alphas)
+        rc = dll().orc_quotient_polys(self.h, w.ctypes.data, z.ctypes.data, b.ctypes.data, g.ctypes.data, a.ctypes.data,
+                                      pih.ctypes.data, out.ctypes.data)
+        if rc != 0:
+            raise ValueError("orc_quotient_polys takes circuits without lookup tables")
+        return out
 
     def verify(self, proof):
         b = np.frombuffer(proof, dtype=np.uint8)

@@ -452,12 +452,117 @@ static void ext_coset_fft(gl2* v, unsigned log_n, uint64_t shift) {
     free(a);
 }
 
+/* wires_permutation_partial_products_and_zs (plonk.h) */
+void orc_partial_products_and_zs(const orc_circuit* c, const uint64_t* wires, const uint64_t* betas, const uint64_t* gammas,
+                                 uint64_t* zs_values) {
+    const orc_circuit_desc* d = &c->d;
+    const size_t n = c->n;
+    const uint32_t nc = d->num_challenges, npp = d->num_partial_products, routed = d->num_routed_wires;
+    const uint32_t chunk = d->quotient_degree_factor;
+    /* (i) per row, in parallel: cumulative chunk quotients; (ii) serial running product down the
+     * rows (Z_0 = 1, Z_{i+1} = Z_i * rowprod_i); (iii) partial products = Z_i * cumulative quotient */
+    uint64_t w_n = gl_root_of_unity(c->log_n);
+    uint32_t n_chunks = (routed + chunk - 1) / chunk;
+    for (uint32_t ci = 0; ci < nc; ci++) {
+#pragma omp parallel for schedule(static)
+        for (size_t i = 0; i < n; i++) {
+            uint64_t x = gl_pow(w_n, i);
+            uint64_t acc = 1;
+            for (uint32_t q = 0; q < n_chunks; q++) {
+                uint64_t num = 1, den = 1;
+                for (uint32_t j = q * chunk; j < (q + 1) * chunk && j < routed; j++) {
+                    uint64_t wv = wires[(size_t)j * n + i];
+                    uint64_t s_id = gl_mul(c->k_is[j], x);
+                    num = gl_mul(num, gl_add(gl_add(wv, gl_mul(betas[ci], s_id)), gammas[ci]));
+                    den = gl_mul(den, gl_add(gl_add(wv, gl_mul(betas[ci], c->sigma_values[(size_t)j * n + i])), gammas[ci]));
+                }
+                acc = gl_mul(acc, gl_mul(num, gl_inv(den)));
+                if (q + 1 < n_chunks) zs_values[(size_t)(nc + ci * npp + q) * n + i] = acc;
+                else zs_values[(size_t)ci * n + i] = acc;
+            }
+        }
+        uint64_t z_x = 1;
+        for (size_t i = 0; i < n; i++) {
+            uint64_t rowprod = zs_values[(size_t)ci * n + i];
+            zs_values[(size_t)ci * n + i] = z_x;
+            z_x = gl_mul(z_x, rowprod);
+        }
+#pragma omp parallel for schedule(static)
+        for (size_t i = 0; i < n; i++)
+            for (uint32_t q = 0; q + 1 < n_chunks; q++) {
+                uint64_t* pp = &zs_values[(size_t)(nc + ci * npp + q) * n + i];
+                *pp = gl_mul(*pp, zs_values[(size_t)ci * n + i]);
+            }
+    }
+}
+
+/* compute_quotient_polys on the opened LDE rows (bit-reversed leaves: num_wires resp. n_zs words per row, the lookup columns
+ * included) -> n_q chunks of n coefficients, column-major */
+static void quotient_chunks(const orc_circuit* c, const uint64_t* wires_leaves, const uint64_t* zs_leaves, const uint64_t* betas,
+                            const uint64_t* gammas, const uint64_t* alphas, const uint64_t* deltas, const uint64_t* lut_polys,
+                            const uint64_t* pih, uint64_t* qchunks) {
+    const orc_circuit_desc* d = &c->d;
+    const size_t n = c->n, L = c->L;
+    const uint32_t nc = d->num_challenges, npp = d->num_partial_products;
+    const uint32_t chunk = d->quotient_degree_factor;
+    uint64_t* qvals = (uint64_t*)malloc(8 * L * nc); /* column-major nc x L */
+    {
+        uint32_t rate = 1u << d->rate_bits;
+        uint64_t z_h_evals[64];
+        uint64_t g_n = gl_exp_pow2(GL_GEN, c->log_n);
+        uint64_t w_rate = gl_root_of_unity(d->rate_bits);
+        for (uint32_t r = 0; r < rate; r++) z_h_evals[r] = gl_sub(gl_mul(g_n, gl_pow(w_rate, r)), 1);
+        uint64_t w_L = gl_root_of_unity(c->log_L);
+        size_t next_step = (size_t)1 << d->rate_bits; /* quotient_degree_bits == rate_bits */
+#pragma omp parallel
+        {
+            uint64_t* tmp = (uint64_t*)malloc(8 * (3 * c->max_constraints + 64 + nc * (npp + 2 + c->n_lk_terms)));
+#pragma omp for schedule(static)
+            for (size_t i = 0; i < L; i++) {
+                uint64_t x = gl_mul(GL_GEN, gl_pow(w_L, i));
+                size_t li = gl_bitrev(i, c->log_L), ln = gl_bitrev((i + next_step) % L, c->log_L);
+                uint64_t out[4];
+                vanishing_base(c, x, i, c->cs_leaves + li * c->n_cs, wires_leaves + li * d->num_wires,
+                               zs_leaves + li * c->n_zs, zs_leaves + ln * c->n_zs, betas, gammas, alphas, deltas,
+                               lut_polys, pih,
+                               z_h_evals, tmp, out);
+                for (uint32_t ci = 0; ci < nc; ci++) qvals[(size_t)ci * L + i] = out[ci];
+            }
+            free(tmp);
+        }
+    }
+    /* coset_ifft, split into quotient_degree_factor chunks of n coefficients */
+    for (uint32_t ci = 0; ci < nc; ci++) {
+        orc_coset_ifft(qvals + (size_t)ci * L, c->log_L, GL_GEN);
+        /* trim_to_len(quotient_degree): here quotient_degree = L, nothing to trim */
+        memcpy(qchunks + (size_t)ci * chunk * n, qvals + (size_t)ci * L, 8 * n * chunk);
+    }
+    free(qvals);
+}
+
+/* compute_quotient_polys from the wires' and the Zs' coefficients (plonk.h) */
+int orc_quotient_polys(const orc_circuit* c, const uint64_t* wires_coeffs, const uint64_t* zs_coeffs, const uint64_t* betas,
+                       const uint64_t* gammas, const uint64_t* alphas, const uint64_t* public_inputs_hash,
+                       uint64_t* out_chunk_coeffs) {
+    const orc_circuit_desc* d = &c->d;
+    if (d->num_luts) return -1;
+    batch bw, bz;
+    batch_alloc(c, &bw, d->num_wires);
+    batch_alloc(c, &bz, c->n_zs);
+    orc_commit_from_coeffs(wires_coeffs, d->num_wires, c->log_n, d->rate_bits, d->cap_height, bw.leaves, bw.digests, bw.cap);
+    orc_commit_from_coeffs(zs_coeffs, c->n_zs, c->log_n, d->rate_bits, d->cap_height, bz.leaves, bz.digests, bz.cap);
+    const uint64_t deltas[16] = {0}, lut_polys[4 * 16] = {0};
+    quotient_chunks(c, bw.leaves, bz.leaves, betas, gammas, alphas, deltas, lut_polys, public_inputs_hash, out_chunk_coeffs);
+    batch_free(&bw);
+    batch_free(&bz);
+    return 0;
+}
+
 size_t orc_prove_traced(const orc_circuit* c, const uint64_t* wires, const uint64_t* public_inputs,
                         uint8_t* proof_out, size_t cap_bytes, orc_trace* tr) {
     const orc_circuit_desc* d = &c->d;
     const size_t n = c->n, L = c->L;
     const uint32_t nc = d->num_challenges, npp = d->num_partial_products, routed = d->num_routed_wires;
-    const uint32_t chunk = d->quotient_degree_factor;
     const unsigned cap_h = d->cap_height;
     wbuf w = {proof_out, 0, cap_bytes, 0};
     size_t ret = 0;
@@ -499,45 +604,9 @@ size_t orc_prove_traced(const orc_circuit* c, const uint64_t* wires, const uint6
             for (uint32_t t = 0; t < d->num_luts; t++) lut_polys[ci * d->num_luts + t] = get_lut_poly(c, t, deltas + 4 * ci);
     }
 
-    /* 4. wires_permutation_partial_products_and_zs: column order [Z_0..Z_{nc-1}, pp(0,·), pp(1,·)..] */
+    /* 4. wires_permutation_partial_products_and_zs, then the lookup columns after them */
     uint64_t* zs_values = (uint64_t*)malloc(8 * n * c->n_zs);
-    {
-        /* (i) per row, in parallel: cumulative chunk quotients; (ii) serial running product down the
-         * rows (Z_0 = 1, Z_{i+1} = Z_i * rowprod_i); (iii) partial products = Z_i * cumulative quotient */
-        uint64_t w_n = gl_root_of_unity(c->log_n);
-        uint32_t n_chunks = (routed + chunk - 1) / chunk;
-        for (uint32_t ci = 0; ci < nc; ci++) {
-#pragma omp parallel for schedule(static)
-            for (size_t i = 0; i < n; i++) {
-                uint64_t x = gl_pow(w_n, i);
-                uint64_t acc = 1;
-                for (uint32_t q = 0; q < n_chunks; q++) {
-                    uint64_t num = 1, den = 1;
-                    for (uint32_t j = q * chunk; j < (q + 1) * chunk && j < routed; j++) {
-                        uint64_t wv = wires[(size_t)j * n + i];
-                        uint64_t s_id = gl_mul(c->k_is[j], x);
-                        num = gl_mul(num, gl_add(gl_add(wv, gl_mul(betas[ci], s_id)), gammas[ci]));
-                        den = gl_mul(den, gl_add(gl_add(wv, gl_mul(betas[ci], c->sigma_values[(size_t)j * n + i])), gammas[ci]));
-                    }
-                    acc = gl_mul(acc, gl_mul(num, gl_inv(den)));
-                    if (q + 1 < n_chunks) zs_values[(size_t)(nc + ci * npp + q) * n + i] = acc;
-                    else zs_values[(size_t)ci * n + i] = acc;
-                }
-            }
-            uint64_t z_x = 1;
-            for (size_t i = 0; i < n; i++) {
-                uint64_t rowprod = zs_values[(size_t)ci * n + i];
-                zs_values[(size_t)ci * n + i] = z_x;
-                z_x = gl_mul(z_x, rowprod);
-            }
-#pragma omp parallel for schedule(static)
-            for (size_t i = 0; i < n; i++)
-                for (uint32_t q = 0; q + 1 < n_chunks; q++) {
-                    uint64_t* pp = &zs_values[(size_t)(nc + ci * npp + q) * n + i];
-                    *pp = gl_mul(*pp, zs_values[(size_t)ci * n + i]);
-                }
-        }
-    }
+    orc_partial_products_and_zs(c, wires, betas, gammas, zs_values);
     /* compute_all_lookup_polys: the rounds' (RE, SLDC_0..S-1) after the partial products in the same commitment */
     for (uint32_t ci = 0; ci < nc && c->n_lk_polys; ci++)
         compute_lookup_polys(c, wires, deltas + 4 * ci, zs_values + (size_t)(c->n_zpp + ci * (1 + c->lk.n_sldc)) * n);
@@ -549,42 +618,9 @@ size_t orc_prove_traced(const orc_circuit* c, const uint64_t* wires, const uint6
     for (uint32_t i = 0; i < nc; i++) alphas[i] = orc_ch_challenge(&ch);
 
     /* 5. compute_quotient_polys */
-    uint64_t* qvals = (uint64_t*)malloc(8 * L * nc); /* column-major nc x L */
-    {
-        uint32_t rate = 1u << d->rate_bits;
-        uint64_t z_h_evals[64];
-        uint64_t g_n = gl_exp_pow2(GL_GEN, c->log_n);
-        uint64_t w_rate = gl_root_of_unity(d->rate_bits);
-        for (uint32_t r = 0; r < rate; r++) z_h_evals[r] = gl_sub(gl_mul(g_n, gl_pow(w_rate, r)), 1);
-        uint64_t w_L = gl_root_of_unity(c->log_L);
-        size_t next_step = (size_t)1 << d->rate_bits; /* quotient_degree_bits == rate_bits */
-#pragma omp parallel
-        {
-            uint64_t* tmp = (uint64_t*)malloc(8 * (3 * c->max_constraints + 64 + nc * (npp + 2 + c->n_lk_terms)));
-#pragma omp for schedule(static)
-            for (size_t i = 0; i < L; i++) {
-                uint64_t x = gl_mul(GL_GEN, gl_pow(w_L, i));
-                size_t li = gl_bitrev(i, c->log_L), ln = gl_bitrev((i + next_step) % L, c->log_L);
-                uint64_t out[4];
-                vanishing_base(c, x, i, c->cs_leaves + li * c->n_cs, bw.leaves + li * d->num_wires,
-                               bz.leaves + li * c->n_zs, bz.leaves + ln * c->n_zs, betas, gammas, alphas, deltas,
-                               lut_polys, pih,
-                               z_h_evals, tmp, out);
-                for (uint32_t ci = 0; ci < nc; ci++) qvals[(size_t)ci * L + i] = out[ci];
-            }
-            free(tmp);
-        }
-    }
-    /* coset_ifft, split into quotient_degree_factor chunks of n coefficients */
     uint64_t* qchunks = (uint64_t*)malloc(8 * n * c->n_q);
+    quotient_chunks(c, bw.leaves, bz.leaves, betas, gammas, alphas, deltas, lut_polys, pih, qchunks);
     int degree_ok = 1;
-    for (uint32_t ci = 0; ci < nc; ci++) {
-        orc_coset_ifft(qvals + (size_t)ci * L, c->log_L, GL_GEN);
-        /* trim_to_len(quotient_degree): here quotient_degree = L, nothing to trim */
-        memcpy(qchunks + (size_t)ci * chunk * n, qvals + (size_t)ci * L, 8 * n * chunk);
-    }
-    (void)degree_ok;
-    free(qvals);
     if (tr && tr->quotient_chunk_coeffs) memcpy(tr->quotient_chunk_coeffs, qchunks, 8 * n * c->n_q);
     batch_alloc(c, &bq, c->n_q);
     memcpy(bq.coeffs, qchunks, 8 * n * c->n_q);

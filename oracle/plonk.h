@@ -118,6 +118,19 @@ size_t orc_prove(const orc_circuit* c, const uint64_t* wires, const uint64_t* pu
 /* verify(): 1 = accept, <= 0 = reject (negative values name the failing check) */
 int orc_verify(const orc_circuit* c, const uint8_t* proof, size_t len);
 
+/* plonk::prover::wires_permutation_partial_products_and_zs: the Zs and partial products (not the lookup columns) from the
+ * witness on H.  wires_values: num_wires x n column-major; out_values: num_challenges * (1 + num_partial_products) x n
+ * column-major, [Z_0 .. Z_{nc-1}, pp(0, 0 ..), pp(1, 0 ..) ..].  orc_prove_traced computes its Zs with it. */
+void orc_partial_products_and_zs(const orc_circuit* c, const uint64_t* wires_values, const uint64_t* betas,
+                                 const uint64_t* gammas, uint64_t* out_values);
+/* plonk::prover::compute_quotient_polys from the coefficients of the wires (num_wires x n) and of the Zs and partial products
+ * (num_challenges * (1 + num_partial_products) x n), both column-major: out_chunk_coeffs, num_challenges *
+ * quotient_degree_factor chunks of n coefficients, column-major.  orc_prove_traced runs the same evaluation on the LDE rows it
+ * has committed.  0 = ok, -1 = a circuit with lookup tables (their terms need the lookup challenges). */
+int orc_quotient_polys(const orc_circuit* c, const uint64_t* wires_coeffs, const uint64_t* zs_coeffs, const uint64_t* betas,
+                       const uint64_t* gammas, const uint64_t* alphas, const uint64_t* public_inputs_hash,
+                       uint64_t* out_chunk_coeffs);
+
 /* stage-level access for stage-by-stage parity tests */
 typedef struct {
     uint64_t betas[4], gammas[4], alphas[4];
