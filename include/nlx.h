@@ -272,7 +272,10 @@ int32_t nlx_commit_from_coeffs(nlx_ctx* ctx, const uint64_t* coeffs, size_t n_co
 /* The same with the Merkle tree's hasher chosen: NLX_HASHER_POSEIDON_GOLDILOCKS is exactly the entries above,
  * NLX_HASHER_POSEIDON_BN128 hashes leaves (hash_or_noop of the LDE row) and nodes with PoseidonBN128; its digests have the
  * Goldilocks layout, so nlx_commit_get_* / open_rows / eval_at work unchanged.  Any other value: NLX_E_RANGE.  A BN128
- * commitment cannot feed a Goldilocks transcript: nlx_quotient_eval and nlx_fri_prove return NLX_E_UNSUPPORTED for it.
+ * commitment cannot feed a Goldilocks transcript: nlx_quotient_eval on a Goldilocks circuit and nlx_fri_prove return
+ * NLX_E_UNSUPPORTED for it (a BN128 circuit, nlx_circuit_build_hasher, and nlx_fri_prove_hasher take it).
+ * Merkle levels of at most T parents run a lane-split kernel (four lanes per permutation; same digests): T is a constant of the
+ * library that the environment variable NLX_PBN_QUAD_MAX_PARENTS, read at nlx_ctx_create, overrides (0 = never).
  * Kernel-timing names: "hash_lde_leaves_bn128" and "merkle_levels_bn128", units BN128 permutations. */
 #define NLX_HASHER_POSEIDON_GOLDILOCKS 0
 #define NLX_HASHER_POSEIDON_BN128 1
@@ -397,6 +400,19 @@ typedef struct nlx_circuit nlx_circuit;
  * both column-major subgroup evaluations, and keeps everything the prover needs resident in HBM. */
 int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants,
                           const uint64_t* sigmas, nlx_circuit** out);
+/* The same with the config's Hasher chosen (NLX_HASHER_*): NLX_HASHER_POSEIDON_GOLDILOCKS is the entry above.
+ * NLX_HASHER_POSEIDON_BN128 is plonky2x's PoseidonBN128GoldilocksConfig (the wrapper circuit's config; rules recalled, not pinned
+ * against Rust output - tools/bn128_config_model.py): every Merkle tree of the proof hashes with
+ * PoseidonBN128, a digest enters the transcript as five Goldilocks limbs (7, 7, 7, 7, 4 little-endian bytes), the challenger's
+ * sponge, the public-inputs hash and the proof of work stay Goldilocks Poseidon, the circuit digest is a BN128 digest, and the
+ * proof bytes keep their layout (a digest = four little-endian words).  Such a circuit goes through the prove, batch-prove,
+ * digest, cap and stage entries like any other; its stage commitments are BN128 commitments.
+ * Any other hasher: NLX_E_RANGE.  NLX_E_UNSUPPORTED under BN128 for circuits with lookup tables and for shapes with an oracle of
+ * 4 columns or fewer (num_challenges * quotient_degree_factor <= 4: such a leaf is its own digest and has none when >= r). */
+int32_t nlx_circuit_build_hasher(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants,
+                                 const uint64_t* sigmas, uint32_t hasher, nlx_circuit** out);
+/* the circuit's NLX_HASHER_* (NLX_E_INVAL for NULL) */
+int32_t nlx_circuit_hasher(const nlx_circuit* c);
 void nlx_circuit_destroy(nlx_circuit* c);
 int32_t nlx_circuit_digest(const nlx_circuit* c, uint64_t out[4]);
 int32_t nlx_circuit_constants_sigmas_cap(const nlx_circuit* c, uint64_t* cap_out);
@@ -404,7 +420,11 @@ size_t nlx_proof_max_bytes(const nlx_circuit* c);
 
 /* prove_with_partition_witness + ProofWithPublicInputs::to_bytes.
  * wires: num_wires x n column-major (host or device).  proof_out: host buffer of proof_cap bytes.
- * Fails with NLX_E_INVAL if the witness does not satisfy the circuit (quotient degree check). */
+ * Under NLX_HASHER_POSEIDON_GOLDILOCKS the witness is not checked against the circuit (with quotient_degree_factor = 2^rate_bits
+ * plonky2's quotient degree check is vacuous): an unsatisfied witness yields a proof that a verifier rejects.  A circuit built
+ * with NLX_HASHER_POSEIDON_BN128 fails with NLX_E_INVAL instead, here and in nlx_quotient_eval, when the top
+ * quotient_degree_factor coefficients of a quotient polynomial are not zero: a check against wrong
+ * witnesses, not a verifier. */
 int32_t nlx_prove(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_inputs, uint8_t* proof_out,
                   size_t proof_cap, size_t* proof_len);
 
@@ -436,6 +456,10 @@ typedef struct {
 void nlx_challenger_init(nlx_challenger* c);
 int32_t nlx_challenger_observe(nlx_challenger* c, const uint64_t* elements, size_t n);
 int32_t nlx_challenger_challenge(nlx_challenger* c, uint64_t* out, size_t n);
+/* Challenger::observe_hash / observe_cap (host only): n_digests digests of four words each.  NLX_HASHER_POSEIDON_GOLDILOCKS: the
+ * four words are the elements.  NLX_HASHER_POSEIDON_BN128: each digest enters as five Goldilocks elements, its 32 little-endian
+ * bytes cut into chunks of 7, 7, 7, 7 and 4; a digest >= r: NLX_E_RANGE, nothing observed.  Other hashers: NLX_E_RANGE. */
+int32_t nlx_challenger_observe_hash(nlx_challenger* c, const uint64_t* digests, size_t n_digests, uint32_t hasher);
 /* PoseidonHash::hash_no_pad on the host (public-inputs hash, circuit digest) */
 int32_t nlx_hash_no_pad(const uint64_t* elements, size_t n, uint64_t out[4]);
 
@@ -456,6 +480,14 @@ int32_t nlx_fri_prove(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n
                       const uint64_t zeta[2], const uint64_t* openings_zeta, const uint64_t* openings_next,
                       const nlx_fri_params* params, nlx_challenger* challenger, uint8_t* proof_out, size_t proof_cap,
                       size_t* proof_len);
+
+/* The same with the hasher of the commit-phase Merkle trees and of cap observation chosen; every oracle must carry that hasher
+ * (NLX_E_UNSUPPORTED otherwise; an unknown hasher: NLX_E_RANGE).  Hasher 0 is the entry above.  Kernel-timing names of the BN128
+ * commit phase: "fri_leaves_bn128" and "fri_merkle_levels_bn128", units BN128 permutations. */
+int32_t nlx_fri_prove_hasher(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n_oracles, const uint32_t* n_next,
+                             const uint64_t zeta[2], const uint64_t* openings_zeta, const uint64_t* openings_next,
+                             const nlx_fri_params* params, uint32_t hasher, nlx_challenger* challenger, uint8_t* proof_out,
+                             size_t proof_cap, size_t* proof_len);
 
 /* a13: plonky2x LocalProver::batch_prove.  Proves n_jobs independent jobs with n_workers concurrent
  * workers.  workers[i] are circuits built from the SAME description on DISTINCT contexts (one stream +

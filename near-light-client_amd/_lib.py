@@ -112,6 +112,9 @@ SIGNATURES = {
     "nlx_commit_get_leaves": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_commit_get_digests": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_circuit_build": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
+    "nlx_circuit_build_hasher": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                  c_void_pp]),
+    "nlx_circuit_hasher": (ctypes.c_int32, [ctypes.c_void_p]),
     "nlx_circuit_destroy": (None, [ctypes.c_void_p]),
     "nlx_circuit_digest": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_circuit_constants_sigmas_cap": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -124,11 +127,15 @@ SIGNATURES = {
                                            ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
     "nlx_challenger_init": (None, [ctypes.c_void_p]),
     "nlx_challenger_observe": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
+    "nlx_challenger_observe_hash": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]),
     "nlx_challenger_challenge": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]),
     "nlx_hash_no_pad": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "nlx_fri_prove": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "nlx_fri_prove_hasher": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "nlx_batch_prove": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
     "nlx_prove_stage_times": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p,
                                                ctypes.c_void_p]),

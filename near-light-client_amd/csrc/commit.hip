@@ -122,7 +122,7 @@ int32_t commit_build(nlx_ctx* ctx, const uint64_t* d_in, size_t in_stride, Commi
         launch_pbn_hash_lde_leaves(st, c->lde, L, n_cols, log_n, rate_bits, c->digests, d_bad);
         ctx->end_kernel();
         ctx->begin_kernel("merkle_levels_bn128", 64.0 * L, (double)L - (double)((size_t)1 << cap_height));
-        c->cap = launch_pbn_merkle_levels(st, c->digests, L, cap_height);
+        c->cap = launch_pbn_merkle_levels(st, c->digests, L, cap_height, ctx->pbn_quad_max_parents);
         ctx->end_kernel();
     } else if (grouped) {
         // permutations: every run's ceil(len / 8), then ceil(4 K / 8) per leaf over the runs' digests

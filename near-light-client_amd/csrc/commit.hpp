@@ -46,7 +46,12 @@ nlx_commit commit_view(const nlx_commit* c, uint32_t k);
 void launch_pbn_hash_lde_leaves(hipStream_t st, const uint64_t* d_lde, size_t col_stride, uint32_t n_cols, unsigned log_n,
                                 unsigned rate_bits, uint64_t* d_digests, uint32_t* d_bad);
 // levels down to the cap with two_to_one; returns the cap level inside d_digests
-const uint64_t* launch_pbn_merkle_levels(hipStream_t st, uint64_t* d_digests, size_t n_leaves, unsigned cap_height);
+// (levels of at most quad_max_parents parents through the lane-split kernel)
+const uint64_t* launch_pbn_merkle_levels(hipStream_t st, uint64_t* d_digests, size_t n_leaves, unsigned cap_height,
+                                         size_t quad_max_parents);
+// commit-phase leaf digests of a FRI layer (launch_fri_leaves' index map and layout), hash_no_pad of the 2 arity words of a coset
+void launch_pbn_fri_leaves(hipStream_t st, const uint64_t* d_values, unsigned log_n, unsigned rate_bits, unsigned arity_bits,
+                           uint64_t* d_digests, size_t quad_max_leaves);
 // a zeroed device word for the BN128 kernels' range flag, and its read-back once the stream has run (synchronises)
 struct RangeFlag {
     nlx_ctx* ctx;

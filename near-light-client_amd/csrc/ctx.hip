@@ -2,6 +2,7 @@
 // lazily built twiddle / coset-scale tables.
 #include "ctx.hpp"
 #include <stdexcept>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include "gl.hpp"
@@ -245,6 +246,8 @@ int32_t nlx_ctx_create(int device, nlx_ctx** out) NLX_TRY {
         return NLX_E_HIP;
     }
     c->stream = c->own_stream;
+    c->pbn_quad_max_parents = nlx::PBN_QUAD_MAX_PARENTS_DEFAULT;
+    if (const char* e = getenv("NLX_PBN_QUAD_MAX_PARENTS")) c->pbn_quad_max_parents = (size_t)strtoull(e, nullptr, 10);
     *out = c;
     return NLX_OK;
 } NLX_CATCH(nullptr)

@@ -45,6 +45,10 @@ struct nlx_ctx {
     void begin_kernel(const char* name, double alg_bytes, double units = 0.0);  // units: work items other than bytes (Poseidon permutations)
     void end_kernel();
 
+    // PoseidonBN128 Merkle levels (and FRI leaf layers) of at most this many parents run the lane-split kernels
+    // (poseidon_bn128.hip); set at creation: NLX_PBN_QUAD_MAX_PARENTS overrides PBN_QUAD_MAX_PARENTS_DEFAULT, 0 = never
+    size_t pbn_quad_max_parents = 0;
+
     // pinned staging buffer for small device->host reads
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -76,6 +80,12 @@ struct nlx_ctx {
 // function-try-block:   int32_t nlx_foo(nlx_ctx* ctx, ...) NLX_TRY { ... } NLX_CATCH(ctx)
 // std::bad_alloc -> NLX_E_NOMEM, anything else -> NLX_E_INVAL, with nlx_last_error set when the call has a context.
 namespace nlx {
+// T of the lane-split dispatch (nlx_ctx::pbn_quad_max_parents).  Measured on MI355X (tools/bench_prove_bn128.py, "levels" of
+// profiles/bn128_prove_bench.json; both kernels interleaved in one process, median of 5): k_pbn_merkle_level_quad takes 158 us
+// up to 2^8 parents, 181 us at 2^14 and 303 us at 2^15, k_pbn_merkle_level 368 - 379 us from 2^6 to 2^15 (spread within a size
+// below 3 % there); at 2^16 the lane-split kernel is the slower one (560 against 396 us).  2^15 is the largest size at which it
+// wins (1.24x; an earlier run of the same table gave 319 against 396 us there, and 613 against 431 us at 2^16).
+constexpr size_t PBN_QUAD_MAX_PARENTS_DEFAULT = (size_t)1 << 15;
 extern std::atomic<int> batch_spawn_fault_after;   // ctx.hip
 inline void on_exception(nlx_ctx* ctx, const char* what) noexcept {
     if (!ctx) return;

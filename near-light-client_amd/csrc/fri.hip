@@ -110,12 +110,23 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
         uint64_t* dg = dalloc(merkle_digest_words(n_leaves, cap_h) * 8);
         FRI_ALLOC(dg);
         layer_digests[r] = dg;
-        if (n_leaves <= ((size_t)1 << 13)) launch_fri_leaves_wide(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg);
-        else launch_fri_leaves(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg);
-        const uint64_t* d_cap = launch_merkle_levels(st, dg, n_leaves, cap_h);
+        const uint64_t* d_cap;
+        if (a.hasher == NLX_HASHER_POSEIDON_BN128) {
+            // units: BN128 permutations - ceil(2 arity / 9) per leaf, one per interior node
+            ctx->begin_kernel("fri_leaves_bn128", (16.0 * arity + 32.0) * n_leaves, (double)n_leaves * ((2 * arity + 8) / 9));
+            launch_pbn_fri_leaves(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg, ctx->pbn_quad_max_parents);
+            ctx->end_kernel();
+            ctx->begin_kernel("fri_merkle_levels_bn128", 64.0 * n_leaves, n_leaves > ((size_t)1 << cap_h) ? (double)n_leaves - (double)((size_t)1 << cap_h) : 0.0);
+            d_cap = launch_pbn_merkle_levels(st, dg, n_leaves, cap_h, ctx->pbn_quad_max_parents);
+            ctx->end_kernel();
+        } else {
+            if (n_leaves <= ((size_t)1 << 13)) launch_fri_leaves_wide(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg);
+            else launch_fri_leaves(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg);
+            d_cap = launch_merkle_levels(st, dg, n_leaves, cap_h);
+        }
         FRI_CHECK(fetch(ctx, cap.data(), d_cap, capw * 8));
         w.u64s(cap.data(), capw);
-        ch.observe(cap.data(), capw);
+        if (observe_hash(a.hasher, ch, cap.data(), capw / 4)) return ctx->fail(NLX_E_RANGE, "FRI: a commit-phase cap digest is not canonical");
         uint64_t beta[2];
         ch.ext_challenge(beta);
         uint64_t* nxt = (r == 0) ? d_fri_b : dalloc(((size_t)16 << (ln - a.arity_bits + a.rate_bits)) + 256);

@@ -29,6 +29,7 @@ struct FriProveArgs {
     uint32_t n_queries = 0, n_rounds = 0;
     const uint64_t* d_coset_base = nullptr;  // device: g * w_L^r, r < 2^rate_bits
     const uint64_t* d_wA_inv = nullptr;      // device: w_A^-i, i < 2^arity_bits
+    uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS;   // of the commit-phase trees and of cap observation (the oracles carry the same)
 };
 
 // Draws fri_alpha, runs combine / commit phase / proof of work / queries and appends the FriProof

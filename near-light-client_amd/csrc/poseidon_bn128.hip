@@ -1,10 +1,12 @@
 // PoseidonBN128 kernels for gfx950 (the Merkle hash of plonky2x's PoseidonBN128GoldilocksConfig; spec: tools/gen_poseidon_bn128.py,
 // DESIGN.md §16): batched permutation, hash_or_noop of row-major rows and of the rows of a commitment's LDE table, Merkle levels
-// with two_to_one - and their C-ABI entry points.
+// with two_to_one, the commit-phase leaves of a FRI layer - and their C-ABI entry points.
 //
 // One state per lane: four Fr elements on nine 29-bit limbs in Montgomery form (36 VGPRs), the permutation of
 // poseidon_bn128.hpp (round constants by scalar loads, one loop over the 64 rounds).  Digests leave the kernels canonical, four
 // little-endian u64 words each, so cap / digest / path buffers have the shapes of the Goldilocks ones.
+// Short Merkle levels and FRI leaf layers (at most nlx_ctx::pbn_quad_max_parents items) run the lane-split form instead: one state
+// per quad of lanes (pbn::permute_quad), for the latency of a launch that does not fill the chip.
 // A <= 4-element input whose packed value is not below r has no digest (plonky2x's from_bytes fails there): the kernel sets
 // *bad and the entry point returns NLX_E_RANGE.
 #include <hip/hip_runtime.h>
@@ -148,6 +150,88 @@ __global__ __launch_bounds__(256) void k_pbn_merkle_level(const uint64_t* __rest
     pbn_store(parents, i, s[0]);
 }
 
+// the same level with one parent per quad of lanes (pbn::permute_quad): lane q holds element q of [0, 0, a, b]
+__global__ __launch_bounds__(256) void k_pbn_merkle_level_quad(const uint64_t* __restrict__ children, uint64_t* __restrict__ parents,
+                                                               size_t n_parents) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t q = (uint32_t)(t & 3);
+    const bool live = (t >> 2) < n_parents;
+    const size_t i = live ? t >> 2 : n_parents - 1;   // spare quads redo the last parent and store nothing: a quad stays whole
+    const ulonglong2* src = reinterpret_cast<const ulonglong2*>(children + i * 8 + (q & 1) * 4);
+    const ulonglong2 a0 = src[0], a1 = src[1];
+    Fe s = pbn::from_words(a0.x, a0.y, a1.x, a1.y);
+#pragma unroll
+    for (int l = 0; l < pbn::NL; l++) s.v[l] = q >= 2 ? s.v[l] : 0u;
+    const pbn::QuadRow row = pbn::quad_row(q);
+    pbn::permute_quad(s, q, row);
+    if (live && q == 0) pbn_store(parents, i, s);
+}
+
+// Commit-phase leaf digests of a FRI layer (the index maps and the output layout of k_fri_leaves, prover_kernels.hip): the
+// leaf's 2 arity words in slot order, hash_no_pad: ceil(2 arity / 9) = 1, 2 or 4 permutations.  Word w of a leaf is component
+// w & 1 of the extension element in slot w >> 1.
+__device__ __forceinline__ uint64_t pbn_fri_word(const uint64_t* __restrict__ v, size_t np, uint32_t w, int arity_bits) {
+    const uint32_t mm = __brev(w >> 1) >> (32 - arity_bits);
+    return gl::canon(v[((size_t)mm * np) * 2 + (w & 1)]);
+}
+template <int ARITY_BITS>
+__global__ __launch_bounds__(256) void k_pbn_fri_leaves(const uint64_t* __restrict__ values, unsigned log_n, unsigned rate_bits,
+                                                        uint64_t* __restrict__ digests) {
+    constexpr uint32_t WORDS = 2u << ARITY_BITS;
+    const unsigned log_np = log_n - ARITY_BITS;
+    const size_t jp = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (jp >> (log_np + rate_bits)) return;
+    const size_t np = (size_t)1 << log_np, n = (size_t)1 << log_n;
+    const uint32_t r = (uint32_t)(jp >> log_np), kp = (uint32_t)(jp & (np - 1));
+    const uint64_t* v = values + ((size_t)r * n + kp) * 2;
+    Fe s[pbn::T];
+#pragma unroll
+    for (int i = 0; i < pbn::T; i++) s[i] = f29::zero();
+#pragma unroll 1
+    for (uint32_t c = 0; c < WORDS; c += pbn::CHUNK) {
+        const uint32_t rem = WORDS - c;
+        uint64_t e[pbn::CHUNK];
+#pragma unroll
+        for (int j = 0; j < pbn::CHUNK; j++) e[j] = (uint32_t)j < rem ? pbn_fri_word(v, np, c + j, ARITY_BITS) : 0;
+        pbn_absorb(s, e, rem);
+        pbn::permute(s);
+    }
+    const size_t leaf = ((size_t)gl::bitrev32(r, rate_bits) << log_np) + gl::bitrev32(kp, log_np);
+    pbn_store(digests, leaf, s[0]);
+}
+// the same with one leaf per quad: lane q >= 1 packs group q - 1 of the chunk into its slot, lane 0 keeps the capacity slot
+template <int ARITY_BITS>
+__global__ __launch_bounds__(256) void k_pbn_fri_leaves_quad(const uint64_t* __restrict__ values, unsigned log_n, unsigned rate_bits,
+                                                             uint64_t* __restrict__ digests) {
+    constexpr uint32_t WORDS = 2u << ARITY_BITS;
+    const unsigned log_np = log_n - ARITY_BITS;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t q = (uint32_t)(t & 3);
+    const size_t n_leaves = (size_t)1 << (log_np + rate_bits);
+    const bool live = (t >> 2) < n_leaves;
+    const size_t jp = live ? t >> 2 : n_leaves - 1;
+    const size_t np = (size_t)1 << log_np, n = (size_t)1 << log_n;
+    const uint32_t r = (uint32_t)(jp >> log_np), kp = (uint32_t)(jp & (np - 1));
+    const uint64_t* v = values + ((size_t)r * n + kp) * 2;
+    const pbn::QuadRow row = pbn::quad_row(q);
+    const uint32_t g3 = 3 * ((q + 3) & 3);   // first word of this lane's group within a chunk (lane 0: past every chunk)
+    Fe s = f29::zero();
+#pragma unroll 1
+    for (uint32_t c = 0; c < WORDS; c += pbn::CHUNK) {
+        const uint32_t rem = WORDS - c;
+        const bool mine = q != 0 && g3 < rem;
+        uint64_t e[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) e[j] = (mine && g3 + j < rem) ? pbn_fri_word(v, np, c + g3 + j, ARITY_BITS) : 0;
+        const Fe in = pbn::from_gl3(e[0], e[1], e[2]);
+#pragma unroll
+        for (int l = 0; l < pbn::NL; l++) s.v[l] = mine ? in.v[l] : s.v[l];
+        pbn::permute_quad(s, q, row);
+    }
+    const size_t leaf = ((size_t)gl::bitrev32(r, rate_bits) << log_np) + gl::bitrev32(kp, log_np);
+    if (live && q == 0) pbn_store(digests, leaf, s);
+}
+
 // ---- host launchers (stream-ordered, no synchronisation); `bad`: a device word the caller zeroed ----
 static unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -158,20 +242,37 @@ void launch_pbn_hash_lde_leaves(hipStream_t st, const uint64_t* d_lde, size_t co
                        d_digests, d_bad);
 }
 
-// level-major digests from the leaf level down to the cap level; returns the cap inside d_digests.  Every level is one launch
-// with one lane per parent: below ~2^16 parents a level no longer fills the chip and costs one permutation's latency.
-const uint64_t* launch_pbn_merkle_levels(hipStream_t st, uint64_t* d_digests, size_t n_leaves, unsigned cap_height) {
+// level-major digests from the leaf level down to the cap level; returns the cap inside d_digests.  Every level is one launch:
+// below ~2^16 parents a level no longer fills the chip and costs one permutation's latency, which the lane-split kernel shortens.
+// Levels of at most quad_max_parents parents go through the lane-split kernel (nlx_ctx::pbn_quad_max_parents).
+const uint64_t* launch_pbn_merkle_levels(hipStream_t st, uint64_t* d_digests, size_t n_leaves, unsigned cap_height,
+                                         size_t quad_max_parents) {
     const size_t cap = (size_t)1 << cap_height;
     uint64_t* cur = d_digests;
     size_t lvl = n_leaves;
     while (lvl > cap) {
         uint64_t* nxt = cur + lvl * 4;
         const size_t half = lvl >> 1;
-        hipLaunchKernelGGL(k_pbn_merkle_level, dim3(blocks_of(half)), dim3(256), 0, st, cur, nxt, half);
+        if (half <= quad_max_parents) hipLaunchKernelGGL(k_pbn_merkle_level_quad, dim3(blocks_of(4 * half)), dim3(256), 0, st, cur, nxt, half);
+        else hipLaunchKernelGGL(k_pbn_merkle_level, dim3(blocks_of(half)), dim3(256), 0, st, cur, nxt, half);
         cur = nxt;
         lvl = half;
     }
     return cur;
+}
+
+void launch_pbn_fri_leaves(hipStream_t st, const uint64_t* d_values, unsigned log_n, unsigned rate_bits, unsigned arity_bits,
+                           uint64_t* d_digests, size_t quad_max_leaves) {
+    const size_t leaves = (size_t)1 << (log_n - arity_bits + rate_bits);
+    const bool quad = leaves <= quad_max_leaves;
+    const dim3 grid(blocks_of(quad ? 4 * leaves : leaves)), block(256);
+#define NLX_PBN_FRI(AB)                                                                                                   \
+    if (quad) hipLaunchKernelGGL(k_pbn_fri_leaves_quad<AB>, grid, block, 0, st, d_values, log_n, rate_bits, d_digests);   \
+    else hipLaunchKernelGGL(k_pbn_fri_leaves<AB>, grid, block, 0, st, d_values, log_n, rate_bits, d_digests)
+    if (arity_bits == 4) { NLX_PBN_FRI(4); }
+    else if (arity_bits == 3) { NLX_PBN_FRI(3); }
+    else if (arity_bits == 2) { NLX_PBN_FRI(2); }
+#undef NLX_PBN_FRI
 }
 
 }  // namespace nlx
@@ -243,7 +344,9 @@ int32_t nlx_poseidon_bn128_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, si
     if (!rc) {
         hipLaunchKernelGGL(k_pbn_hash_rows, dim3(blocks_of(n_leaves)), dim3(256), 0, ctx->stream, in.as<uint64_t>(),
                            (uint32_t)leaf_len, n_leaves, d_dig, bad.d);
-        const uint64_t* d_cap = launch_pbn_merkle_levels(ctx->stream, d_dig, n_leaves, cap_height);
+        ctx->begin_kernel("merkle_levels_bn128", 64.0 * n_leaves, (double)n_leaves - (double)((size_t)1 << cap_height));
+        const uint64_t* d_cap = launch_pbn_merkle_levels(ctx->stream, d_dig, n_leaves, cap_height, ctx->pbn_quad_max_parents);
+        ctx->end_kernel();
         const hipError_t le = hipGetLastError();
         rc = le != hipSuccess ? ctx->hip_fail(le, "kernel launch") : bad.check("nlx_poseidon_bn128_merkle_build");
         if (!rc) {

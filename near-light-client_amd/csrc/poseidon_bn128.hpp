@@ -34,6 +34,7 @@ static_assert(NLX_PBN_T == 4, "the round below is written out for width 4");
 
 #if defined(__HIP__)
 __constant__ static const uint32_t RC_DEV[ROUNDS * T * NL] = NLX_PBN_RC_INIT;
+__constant__ static const uint32_t MDS_DEV[T * T * NL] = NLX_PBN_MDS_INIT;   // the lane-split form reads its row per lane
 #endif
 static const uint32_t RC_HOST[ROUNDS * T * NL] = NLX_PBN_RC_INIT;
 
@@ -144,6 +145,72 @@ F29_HD void permute(Fe (&s)[T], Observer obs = Observer{}) {
         for (int i = 0; i < T; i++) obs(MDS_OUT, s[i]);
     }
 }
+
+#if defined(__HIP__)
+// ---- the lane-split form: four adjacent lanes hold one state, lane q = lane & 3 holding element q ----
+// For the latency-bound top of a Merkle tree, where a level has fewer parents than the chip has lanes: a round is the lane's own
+// constant, the S-box on every lane (kept on lane 0 only in a partial round: a select, no divergent branch), three quad rotations
+// of the nine limbs (DPP quad_perm, no LDS) and ONE dot4 per lane with that lane's MDS row - 513 + 414 dependent multiply-adds
+// per round where the one-lane form runs 513 + 4 x 414 (partial) or 4 x 513 + 4 x 414 (full).
+// Bit-identical to permute(): each lane's dot4 sums the same four products into the same columns (the rotation only reorders
+// exact 64-bit additions) and each S-box sees the same operand, so the lazy-reduction bounds of the header comment carry over
+// unchanged.  The round-constant index depends on the lane here, so the constant is read per lane (one 36-byte read from the
+// 144 contiguous bytes of the round, the same for all 16 quads of a wave) and the NEXT round's read is issued ahead of the S-box.
+// All four lanes of a quad must be active.
+template <int CTRL>
+__device__ __forceinline__ Fe quad_rot(const Fe& x) {   // lane q receives the value of lane (q + k) & 3 of its quad
+    Fe r;
+#pragma unroll
+    for (int l = 0; l < NL; l++) r.v[l] = (uint32_t)__builtin_amdgcn_mov_dpp((int)x.v[l], CTRL, 0xF, 0xF, true);
+    return r;
+}
+constexpr int QUAD_ROT1 = 0x39, QUAD_ROT2 = 0x4E, QUAD_ROT3 = 0x93;   // quad_perm [1,2,3,0], [2,3,0,1], [3,0,1,2]
+
+struct QuadRow {
+    uint32_t m[T][NL];   // m[k] = M[q][(q + k) & 3]: the entry that multiplies the value rotated in from k lanes up
+};
+__device__ __forceinline__ QuadRow quad_row(uint32_t q) {
+    QuadRow r;
+#pragma unroll
+    for (int k = 0; k < T; k++)
+#pragma unroll
+        for (int l = 0; l < NL; l++) r.m[k][l] = MDS_DEV[(q * T + ((q + k) & 3)) * NL + l];
+    return r;
+}
+__device__ __forceinline__ Fe dot4_quad(const QuadRow& row, const Fe (&t)[T]) {
+    uint64_t col[2 * NL];
+#pragma unroll
+    for (int k = 0; k < 2 * NL; k++) col[k] = 0;
+#pragma unroll
+    for (int j = 0; j < T; j++) {
+#pragma unroll
+        for (int a = 0; a < NL; a++) {
+            const uint64_t m = row.m[j][a];
+#pragma unroll
+            for (int b = 0; b < NL; b++) col[a + b] += m * t[j].v[b];
+        }
+    }
+    return mont_reduce(col);
+}
+// s: this lane's element (Montgomery form, < 2^255 on entry and on exit); q = lane & 3
+__device__ __forceinline__ void permute_quad(Fe& s, uint32_t q, const QuadRow& row) {
+    Fe c = load_rc(RC_DEV, 0, q);
+#pragma unroll 1
+    for (int round = 0; round < ROUNDS; round++) {
+        const Fe x = f29::add(s, c);
+        c = load_rc(RC_DEV, round + 1 < ROUNDS ? round + 1 : round, q);
+        const bool keep = q == 0 || round < RF / 2 || round >= RF / 2 + RP;
+        const Fe y = sbox(x);
+        Fe t[T];
+#pragma unroll
+        for (int l = 0; l < NL; l++) t[0].v[l] = keep ? y.v[l] : x.v[l];
+        t[1] = quad_rot<QUAD_ROT1>(t[0]);
+        t[2] = quad_rot<QUAD_ROT2>(t[0]);
+        t[3] = quad_rot<QUAD_ROT3>(t[0]);
+        s = dot4_quad(row, t);
+    }
+}
+#endif
 
 // ---- in and out ----
 F29_HD Fe to_mont(const Fe& plain) {   // plain < 2^256 -> plain R' mod r, < 2^255

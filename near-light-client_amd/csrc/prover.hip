@@ -99,6 +99,8 @@ struct nlx_circuit {
     std::vector<uint64_t> k_is;
     uint32_t n_consts_all = 0, n_cs = 0, n_zs = 0, n_q = 0, n_fri_rounds = 0, n_terms = 0, max_gate_constraints = 0;
     nlx_commit* cs = nullptr;           // constants + sigmas commitment
+    uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS;   // the config's Hasher: every Merkle tree of the proof, and how digests enter the transcript
+    uint32_t* d_bad = nullptr;          // BN128: the leaf kernels' range word (never set: oracles of <= 4 columns are refused at build)
     std::vector<uint64_t> cs_cap;       // host copy
     uint64_t* d_sigma_values = nullptr; // [routed][n]
     GateDev* d_gates = nullptr;
@@ -134,10 +136,14 @@ struct nlx_circuit {
     size_t L() const { return (size_t)1 << (d.degree_bits + d.rate_bits); }
 };
 
-extern "C" {
+namespace {
+// every commitment of a circuit's proofs carries the circuit's hasher
+int32_t commit_for(nlx_circuit* c, const uint64_t* d_in, CommitInput kind, uint32_t n_cols, nlx_commit** out) {
+    return commit_build(c->ctx, d_in, c->n(), kind, n_cols, c->d.degree_bits, c->d.rate_bits, c->d.cap_height, out, 0, 0, c->hasher, c->d_bad);
+}
 
-int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants,
-                          const uint64_t* sigmas, nlx_circuit** out) NLX_TRY {
+int32_t circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants, const uint64_t* sigmas,
+                      uint32_t hasher, nlx_circuit** out) {
     if (!ctx) return NLX_E_INVAL;
     if (!desc || !constants || !sigmas || !out || !desc->gates || !desc->k_is)
         return ctx->fail(NLX_E_INVAL, "NULL argument");
@@ -150,6 +156,17 @@ int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint
     if (d.fri_arity_bits < 2 || d.fri_arity_bits > 4) return ctx->fail(NLX_E_UNSUPPORTED, "fri_arity_bits must be in [2, 4]");
     if (d.degree_bits < d.fri_arity_bits || d.degree_bits + d.rate_bits > 30) return ctx->fail(NLX_E_RANGE, "degree_bits out of range");
     if (d.num_routed_wires > d.num_wires || d.num_routed_wires == 0) return ctx->fail(NLX_E_INVAL, "bad wire counts");
+    if (hasher != NLX_HASHER_POSEIDON_GOLDILOCKS && hasher != NLX_HASHER_POSEIDON_BN128) return ctx->fail(NLX_E_RANGE, "unknown hasher %u", hasher);
+    if (hasher == NLX_HASHER_POSEIDON_BN128) {
+        if (d.num_luts) return ctx->fail(NLX_E_UNSUPPORTED, "circuits with lookup tables are not proved under the PoseidonBN128 config");
+        // hash_or_noop: a row of <= 4 elements is its own digest and has none when it packs to a value >= r, which a random LDE
+        // row does - such an oracle cannot be committed
+        const uint32_t zs_cols = d.num_challenges * (1 + d.num_partial_products);
+        if (d.num_challenges * d.quotient_degree_factor <= 4 || zs_cols <= 4 || d.num_wires <= 4 ||
+            d.num_selectors + d.num_constants + d.num_routed_wires <= 4)
+            return ctx->fail(NLX_E_UNSUPPORTED, "PoseidonBN128 config: every oracle needs more than 4 columns (num_challenges * quotient_degree_factor = %u)",
+                             d.num_challenges * d.quotient_degree_factor);
+    }
     const uint32_t n_chunks = (d.num_routed_wires + d.quotient_degree_factor - 1) / d.quotient_degree_factor;
     if (n_chunks > 10 || n_chunks != d.num_partial_products + 1) return ctx->fail(NLX_E_INVAL, "num_partial_products mismatch");
     if (d.fri_num_queries > 128 || d.cap_height > 6) return ctx->fail(NLX_E_RANGE, "FRI parameters out of range");
@@ -212,6 +229,7 @@ int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint
     if (!c) return ctx->fail(NLX_E_NOMEM, "host allocation failed");
     c->ctx = ctx;
     c->d = d;
+    c->hasher = hasher;
     c->gates.assign(d.gates, d.gates + d.num_gates);
     for (const nlx_gate_desc& gt : c->gates) c->max_gate_constraints = std::max(c->max_gate_constraints, gate_num_constraints(gt));
     c->k_is.assign(d.k_is, d.k_is + d.num_routed_wires);
@@ -254,6 +272,11 @@ int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint
     if (rc) return fail(rc);
     rc = ctx->get_coset_scale(log_n, d.rate_bits, &c->d_inv_scale_br, true);
     if (rc) return fail(rc);
+    if (hasher == NLX_HASHER_POSEIDON_BN128) {
+        c->d_bad = (uint32_t*)ctx->alloc(256);
+        if (!c->d_bad) return fail(NLX_E_NOMEM);
+        if (hipMemsetAsync(c->d_bad, 0, 4, ctx->stream) != hipSuccess) return fail(ctx->fail(NLX_E_HIP, "hipMemsetAsync failed"));
+    }
 
     // constants ++ sigmas -> one device matrix -> commitment
     {
@@ -263,7 +286,7 @@ int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint
         hipError_t e1 = hipMemcpyAsync(d_vals, constants, cb, is_device_ptr(constants) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
         hipError_t e2 = hipMemcpyAsync((uint8_t*)d_vals + cb, sigmas, sb, is_device_ptr(sigmas) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
         if (e1 != hipSuccess || e2 != hipSuccess) { ctx->release(d_vals); return fail(ctx->hip_fail(e1 != hipSuccess ? e1 : e2, "hipMemcpyAsync")); }
-        rc = commit_build(ctx, d_vals, n, CommitInput::ValuesNatural, c->n_cs, log_n, d.rate_bits, d.cap_height, &c->cs);
+        rc = commit_for(c, d_vals, CommitInput::ValuesNatural, c->n_cs, &c->cs);
         if (rc) { ctx->release(d_vals); return fail(rc); }
         c->d_sigma_values = (uint64_t*)ctx->alloc(sb);
         if (!c->d_sigma_values) { ctx->release(d_vals); return fail(NLX_E_NOMEM); }
@@ -403,7 +426,19 @@ int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint
     if (rc) return fail(rc);
     bool zero = true;
     for (int i = 0; i < 4; i++) zero = zero && d.circuit_digest[i] == 0;
-    if (zero) {
+    if (zero && hasher == NLX_HASHER_POSEIDON_BN128) {
+        // the same under Hasher = PoseidonBN128Hash (tools/bn128_config_model.py rule 4, recalled): the cap flattened to five
+        // limbs per digest, the domain separator's BN128 digest as five limbs, degree_bits; a BN128 digest, four words
+        const size_t n_cap = c->cs_cap.size() / 4;
+        std::vector<uint64_t> parts(n_cap * BN128_DIGEST_LIMBS);
+        for (size_t i = 0; i < n_cap; i++) bn128_digest_limbs(&c->cs_cap[4 * i], &parts[i * BN128_DIGEST_LIMBS]);
+        uint64_t pad[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, dom[4], dl[BN128_DIGEST_LIMBS];
+        bn128_hash_no_pad_host(pad, 12, dom);
+        bn128_digest_limbs(dom, dl);
+        parts.insert(parts.end(), dl, dl + BN128_DIGEST_LIMBS);
+        parts.push_back(d.degree_bits);
+        bn128_hash_no_pad_host(parts.data(), parts.size(), c->d.circuit_digest);
+    } else if (zero) {
         // circuit_digest = hash_no_pad(cap || hash_pad([]) || degree_bits)   (CircuitBuilder::build)
         std::vector<uint64_t> parts(c->cs_cap);
         uint64_t pad[12] = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1}, dom[4];
@@ -416,7 +451,25 @@ int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint
         if (hipEventCreate(&c->ev[i]) != hipSuccess) return fail(ctx->fail(NLX_E_HIP, "hipEventCreate failed"));
     *out = c;
     return NLX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t nlx_circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants,
+                          const uint64_t* sigmas, nlx_circuit** out) NLX_TRY {
+    return circuit_build(ctx, desc, constants, sigmas, NLX_HASHER_POSEIDON_GOLDILOCKS, out);
 } NLX_CATCH(ctx)
+
+int32_t nlx_circuit_build_hasher(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants, const uint64_t* sigmas,
+                                 uint32_t hasher, nlx_circuit** out) NLX_TRY {
+    return circuit_build(ctx, desc, constants, sigmas, hasher, out);
+} NLX_CATCH(ctx)
+
+int32_t nlx_circuit_hasher(const nlx_circuit* c) NLX_TRY {
+    if (!c) return NLX_E_INVAL;
+    return (int32_t)c->hasher;
+} NLX_CATCH(nullptr)
 
 void nlx_circuit_destroy(nlx_circuit* c) NLX_TRY {
     if (!c) return;
@@ -433,6 +486,7 @@ void nlx_circuit_destroy(nlx_circuit* c) NLX_TRY {
     ctx->release(c->d_idx_of);
     ctx->release(c->d_mult);
     ctx->release(c->d_tabs);
+    ctx->release(c->d_bad);
     for (int i = 0; i <= NLX_MAX_STAGES; i++)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     delete c;
@@ -536,7 +590,7 @@ int32_t zs_stage(nlx_circuit* c, const uint64_t* d_wire_values, const uint64_t b
         if (c->n_lk_polys)
             launch_lookup_polys(ctx->stream, c->lk, c->d_tabs, c->h_tabs.data(), d_wire_values, n, d.num_challenges, d_deltas,
                                 d_zs + (size_t)c->n_zpp * n);
-        rc = commit_build(ctx, d_zs, n, CommitInput::ValuesNatural, c->n_zs, log_n, d.rate_bits, d.cap_height, cz);
+        rc = commit_for(c, d_zs, CommitInput::ValuesNatural, c->n_zs, cz);
     }
     // commit_build only enqueues: the inputs must outlive the stream work
     if (defer) {
@@ -550,6 +604,42 @@ int32_t zs_stage(nlx_circuit* c, const uint64_t* d_wire_values, const uint64_t b
     return rc;
 }
 
+// The quotient degree check (BN128 circuits; the Goldilocks entries keep returning a proof, as they always have).
+// plonky2's `trim_to_len(quotient_degree)` is vacuous here, the quotient being interpolated on exactly quotient_degree = R n points
+// (R = quotient_degree_factor = 2^rate_bits).  But the quotient has slack at the top: every constraint has degree at most
+// (R + 1)(n - 1) - a higher one would alias on the R n points and no proof of the circuit would verify - so for a satisfied
+// witness t = V / Z_H has degree at most R n - (R + 1) and its top R coefficients are zero.  If V = Z_H t0 + r with r != 0
+// (deg r < n), the values V / Z_H on the coset interpolate to t0 + r (1 + x^n + ... + x^((R-1) n)) / (g^(R n) - 1) exactly
+// (1 / (y - 1) = (1 + y + ... + y^(R-1)) / (G - 1) modulo y^R - G), so the top R coefficients of the last chunk are those of
+// r / (G - 1): the remainder's x^(n-R) .. x^(n-1).  A row where V != 0 contributes V(x0) (x0 / n) (x^n - 1) / (x - x0) to r, every
+// coefficient of which is non-zero, and V is a random combination (alphas, drawn after the witness is committed) of the
+// constraints: an unsatisfied witness leaves these R coefficients zero only if sum_x x^j C_k(x) = 0 for every constraint k and
+// every j = 1 .. R, or with probability ~R / p over alpha.  This is a check against wrong witnesses, not a verifier: the full
+// identity is the verifier's check at zeta.
+// Coefficient i of chunk c sits at [challenge R + c][bitrev(i)]; i = n - R + k is position rev(k) n / R + n / R - 1.
+int32_t quotient_degree_check(nlx_circuit* c, const uint64_t* d_qchunks) {
+    nlx_ctx* ctx = c->ctx;
+    const nlx_circuit_desc& d = c->d;
+    const size_t n = c->n();
+    const uint32_t R = 1u << d.rate_bits, nc = d.num_challenges;
+    if (n < 2 * (size_t)R) return NLX_OK;   // the bound above needs the top R coefficients inside the last chunk's upper half
+    uint64_t top[2 * 8];
+    const size_t stride = n / R;
+    int32_t rc = ensure_pinned(ctx, 1u << 20);
+    if (rc) return rc;
+    for (uint32_t ch = 0; ch < nc; ch++) {
+        const uint64_t* src = d_qchunks + ((size_t)ch * R + (R - 1)) * n + (stride - 1);
+        NLX_HIP(ctx, hipMemcpy2DAsync((uint64_t*)ctx->pinned + (size_t)ch * R, 8, src, stride * 8, 8, R, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(top, ctx->pinned, (size_t)nc * R * 8);
+    for (uint32_t i = 0; i < nc * R; i++)
+        if (gl::canon(top[i]) != 0)
+            return ctx->fail(NLX_E_INVAL, "the witness does not satisfy the circuit: the quotient of challenge %u has degree above %u n - %u (the vanishing polynomial is not divisible by Z_H)",
+                             i / R, R, R + 1);
+    return NLX_OK;
+}
+
 // a9: quotient polynomials (compute_quotient_polys) from the three LDE tables, committed from coefficients.
 int32_t quotient_stage(nlx_circuit* c, const nlx_commit* cw, const nlx_commit* cz, const uint64_t betas[2],
                        const uint64_t gammas[2], const uint64_t alphas[2], const uint64_t pih[4],
@@ -559,7 +649,7 @@ int32_t quotient_stage(nlx_circuit* c, const nlx_commit* cw, const nlx_commit* c
     const nlx_circuit_desc& d = c->d;
     hipStream_t st = ctx->stream;
     const unsigned log_n = d.degree_bits;
-    const size_t n = c->n(), L = c->L();
+    const size_t L = c->L();
     const uint32_t nc = d.num_challenges, npp = d.num_partial_products;
     // one alpha power per vanishing term (GateAcc reads ap[T0 + k]): Z(1) terms, permutation terms, lookup terms, gate constraints
     c->n_terms = nc + nc * (npp + 1) + nc * c->n_lk_terms + c->max_gate_constraints;
@@ -608,7 +698,15 @@ int32_t quotient_stage(nlx_circuit* c, const nlx_commit* cw, const nlx_commit* c
         launch_intt_dif_cosets(st, ctx->tables, d_qvals, nc, log_n, d.rate_bits, c->d_inv_scale_br);
         launch_quotient_chunks(st, d_qvals, d_qchunks, log_n, d.rate_bits, nc, c->d_wR_inv, c->d_chunk_scale);
         stage("commit_quotient");
-        rc = commit_build(ctx, d_qchunks, n, CommitInput::CoeffsBitrev, c->n_q, log_n, d.rate_bits, d.cap_height, cq);
+        rc = commit_for(c, d_qchunks, CommitInput::CoeffsBitrev, c->n_q, cq);
+        if (!rc && c->hasher == NLX_HASHER_POSEIDON_BN128) {
+            rc = quotient_degree_check(c, d_qchunks);
+            if (rc) {   // no commitment leaves a refused stage (its kernels are drained first)
+                (void)hipStreamSynchronize(st);
+                nlx_commit_destroy(*cq);
+                *cq = nullptr;
+            }
+        }
     }
     if (defer) {
         for (void* q : {(void*)d_alpha_pows, (void*)d_qvals, (void*)d_qchunks})
@@ -679,7 +777,7 @@ int32_t nlx_prove(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_
         if (d.num_luts)
             launch_set_lookup_wires(st, c->lk, c->d_tabs, c->h_tabs.data(), sw.as<uint64_t>(), n, c->d_mult, c->mult_words,
                                     c->d_mult + c->mult_words);
-        CHECK(commit_build(ctx, sw.as<uint64_t>(), n, CommitInput::ValuesNatural, d.num_wires, log_n, d.rate_bits, cap_h, &cw));
+        CHECK(commit_for(c, sw.as<uint64_t>(), CommitInput::ValuesNatural, d.num_wires, &cw));
         CHECK(fetch(ctx, cap.data(), cw->cap, capw * 8));
         if (d.num_luts) {
             uint32_t bad = 0;
@@ -687,9 +785,9 @@ int32_t nlx_prove(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_
             if (bad) { rc = ctx->fail(NLX_E_INVAL, "a looked-up input is not in its table (set_lookup_wires)"); goto done; }
         }
         w.u64s(cap.data(), capw);
-        ch.observe(d.circuit_digest, 4);
-        ch.observe(pih, 4);
-        ch.observe(cap.data(), capw);
+        CHECK(observe_hash(c->hasher, ch, d.circuit_digest, 1));
+        ch.observe(pih, 4);   // InnerHasher: Goldilocks Poseidon under both configs
+        CHECK(observe_hash(c->hasher, ch, cap.data(), capw / 4));
         uint64_t betas[2] = {0, 0}, gammas[2] = {0, 0}, alphas[2] = {0, 0};
         for (uint32_t i = 0; i < nc; i++) betas[i] = ch.challenge();
         for (uint32_t i = 0; i < nc; i++) gammas[i] = ch.challenge();
@@ -729,7 +827,7 @@ int32_t nlx_prove(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_
         }
         CHECK(fetch(ctx, cap.data(), cz->cap, capw * 8));
         w.u64s(cap.data(), capw);
-        ch.observe(cap.data(), capw);
+        CHECK(observe_hash(c->hasher, ch, cap.data(), capw / 4));
         for (uint32_t i = 0; i < nc; i++) alphas[i] = ch.challenge();
 
         // ---- 5. quotient ----
@@ -737,7 +835,7 @@ int32_t nlx_prove(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_
         CHECK(quotient_stage(c, cw, cz, betas, gammas, alphas, pih, d_deltas, d_deltas ? d_deltas + 8 : nullptr, &cq, stage, &scratch));
         CHECK(fetch(ctx, cap.data(), cq->cap, capw * 8));
         w.u64s(cap.data(), capw);
-        ch.observe(cap.data(), capw);
+        CHECK(observe_hash(c->hasher, ch, cap.data(), capw / 4));
 
         // ---- 6. openings ----
         stage("openings");
@@ -825,6 +923,7 @@ int32_t nlx_prove(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_
             fa.pow_bits = d.fri_pow_bits; fa.n_queries = d.fri_num_queries; fa.n_rounds = NR;
             fa.d_coset_base = c->d_coset_base;
             fa.d_wA_inv = c->d_wA_inv;
+            fa.hasher = c->hasher;
             CHECK(fri_prove(ctx, fa, ch, w, scratch, stage));
         }
         w.usize(d.num_public_inputs);  // write_proof_with_public_inputs: write_usize(len), then the field vec
@@ -932,8 +1031,9 @@ int32_t nlx_quotient_eval(nlx_circuit* c, const nlx_commit* wires, const nlx_com
     const nlx_circuit_desc& d = c->d;
     if (d.num_luts) return ctx->fail(NLX_E_UNSUPPORTED, "circuits with lookup tables are proved through nlx_prove (the stage calls carry no lookup challenges)");
     if (wires->ctx != ctx || zs->ctx != ctx) return ctx->fail(NLX_E_INVAL, "commitments belong to another context");
-    if (wires->hasher != NLX_HASHER_POSEIDON_GOLDILOCKS || zs->hasher != NLX_HASHER_POSEIDON_GOLDILOCKS)
-        return ctx->fail(NLX_E_UNSUPPORTED, "a PoseidonBN128 commitment cannot enter the Goldilocks transcript");
+    if (wires->hasher != c->hasher || zs->hasher != c->hasher)
+        return ctx->fail(NLX_E_UNSUPPORTED, c->hasher == NLX_HASHER_POSEIDON_GOLDILOCKS ? "a PoseidonBN128 commitment cannot enter the Goldilocks transcript"
+                                                                                        : "a Goldilocks commitment cannot enter a PoseidonBN128 circuit's proof");
     if (wires->n_cols != d.num_wires || zs->n_cols != c->n_zs || wires->log_n != d.degree_bits || zs->log_n != d.degree_bits ||
         wires->rate_bits != d.rate_bits || zs->rate_bits != d.rate_bits)
         return ctx->fail(NLX_E_INVAL, "commitment shapes do not match the circuit");
@@ -946,19 +1046,24 @@ int32_t nlx_quotient_eval(nlx_circuit* c, const nlx_commit* wires, const nlx_com
     return rc;
 } NLX_CATCH(nullptr)
 
-int32_t nlx_fri_prove(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n_oracles, const uint32_t* n_next,
+}  // extern "C"
+
+namespace {
+int32_t fri_prove_api(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n_oracles, const uint32_t* n_next,
                       const uint64_t zeta[2], const uint64_t* openings_zeta, const uint64_t* openings_next,
-                      const nlx_fri_params* params, nlx_challenger* challenger, uint8_t* proof_out, size_t proof_cap,
-                      size_t* proof_len) NLX_TRY {
+                      const nlx_fri_params* params, uint32_t hasher, nlx_challenger* challenger, uint8_t* proof_out, size_t proof_cap,
+                      size_t* proof_len) {
     if (!ctx) return NLX_E_INVAL;
+    if (hasher != NLX_HASHER_POSEIDON_GOLDILOCKS && hasher != NLX_HASHER_POSEIDON_BN128) return ctx->fail(NLX_E_RANGE, "unknown hasher %u", hasher);
     if (!oracles || !n_next || !zeta || !openings_zeta || !params || !challenger || !proof_out || !proof_len)
         return ctx->fail(NLX_E_INVAL, "NULL argument");
     *proof_len = 0;
     if (n_oracles < 1 || n_oracles > 4) return ctx->fail(NLX_E_RANGE, "1..4 oracles");
     for (uint32_t o = 0; o < n_oracles; o++) {
         if (!oracles[o] || oracles[o]->ctx != ctx) return ctx->fail(NLX_E_INVAL, "oracle %u: NULL or from another context", o);
-        if (oracles[o]->hasher != NLX_HASHER_POSEIDON_GOLDILOCKS)
-            return ctx->fail(NLX_E_UNSUPPORTED, "oracle %u: a PoseidonBN128 commitment cannot enter the Goldilocks transcript", o);
+        if (oracles[o]->hasher != hasher)
+            return ctx->fail(NLX_E_UNSUPPORTED, hasher == NLX_HASHER_POSEIDON_GOLDILOCKS ? "oracle %u: a PoseidonBN128 commitment cannot enter the Goldilocks transcript"
+                                                                                          : "oracle %u: its Merkle tree is not PoseidonBN128", o);
         if (oracles[o]->log_n != oracles[0]->log_n || oracles[o]->rate_bits != oracles[0]->rate_bits ||
             oracles[o]->cap_height != oracles[0]->cap_height)
             return ctx->fail(NLX_E_INVAL, "oracles must share degree, rate and cap height");
@@ -1000,9 +1105,10 @@ int32_t nlx_fri_prove(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n
     fa.open1 = openings_next;
     fa.log_n = log_n; fa.rate_bits = rate_bits; fa.cap_height = oracles[0]->cap_height; fa.arity_bits = params->arity_bits;
     fa.pow_bits = params->pow_bits; fa.n_queries = params->num_queries;
-    fa.n_rounds = fri_num_rounds(log_n, rate_bits, oracles[0]->cap_height, params->arity_bits, params->final_poly_bits);
+    fa.n_rounds = nlx::fri_num_rounds(log_n, rate_bits, oracles[0]->cap_height, params->arity_bits, params->final_poly_bits);
     fa.d_coset_base = d_small;
     fa.d_wA_inv = d_small + 4 * R;
+    fa.hasher = hasher;
     Challenger ch;
     memcpy(ch.state, challenger->state, sizeof ch.state);
     memcpy(ch.in_buf, challenger->input, sizeof ch.in_buf);
@@ -1023,6 +1129,25 @@ int32_t nlx_fri_prove(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n
     challenger->n_output = ch.n_out;
     *proof_len = w.len;
     return NLX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t nlx_fri_prove(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n_oracles, const uint32_t* n_next,
+                      const uint64_t zeta[2], const uint64_t* openings_zeta, const uint64_t* openings_next,
+                      const nlx_fri_params* params, nlx_challenger* challenger, uint8_t* proof_out, size_t proof_cap,
+                      size_t* proof_len) NLX_TRY {
+    return fri_prove_api(ctx, oracles, n_oracles, n_next, zeta, openings_zeta, openings_next, params, NLX_HASHER_POSEIDON_GOLDILOCKS,
+                         challenger, proof_out, proof_cap, proof_len);
+} NLX_CATCH(ctx)
+
+int32_t nlx_fri_prove_hasher(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n_oracles, const uint32_t* n_next,
+                             const uint64_t zeta[2], const uint64_t* openings_zeta, const uint64_t* openings_next,
+                             const nlx_fri_params* params, uint32_t hasher, nlx_challenger* challenger, uint8_t* proof_out,
+                             size_t proof_cap, size_t* proof_len) NLX_TRY {
+    return fri_prove_api(ctx, oracles, n_oracles, n_next, zeta, openings_zeta, openings_next, params, hasher, challenger, proof_out,
+                         proof_cap, proof_len);
 } NLX_CATCH(ctx)
 
 // plonky2::iop::challenger::Challenger on the host, for callers without their own (tests, the C example)
@@ -1036,6 +1161,22 @@ int32_t nlx_challenger_observe(nlx_challenger* c, const uint64_t* elements, size
         if (elements[i] >= gl::P) return NLX_E_RANGE;
         ch.observe(elements[i]);
     }
+    memcpy(c->state, ch.state, sizeof ch.state); memcpy(c->input, ch.in_buf, sizeof ch.in_buf);
+    memcpy(c->output, ch.out_buf, sizeof ch.out_buf); c->n_input = ch.n_in; c->n_output = ch.n_out;
+    return NLX_OK;
+} NLX_CATCH(nullptr)
+// Challenger::observe_hash / observe_cap: n_digests digests of four words under the given hasher (transcript.hpp observe_hash)
+int32_t nlx_challenger_observe_hash(nlx_challenger* c, const uint64_t* digests, size_t n_digests, uint32_t hasher) NLX_TRY {
+    if (!c || (!digests && n_digests) || c->n_input > 8 || c->n_output > 8) return NLX_E_INVAL;
+    if (hasher != NLX_HASHER_POSEIDON_GOLDILOCKS && hasher != NLX_HASHER_POSEIDON_BN128) return NLX_E_RANGE;
+    if (hasher == NLX_HASHER_POSEIDON_GOLDILOCKS)
+        for (size_t i = 0; i < 4 * n_digests; i++)
+            if (digests[i] >= gl::P) return NLX_E_RANGE;
+    Challenger ch;
+    memcpy(ch.state, c->state, sizeof ch.state); memcpy(ch.in_buf, c->input, sizeof ch.in_buf);
+    memcpy(ch.out_buf, c->output, sizeof ch.out_buf); ch.n_in = c->n_input; ch.n_out = c->n_output;
+    const int32_t rc = observe_hash(hasher, ch, digests, n_digests);
+    if (rc) return rc;
     memcpy(c->state, ch.state, sizeof ch.state); memcpy(c->input, ch.in_buf, sizeof ch.in_buf);
     memcpy(c->output, ch.out_buf, sizeof ch.out_buf); c->n_input = ch.n_in; c->n_output = ch.n_out;
     return NLX_OK;

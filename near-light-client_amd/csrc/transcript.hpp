@@ -7,6 +7,7 @@
 #include "ctx.hpp"
 #include "gl.hpp"
 #include "poseidon.hpp"
+#include "poseidon_bn128.hpp"
 
 namespace nlx {
 
@@ -41,6 +42,52 @@ struct Challenger {
         out[1] = challenge();
     }
 };
+
+// GenericHashOut::to_vec of a PoseidonBN128 digest (plonky2x plonky2_config.rs, recalled - tools/bn128_config_model.py rule 2):
+// the 32 little-endian bytes of the canonical value cut into chunks of 7, 7, 7, 7 and 4 bytes, each a Goldilocks element
+// (limbs 0..3 < 2^56, limb 4 < 2^32)
+constexpr int BN128_DIGEST_LIMBS = 5;
+inline void bn128_digest_limbs(const uint64_t w[4], uint64_t out[BN128_DIGEST_LIMBS]) {
+    constexpr uint64_t M56 = ((uint64_t)1 << 56) - 1;
+    out[0] = w[0] & M56;
+    out[1] = ((w[0] >> 56) | (w[1] << 8)) & M56;
+    out[2] = ((w[1] >> 48) | (w[2] << 16)) & M56;
+    out[3] = ((w[2] >> 40) | (w[3] << 24)) & M56;
+    out[4] = w[3] >> 32;
+}
+
+// Challenger::observe_hash / observe_cap for the config's Hasher: `n` digests of four little-endian words.  Goldilocks digests
+// are their own four elements; a BN128 digest enters as its five limbs and must be canonical (NLX_E_RANGE otherwise, nothing
+// observed).  The sponge itself stays the Goldilocks permutation under both configs.
+inline int32_t observe_hash(uint32_t hasher, Challenger& ch, const uint64_t* digests, size_t n) {
+    if (hasher == NLX_HASHER_POSEIDON_GOLDILOCKS) {
+        ch.observe(digests, 4 * n);
+        return NLX_OK;
+    }
+    for (size_t i = 0; i < n; i++)
+        if (!pbn::lt_r(digests[4 * i], digests[4 * i + 1], digests[4 * i + 2], digests[4 * i + 3])) return NLX_E_RANGE;
+    for (size_t i = 0; i < n; i++) {
+        uint64_t l[BN128_DIGEST_LIMBS];
+        bn128_digest_limbs(digests + 4 * i, l);
+        ch.observe(l, BN128_DIGEST_LIMBS);
+    }
+    return NLX_OK;
+}
+
+// PoseidonBN128Hash::hash_no_pad on the host (the circuit digest under the BN128 config: a dozen permutations, once per circuit):
+// the absorption of poseidon_bn128.hip's pbn_absorb, canonical elements in, the canonical digest out as four words
+inline void bn128_hash_no_pad_host(const uint64_t* in, size_t len, uint64_t out[4]) {
+    pbn::Fe s[pbn::T];
+    for (int i = 0; i < pbn::T; i++) s[i] = f29::zero();
+    for (size_t off = 0; off < len; off += pbn::CHUNK) {
+        uint64_t e[pbn::CHUNK] = {0};
+        const size_t k = len - off < (size_t)pbn::CHUNK ? len - off : (size_t)pbn::CHUNK;
+        for (size_t j = 0; j < k; j++) e[j] = in[off + j];
+        for (size_t g = 0; 3 * g < k; g++) s[g + 1] = pbn::from_gl3(e[3 * g], e[3 * g + 1], e[3 * g + 2]);
+        pbn::permute(s);
+    }
+    pbn::to_words(s[0], out);
+}
 
 inline void hash_no_pad_host(const uint64_t* in, size_t len, uint64_t out[4]) {
     uint64_t st[12] = {0};

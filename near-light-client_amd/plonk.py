@@ -137,12 +137,20 @@ class SyntheticCircuit:
 class CircuitData:
     """Prover-side circuit data resident on the GPU (CircuitBuilder::build output)."""
 
-    def __init__(self, ctx, desc, constants, sigmas):
+    def __init__(self, ctx, desc, constants, sigmas, hasher="poseidon_goldilocks"):
+        """hasher="poseidon_bn128": plonky2x's PoseidonBN128GoldilocksConfig (nlx_circuit_build_hasher) - every Merkle tree of
+        the proof over BN254 Fr, digests entering the transcript as five limbs"""
+        from .batch import _hasher_id
         self.ctx = ctx
         self._desc = desc  # keeps gates / k_is alive
         h = ctypes.c_void_p()
-        ctx.check(dll.nlx_circuit_build(ctx.handle, ctypes.byref(desc), ptr(constants), ptr(sigmas), ctypes.byref(h)))
+        hid = _hasher_id(hasher)
+        if hid == 0:
+            ctx.check(dll.nlx_circuit_build(ctx.handle, ctypes.byref(desc), ptr(constants), ptr(sigmas), ctypes.byref(h)))
+        else:
+            ctx.check(dll.nlx_circuit_build_hasher(ctx.handle, ctypes.byref(desc), ptr(constants), ptr(sigmas), hid, ctypes.byref(h)))
         self.handle = h
+        self._hasher = hasher
         self.cap_height = desc.cap_height
         self.num_wires = desc.num_wires
         self.n = 1 << desc.degree_bits
@@ -150,8 +158,15 @@ class CircuitData:
         ctx._adopt(self)
 
     @classmethod
-    def from_synthetic(cls, ctx, syn):
-        return cls(ctx, syn.desc(), syn.constants, syn.sigmas)
+    def from_synthetic(cls, ctx, syn, hasher="poseidon_goldilocks"):
+        return cls(ctx, syn.desc(), syn.constants, syn.sigmas, hasher=hasher)
+
+    @property
+    def hasher(self):
+        """"poseidon_goldilocks" or "poseidon_bn128" (nlx_circuit_hasher)"""
+        from .batch import HASHERS
+        hid = dll.nlx_circuit_hasher(self.handle)
+        return {v: k for k, v in HASHERS.items()}[hid]
 
     @property
     def circuit_digest(self):
@@ -250,6 +265,14 @@ class Challenger:
         if rc != 0:
             raise NlxError(rc, "nlx_challenger_observe")
 
+    def observe_hash(self, digests, hasher="poseidon_goldilocks"):
+        """Challenger::observe_hash / observe_cap: digests (n, 4) words; a BN128 digest enters as its five limbs"""
+        from .batch import _hasher_id
+        d = np.ascontiguousarray(np.asarray(digests, dtype=np.uint64).reshape(-1, 4))
+        rc = dll.nlx_challenger_observe_hash(ctypes.byref(self.s), ptr(d) if d.size else None, d.shape[0], _hasher_id(hasher))
+        if rc != 0:
+            raise NlxError(rc, "nlx_challenger_observe_hash")
+
     def challenges(self, n):
         out = np.zeros(n, dtype=np.uint64)
         rc = dll.nlx_challenger_challenge(ctypes.byref(self.s), ptr(out), n)
@@ -271,9 +294,13 @@ class FriParams(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("arity_bits", "final_poly_bits", "pow_bits", "num_queries")]
 
 
-def fri_prove(ctx, oracles, n_next, zeta, openings_zeta, openings_next, params, challenger, cap_bytes=1 << 22):
+def fri_prove(ctx, oracles, n_next, zeta, openings_zeta, openings_next, params, challenger, cap_bytes=1 << 22,
+              hasher="poseidon_goldilocks"):
     """nlx_fri_prove: oracles = PolynomialBatch list, n_next[o] = leading columns of oracle o also opened at g*zeta;
-    returns the FriProof bytes and advances `challenger`."""
+    returns the FriProof bytes and advances `challenger`.  hasher: of the commit-phase trees and of cap observation
+    (nlx_fri_prove_hasher); every oracle must carry it."""
+    from .batch import _hasher_id
+    hid = _hasher_id(hasher)
     hs = (ctypes.c_void_p * len(oracles))(*[o.handle for o in oracles])
     nn = (ctypes.c_uint32 * len(oracles))(*[int(x) for x in n_next])
     z = np.ascontiguousarray(zeta, dtype=np.uint64)
@@ -281,8 +308,13 @@ def fri_prove(ctx, oracles, n_next, zeta, openings_zeta, openings_next, params, 
     o1 = np.ascontiguousarray(np.asarray(openings_next, dtype=np.uint64).reshape(-1))
     buf = np.zeros(cap_bytes, dtype=np.uint8)
     n = ctypes.c_size_t()
-    ctx.check(dll.nlx_fri_prove(ctx.handle, hs, len(oracles), nn, ptr(z), ptr(o0), ptr(o1) if o1.size else None,
-                                ctypes.byref(params), ctypes.byref(challenger.s), buf.ctypes.data, buf.size, ctypes.byref(n)))
+    if hid == 0:
+        ctx.check(dll.nlx_fri_prove(ctx.handle, hs, len(oracles), nn, ptr(z), ptr(o0), ptr(o1) if o1.size else None,
+                                    ctypes.byref(params), ctypes.byref(challenger.s), buf.ctypes.data, buf.size, ctypes.byref(n)))
+    else:
+        ctx.check(dll.nlx_fri_prove_hasher(ctx.handle, hs, len(oracles), nn, ptr(z), ptr(o0), ptr(o1) if o1.size else None,
+                                           ctypes.byref(params), hid, ctypes.byref(challenger.s), buf.ctypes.data, buf.size,
+                                           ctypes.byref(n)))
     return buf[:n.value].tobytes()
 
 
