@@ -229,8 +229,22 @@ typedef struct {
      * t_out receives ALL 4 n of them (4 n x 4 words) and *high_chunk_is_zero tells whether coefficients 3 n + 6 .. 4 n - 1 vanish;
      * gnark's h1, h2, h3 are t[0 : n + 2], t[n + 2 : 2 n + 4], t[2 n + 4 : 3 n + 6].  log_n >= 3.  NULL / flag clear: as before. */
     const uint64_t *blinding;
+    /* Bsb22 commitments (flags |= NLX_BN254_PLONK_COMMIT; gnark: api.Commit, the selectors Qcp and the polynomials PI2 of its
+     * proving key and proof).  The gate identity gains sum_j qcp[j] pi2[j], j < n_commit: qcp[j] is 1 on the rows whose L wire
+     * commitment j covers and 0 elsewhere; pi2[j] holds those L values, two blinding values on rows where qcp[j] is 0, and 0
+     * elsewhere.  qcp and pi2 are HOST arrays of n_commit pointers, each to n x 4 words on H (host or device) like the other
+     * polynomials; pi2 is not blinded by (X^n - 1) multiples.  The degree bound and t_out are as without commitments, and
+     * *high_chunk_is_zero also turns 0 when a pi2 does not close its rows.  May be combined with NLX_BN254_PLONK_BLINDED.
+     * These three fields are read ONLY when the flag is set: a caller compiled against the struct that ended at `blinding`
+     * keeps working.  With the flag set: n_commit outside 1 .. NLX_BN254_PLONK_MAX_COMMIT -> NLX_E_RANGE; a NULL array or a
+     * NULL entry -> NLX_E_INVAL. */
+    uint32_t n_commit;
+    const uint64_t *const *qcp;
+    const uint64_t *const *pi2;
 } nlx_bn254_plonk_quotient_args;
 #define NLX_BN254_PLONK_BLINDED 0x100u
+#define NLX_BN254_PLONK_COMMIT 0x200u
+#define NLX_BN254_PLONK_MAX_COMMIT 4u
 int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_args* args, uint64_t* t_out, int32_t* high_chunk_is_zero);
 /* The permutation's grand product (gnark computeZ / the paper's round 2): z(w^0) = 1,
  * z(w^(i+1)) = z(w^i) prod_j (w_j(i) + beta id_j(i) + gamma) / (w_j(i) + beta s_j(i) + gamma), id = (w^i, k1 w^i, k2 w^i).

@@ -285,19 +285,21 @@ def bn254_msm_g1(ctx, points, scalars, montgomery=False):
 class _PlonkQuotientArgs(ctypes.Structure):
     """nlx_bn254_plonk_quotient_args (include/nlx.h)"""
     _fields_ = [("log_n", ctypes.c_uint32), ("flags", ctypes.c_uint32)] + [(k, ctypes.c_void_p) for k in (
-        "ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3", "l", "r", "o", "z", "pi", "coset_shift", "k1", "k2", "alpha", "beta", "gamma", "blinding")]
+        "ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3", "l", "r", "o", "z", "pi", "coset_shift", "k1", "k2", "alpha", "beta", "gamma", "blinding")] + [
+        ("n_commit", ctypes.c_uint32), ("qcp", ctypes.POINTER(ctypes.c_void_p)), ("pi2", ctypes.POINTER(ctypes.c_void_p))]
 
 
 def _fr_words(x):
     return np.array([(int(x) >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(4)], dtype=np.uint64)
 
 
-def bn254_plonk_quotient(ctx, polys, coset_shift, k1, k2, alpha, beta, gamma, out=None, blinding=None):
+def bn254_plonk_quotient(ctx, polys, coset_shift, k1, k2, alpha, beta, gamma, out=None, blinding=None, qcp=None, pi2=None):
     """The PLONK prover's quotient chain over BN254's scalar field (nlx_bn254_plonk_quotient).  polys: dict with the values on
     H of ql qr qm qo qk s1 s2 s3 l r o z and optionally pi, each an (n, 4) uint64 array of fr.Element words (Montgomery) or a
     device tensor of that shape; the six scalars: integers in Montgomery form.  Returns (t, ok): t = (3, n, 4) uint64, the
     chunks t_lo, t_mid, t_hi (or `out`, a device tensor of that shape, filled in place); ok = the fourth chunk vanished (the witness
-    satisfies the circuit)."""
+    satisfies the circuit).  qcp, pi2: lists of 1 .. 4 polynomials each, of the same kind as the others (the Bsb22 commitments'
+    selectors and committed polynomials, NLX_BN254_PLONK_COMMIT): the gate gains sum_j qcp[j] pi2[j]."""
     names = ("ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3", "l", "r", "o", "z")
     keep, args = [], _PlonkQuotientArgs()
     n = None
@@ -330,6 +332,30 @@ def bn254_plonk_quotient(ctx, polys, coset_shift, k1, k2, alpha, beta, gamma, ou
         keep.append(bw)
         args.blinding = bw.ctypes.data
         args.flags = 1 | 0x100
+    if qcp is not None or pi2 is not None:
+        if qcp is None or pi2 is None or len(qcp) != len(pi2):
+            raise ValueError("qcp and pi2 go together: one polynomial each per commitment")
+        arrays = []
+        for name, group in (("qcp", qcp), ("pi2", pi2)):
+            ptrs = []
+            for v in group:
+                if v is None:             # handed on as NULL: the library refuses it
+                    ptrs.append(None)
+                    continue
+                if hasattr(v, "data_ptr"):
+                    shape, ptr = tuple(v.shape), v.data_ptr()
+                else:
+                    v = np.ascontiguousarray(v, dtype=np.uint64)
+                    shape, ptr = v.shape, v.ctypes.data
+                if shape != (n, 4):
+                    raise ValueError("%s: expected shape (n, 4)" % name)
+                keep.append(v)
+                ptrs.append(ptr)
+            arrays.append((ctypes.c_void_p * max(1, len(ptrs)))(*ptrs))
+        keep.append(arrays)
+        args.n_commit = len(qcp)      # the library refuses a count outside 1 .. 4
+        args.qcp, args.pi2 = arrays
+        args.flags |= 0x200
     for k, x in (("coset_shift", coset_shift), ("k1", k1), ("k2", k2), ("alpha", alpha), ("beta", beta), ("gamma", gamma)):
         w = _fr_words(x)
         keep.append(w)

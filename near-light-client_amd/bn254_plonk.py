@@ -63,8 +63,14 @@ class ProvingKey:
 
     NAMES = ("ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3")
 
-    def __init__(self, ctx, values, srs, k1, k2, device="cuda:0"):
-        """values: dict name -> n integers (canonical, values on H); srs: (>= n, 8) G1Affine words (array or device tensor)"""
+    def __init__(self, ctx, values, srs, k1, k2, device="cuda:0", commitments=()):
+        """values: dict name -> n integers (canonical, values on H); srs: (>= n, 8) G1Affine words (array or device tensor).
+        commitments: one dict per Bsb22 commitment, in commitment order - "committed": the rows whose L wire it covers, "row":
+        its commitment row i_j, "last_row": the key-wide second blinding row (gnark: the last constraint) - with the selector
+        of commitment j as values["qcp<j>"] (1 on the committed rows, 0 elsewhere).  The selectors are kept like the other fixed
+        polynomials: qcp_values, qcp_coeffs (k, n, 4) and qcp_commitments.  Two names that must not be confused: the
+        parameter `commitments` describes the circuit's Bsb22 commitments and is kept as self.bsb22; the attribute
+        self.commitments is, as before, the dict of the fixed polynomials' KZG commitments by name."""
         import torch
         self.ctx, self.device = ctx, device
         self.n = len(values["ql"])
@@ -75,6 +81,24 @@ class ProvingKey:
         self.values = torch.from_numpy(packed.view(np.int64)).to(device)                      # (8, n, 4)
         self.coeffs = B.bn254_ntt(ctx, self.values.clone(), inverse=True, montgomery=True)     # in place on the clone
         self.commitments = {k: B.bn254_msm_g1(ctx, self.srs[:self.n], self.coeffs[i], montgomery=True) for i, k in enumerate(self.NAMES)}
+        self.bsb22 = [{"committed": sorted(int(i) for i in c["committed"]), "row": int(c["row"]), "last_row": int(c["last_row"])} for c in commitments]
+        self.qcp_values = self.qcp_coeffs = None
+        self.qcp_commitments = []
+        if self.bsb22:
+            if len(self.bsb22) > 4:
+                raise ValueError("at most four Bsb22 commitments")
+            qcp = []
+            for j, c in enumerate(self.bsb22):
+                q = [int(x) % R for x in values["qcp%d" % j]]
+                qcp.append(q)
+                if c["last_row"] != self.bsb22[0]["last_row"] or not all(0 <= i < self.n for i in c["committed"] + [c["row"], c["last_row"]]):
+                    raise ValueError("commitment %d: rows outside H, or a last_row that differs from the key's" % j)
+                if len(q) != self.n or [i for i in range(self.n) if q[i]] != c["committed"] or any(q[i] != 1 for i in c["committed"]):
+                    raise ValueError("qcp%d is not 1 on the committed rows and 0 elsewhere" % j)
+            packed = B.bn254_pack([[_to_mont(x) for x in q] for q in qcp])
+            self.qcp_values = torch.from_numpy(packed.view(np.int64)).to(device)              # (k, n, 4)
+            self.qcp_coeffs = B.bn254_ntt(ctx, self.qcp_values.clone(), inverse=True, montgomery=True)
+            self.qcp_commitments = [B.bn254_msm_g1(ctx, self.srs[:self.n], self.qcp_coeffs[j], montgomery=True) for j in range(len(self.bsb22))]
 
     def value(self, name):
         return self.values[self.NAMES.index(name)]
@@ -204,7 +228,9 @@ def groth16_quotient(ctx, a, b, c, coset_shift=5):
 # ---- the proof in gnark's shape: its fiat-shamir, its blinding, its batched opening, its bytes (round 4) ----------------------
 # The host-side mirror of gnark backend/plonk/bn254 Prove (Go, not in /root/reference; succinct.json:7-8 names the entry point
 # that runs it), restated from its published structure [U: from memory, no gnark-produced vector exists here]; every heavy
-# step is one library call on device-resident polynomials.  oracle/bn254_py.py gnark_plonk_prove_model restates the same
+# step is one library call on device-resident polynomials.  Bsb22 commitments (api.Commit: what the wrapper circuit's range
+# checks go through) are part of it: tools/gnark_bsb22_model.py states their rules one by one and is the model for keys that
+# have them (tests/test_gpu_bn254_bsb22.py).  oracle/bn254_py.py gnark_plonk_prove_model restates the same
 # protocol on big integers (tests only); tests/test_gpu_bn254_plonk.py compares the BYTES and runs the model's verifier.
 Q = B.BN254_Q
 
@@ -269,10 +295,30 @@ def _blinded(torch, coeffs, n, b):
     return out
 
 
-def prove_gnark(pk, l, r, o, public_inputs=(), blinding=None):
+BSB22_DST = b"BSB22-Plonk"
+
+
+def hash_to_field(msg, dst=BSB22_DST):
+    """gnark-crypto fr.Hash(msg, dst, 1)[0]: RFC 9380 expand_message_xmd over SHA-256 to 48 bytes, read big-endian, mod r.  How
+    a Bsb22 commitment comes back into the circuit: c_j = hash_to_field([PI2_j].Marshal())."""
+    dst_prime = bytes(dst) + bytes([len(dst)])
+    b0 = hashlib.sha256(bytes(64) + bytes(msg) + (48).to_bytes(2, "big") + b"\x00" + dst_prime).digest()
+    b1 = hashlib.sha256(b0 + b"\x01" + dst_prime).digest()
+    b2 = hashlib.sha256(bytes(x ^ y for x, y in zip(b0, b1)) + b"\x02" + dst_prime).digest()
+    return int.from_bytes((b1 + b2)[:48], "big") % R
+
+
+def prove_gnark(pk, l=None, r=None, o=None, public_inputs=(), blinding=None, commit_blinding=None, witness=None):
     """l, r, o: the wire values on H (n canonical integers each).  public_inputs: the values of the public-input polynomial on
     the first points of H (the circuit's qk leaves them out, as gnark's does).  blinding: nine scalars (l 2, r 2, o 2, z 3) -
     random when None; a test passes them to compare bytes with the model.  The SRS must hold n + 3 points.
+    A key with k Bsb22 commitments (ProvingKey(commitments=...)): commitment j's polynomial pi2_j takes the L values on its
+    committed rows and two blinding scalars (commit_blinding[2 j] on its commitment row, then commit_blinding[2 j + 1] on
+    last_row; 2 k scalars, random when None), [PI2_j] is its KZG commitment and c_j = hash_to_field([PI2_j].Marshal()) is the
+    value the circuit expects on the L wire of the commitment row.  Committed values may depend on earlier c_j: pass
+    witness = a callable that receives [c_0 .. c_{j-1}] and returns (l, r, o) - it is called once per commitment and once
+    with all k values for the final wires - or pass full l, r, o when every c_j is known already.  ValueError if in the end
+    l[i_j] != c_j or a committed value differs from what was committed.
     Returns the proof's bytes (gnark Proof.WriteTo layout)."""
     import secrets
     import torch
@@ -280,16 +326,48 @@ def prove_gnark(pk, l, r, o, public_inputs=(), blinding=None):
     w, u, dev = root_of_unity(log_n), pk.k1, pk.device
     if pk.srs.shape[0] < n + 3:
         raise ValueError("the SRS must hold n + 3 points (blinded polynomials have up to n + 3 coefficients)")
+    if (witness is None) == (l is None) or (witness is None and (r is None or o is None)):
+        raise ValueError("pass the wires l, r, o or a callable witness(cs) -> (l, r, o)")
     b = [secrets.randbelow(R) for _ in range(9)] if blinding is None else [int(x) % R for x in blinding]
     commit = lambda c: B.bn254_msm_g1(ctx, pk.srs[:c.shape[0]], c.contiguous(), montgomery=True)
     at = lambda c, point: _from_words_mont(B.bn254_kzg_open(ctx, c.contiguous(), _to_mont(point), want_quotient=False)[0])
+    to_dev = lambda cols: torch.from_numpy(B.bn254_pack([[_to_mont(x) for x in col] for col in cols]).view(np.int64)).to(dev)
+    # round 0: the Bsb22 commitments, in order; the witness is completed between them
+    k = len(pk.bsb22)
+    cb = [secrets.randbelow(R) for _ in range(2 * k)] if commit_blinding is None else [int(x) % R for x in commit_blinding]
+    if len(cb) != 2 * k:
+        raise ValueError("two blinding scalars per Bsb22 commitment")
+    cs, committed, pi2_values, pi2_coeffs, pi2c = [], [], [], [], []
+    for j, info in enumerate(pk.bsb22):
+        lj = l if witness is None else witness(list(cs))[0]
+        committed.append([int(lj[i]) % R for i in info["committed"]])
+        # pi2_j on H: the committed L values, a blinding scalar on the commitment row, THEN one on last_row (the second
+        # assignment stands if the two coincide), zero elsewhere - only these entries cross to the device
+        entries = dict(zip(info["committed"], committed[j]))
+        entries[info["row"]] = cb[2 * j]
+        entries[info["last_row"]] = cb[2 * j + 1]
+        v = torch.zeros((1, n, 4), dtype=torch.int64, device=dev)
+        v[0, torch.tensor(list(entries), dtype=torch.int64, device=dev)] = to_dev([list(entries.values())])[0]
+        pi2_values.append(v)
+        pi2_coeffs.append(B.bn254_ntt(ctx, v.clone(), inverse=True, montgomery=True)[0])
+        pi2c.append(commit(pi2_coeffs[j]))
+        cs.append(hash_to_field(g1_marshal(pi2c[j])))
+    if witness is not None:
+        l, r, o = witness(list(cs))
+    for j, info in enumerate(pk.bsb22):
+        if int(l[info["row"]]) % R != cs[j]:
+            raise ValueError("Bsb22 commitment %d: the L wire of its commitment row is not the hash of the commitment" % j)
+        if [int(l[i]) % R for i in info["committed"]] != committed[j]:
+            raise ValueError("Bsb22 commitment %d: a committed value was changed after the commitment" % j)
     fs = FiatShamir("gamma", "beta", "alpha", "zeta")
-    for k in ("s1", "s2", "s3", "ql", "qr", "qm", "qo", "qk"):
-        fs.bind("gamma", g1_marshal(pk.commitments[k]))
+    for name in ("s1", "s2", "s3", "ql", "qr", "qm", "qo", "qk"):
+        fs.bind("gamma", g1_marshal(pk.commitments[name]))
+    for c in pk.qcp_commitments:
+        fs.bind("gamma", g1_marshal(c))
     for x in public_inputs:
         fs.bind("gamma", fr_bytes(x))
     # round 1: blinded wires
-    wires = torch.from_numpy(B.bn254_pack([[_to_mont(x) for x in col] for col in (l, r, o)]).view(np.int64)).to(dev)   # (3, n, 4)
+    wires = to_dev((l, r, o))   # (3, n, 4)
     wire_coeffs = B.bn254_ntt(ctx, wires.clone(), inverse=True, montgomery=True)
     bl = [_blinded(torch, wire_coeffs[i], n, b[2 * i:2 * i + 2]) for i in range(3)]
     lro = [commit(c) for c in bl]
@@ -303,18 +381,23 @@ def prove_gnark(pk, l, r, o, public_inputs=(), blinding=None):
         raise ValueError("the wires do not respect the circuit's copy constraints (the grand product does not close)")
     blz = _blinded(torch, B.bn254_ntt(ctx, z.clone().reshape(1, n, 4), inverse=True, montgomery=True)[0], n, b[6:9])
     zc = commit(blz)
+    for c in pi2c:
+        fs.bind("alpha", g1_marshal(c))
     fs.bind("alpha", g1_marshal(zc))
     alpha = fs.challenge("alpha")
     # round 3: the quotient of the BLINDED polynomials (nlx_bn254_plonk_quotient patches the coefficients it derives from the
     # values on H), all 4 n coefficients, cut into h1 h2 h3 of n + 2
-    polys = {k: pk.value(k) for k in pk.NAMES}
+    polys = {name: pk.value(name) for name in pk.NAMES}
     polys.update(l=wires[0], r=wires[1], o=wires[2], z=z)
-    if len(public_inputs):
+    if len(public_inputs) or k:
         pi = [int(x) % R for x in public_inputs] + [0] * (n - len(public_inputs))
-        polys["pi"] = torch.from_numpy(B.bn254_pack([[_to_mont(x) for x in pi]])[0].view(np.int64)).to(dev)
+        for j, info in enumerate(pk.bsb22):
+            pi[info["row"]] = cs[j]           # PI(w^i_j) = c_j: the commitment row reads - l + c_j = 0
+        polys["pi"] = to_dev([pi])[0]
     h4 = torch.empty((4 * n, 4), dtype=torch.int64, device=dev)
     _, ok = B.bn254_plonk_quotient(ctx, polys, *[_to_mont(x) for x in (u, pk.k1, pk.k2, alpha, beta, gamma)], out=h4,
-                                   blinding=[_to_mont(x) for x in b])
+                                   blinding=[_to_mont(x) for x in b],
+                                   qcp=[pk.qcp_values[j] for j in range(k)] if k else None, pi2=[v[0] for v in pi2_values] if k else None)
     if not ok:
         raise ValueError("the witness does not satisfy the circuit (the quotient has more than 3 n + 6 coefficients)")
     hs = [h4[0:n + 2], h4[n + 2:2 * n + 4], h4[2 * n + 4:3 * n + 6]]
@@ -341,14 +424,16 @@ def prove_gnark(pk, l, r, o, public_inputs=(), blinding=None):
         out[:c.shape[0]] = c
         return out
     lin = torch.empty((m, 4), dtype=torch.int64, device=dev)
-    lincomb(ctx, [padded(pk.coeff(k)) for k in ("qm", "ql", "qr", "qo", "qk")] + [blz, padded(pk.coeff("s3"))],
-            [lz * rz % R, lz, rz, oz, 1, (alpha * a_ + alpha * alpha % R * l1) % R, (-alpha * b_ % R * beta % R * zw) % R], lin)
+    qcpz = [at(pk.qcp_coeffs[j], zeta) for j in range(k)]
+    lincomb(ctx, [padded(pk.coeff(name)) for name in ("qm", "ql", "qr", "qo", "qk")] + [blz, padded(pk.coeff("s3"))] + [padded(pi2_coeffs[j]) for j in range(k)],
+            [lz * rz % R, lz, rz, oz, 1, (alpha * a_ + alpha * alpha % R * l1) % R, (-alpha * b_ % R * beta % R * zw) % R] + qcpz, lin)
     zn2 = pow(zeta, n + 2, R)
     folded_h = torch.empty((n + 2, 4), dtype=torch.int64, device=dev)
     lincomb(ctx, [c.contiguous() for c in hs], [1, zn2, zn2 * zn2 % R], folded_h)
     batch = [padded(folded_h), lin, padded(bl[0]), padded(bl[1]), padded(bl[2]), padded(pk.coeff("s1")), padded(pk.coeff("s2"))]
-    digests = [commit(folded_h), commit(lin)] + lro + [pk.commitments["s1"], pk.commitments["s2"]]
-    claimed = [at(batch[0], zeta), at(lin, zeta), lz, rz, oz, s1z, s2z]
+    batch += [padded(pk.qcp_coeffs[j]) for j in range(k)]
+    digests = [commit(folded_h), commit(lin)] + lro + [pk.commitments["s1"], pk.commitments["s2"]] + pk.qcp_commitments
+    claimed = [at(batch[0], zeta), at(lin, zeta), lz, rz, oz, s1z, s2z] + qcpz
     fg = FiatShamir("gamma")
     fg.bind("gamma", fr_bytes(zeta))
     for d in digests:
@@ -357,9 +442,9 @@ def prove_gnark(pk, l, r, o, public_inputs=(), blinding=None):
         fg.bind("gamma", fr_bytes(v))
     gp = fg.challenge("gamma")
     folded = torch.empty((m, 4), dtype=torch.int64, device=dev)
-    lincomb(ctx, batch, [pow(gp, i, R) for i in range(7)], folded)
+    lincomb(ctx, batch, [pow(gp, i, R) for i in range(len(batch))], folded)
     bh = B.bn254_kzg_open(ctx, folded, _to_mont(zeta), srs=pk.srs, want_quotient=False)[2]
     out = b"".join(g1_compress(c) for c in lro) + g1_compress(zc) + b"".join(g1_compress(c) for c in hc)
-    out += (0).to_bytes(4, "big")                                    # Bsb22Commitments: none
-    out += g1_compress(bh) + (7).to_bytes(4, "big") + b"".join(fr_bytes(v) for v in claimed)
+    out += k.to_bytes(4, "big") + b"".join(g1_compress(c) for c in pi2c)      # Bsb22Commitments
+    out += g1_compress(bh) + len(claimed).to_bytes(4, "big") + b"".join(fr_bytes(v) for v in claimed)
     return out + g1_compress(zshift) + fr_bytes(zw)

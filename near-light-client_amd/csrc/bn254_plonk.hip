@@ -16,6 +16,9 @@
 //      the circuit - reported, not assumed)
 //   5. KZG: commitments are nlx_bn254_msm_g1 over the SRS; an opening at zeta is the evaluation, the synthetic division
 //      (p(X) - p(zeta)) / (X - zeta) and one more MSM.
+// gnark's additions to that chain are opt-in flags of nlx_bn254_plonk_quotient: NLX_BN254_PLONK_BLINDED (l r o z blinded by
+// multiples of X^n - 1) and NLX_BN254_PLONK_COMMIT (Bsb22 commitments: the gate also carries sum_j qcp_j pi2_j, the 2 k extra
+// polynomials taking steps 1 and 2 like the thirteen).
 //
 // Arithmetic: bn254_f29.hpp's nine 29-bit limbs (the NTT's and the MSM's element), every sum / difference tightened.  Elements
 // rest in memory as gnark-crypto's fr.Element (Montgomery, R = 2^256: "D-form", x 2^256); the kernels' products divide by
@@ -111,12 +114,14 @@ struct Consts {
     Fe zh_inv[4];    // 1 / (x^n - 1) on the coset: x^n = shift^n i^(k mod 4)
 };
 struct QuotientParams {
-    const uint64_t* ev;   // [13 or 14][4n] evaluations on the coset, natural order: ql qr qm qo qk s1 s2 s3 l r o z (pi)
+    const uint64_t* ev;   // [12 + has_pi + 2 n_commit][4n] evaluations on the coset, natural order: ql qr qm qo qk s1 s2 s3 l r o z
+                          // (pi) (qcp_0 .. pi2_0 ..)
     const uint64_t* x;    // [4n] the points, I-form
     const uint64_t* linv; // [4n] 1 / (n (x - 1)), I-form
     const Consts* k;
     uint64_t* t;          // [4n]
     uint32_t log_n, has_pi;
+    uint32_t n_commit;    // Bsb22 commitments (NLX_BN254_PLONK_COMMIT): read by k_plonk_quotient<true> only
 };
 
 // bad: set to 1 when Z_H vanishes on the coset (the shift lies in the size-4n subgroup): inv_i(0) = 0 would otherwise give a
@@ -193,6 +198,9 @@ __global__ void k_plonk_blind(uint64_t* __restrict__ ev, const uint64_t* __restr
     st(col, pos, add_side ? add(cur, bj) : sub(cur, bj));
 }
 
+// COMMIT: the gate also carries sum_j qcp_j pi2_j (gnark's Bsb22 commitments).  A template, so that the instantiation without
+// commitments stays the kernel it was; with them the trip count comes from the params (wave-uniform, no per-lane branching).
+template <bool COMMIT>
 __global__ __launch_bounds__(256) void k_plonk_quotient(QuotientParams p) {
     const size_t N4 = (size_t)4 << p.log_n;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -207,6 +215,11 @@ __global__ __launch_bounds__(256) void k_plonk_quotient(QuotientParams p) {
     gate = add(gate, mul_dd(E(3, i), o));
     gate = add(gate, E(4, i));
     if (p.has_pi) gate = add(gate, E(12, i));
+    if constexpr (COMMIT) {
+        const int base = 12 + (int)p.has_pi, nc = (int)p.n_commit;
+#pragma unroll 1
+        for (int j = 0; j < nc; j++) gate = add(gate, mul_dd(E(base + j, i), E(base + nc + j, i)));
+    }
     // permutation: the identity side on x, k1 x, k2 x and the sigma side on s1, s2, s3; z at the next point of the size-n
     // subgroup = four positions further on the size-4n coset
     const Fe x = ld(p.x, i), g = k.gamma_d;
@@ -602,13 +615,21 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
     for (int i = 0; i < 12; i++)
         if (!polys[i]) return ctx->fail(NLX_E_INVAL, "NULL polynomial");
     if (a->log_n < 2 || a->log_n > 26) return ctx->fail(NLX_E_RANGE, "log_n must be in [2, 26] (the coset has four times the points)");
-    const bool blinded = (a->flags & NLX_BN254_PLONK_BLINDED) != 0;
-    if ((a->flags & ~NLX_BN254_PLONK_BLINDED) != NLX_BN254_MONTGOMERY) return ctx->fail(NLX_E_UNSUPPORTED, "elements must be fr.Element words (flags = NLX_BN254_MONTGOMERY)");
+    const bool blinded = (a->flags & NLX_BN254_PLONK_BLINDED) != 0, commit = (a->flags & NLX_BN254_PLONK_COMMIT) != 0;
+    if ((a->flags & ~(NLX_BN254_PLONK_BLINDED | NLX_BN254_PLONK_COMMIT)) != NLX_BN254_MONTGOMERY) return ctx->fail(NLX_E_UNSUPPORTED, "elements must be fr.Element words (flags = NLX_BN254_MONTGOMERY)");
     if (blinded) {
         if (!a->blinding || is_device_ptr(a->blinding)) return ctx->fail(NLX_E_INVAL, "the blinding scalars are host values (nine elements of four words)");
         if (a->log_n < 3) return ctx->fail(NLX_E_RANGE, "a blinded quotient needs log_n >= 3 (3 n + 6 coefficients on 4 n points)");
         for (int i = 0; i < 9; i++)
             if (!fr_words_below_r(a->blinding + 4 * i)) return ctx->fail(NLX_E_RANGE, "a blinding scalar is not below r");
+    }
+    // n_commit, qcp, pi2 lie behind the struct a caller of the earlier ABI allocated: read only under the flag
+    const uint32_t K = commit ? a->n_commit : 0;
+    if (commit) {
+        if (K < 1 || K > NLX_BN254_PLONK_MAX_COMMIT) return ctx->fail(NLX_E_RANGE, "n_commit must be in [1, 4]");
+        if (!a->qcp || !a->pi2 || is_device_ptr(a->qcp) || is_device_ptr(a->pi2)) return ctx->fail(NLX_E_INVAL, "qcp and pi2 are host arrays of n_commit pointers");
+        for (uint32_t j = 0; j < K; j++)
+            if (!a->qcp[j] || !a->pi2[j]) return ctx->fail(NLX_E_INVAL, "NULL polynomial (qcp / pi2)");
     }
     {
         const uint64_t* sc[6] = {a->coset_shift, a->k1, a->k2, a->alpha, a->beta, a->gamma};
@@ -619,7 +640,7 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
     }
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    const uint32_t log_n = a->log_n, P = a->pi ? 13 : 12;
+    const uint32_t log_n = a->log_n, P0 = a->pi ? 13 : 12, P = P0 + 2 * K;   // in ev after (pi): qcp_0 .. pi2_0 ..
     const size_t n = (size_t)1 << log_n, N4 = 4 * n;
     std::vector<void*> tmp;
     auto dalloc = [&](size_t bytes) -> uint64_t* {
@@ -654,8 +675,9 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
         if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
     }
     for (uint32_t i = 0; i < P; i++) {
-        hipError_t e = hipMemcpyAsync(d_in + (size_t)i * n * 4, polys[i], n * 32,
-                                      is_device_ptr(polys[i]) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
+        const uint64_t* src = i < P0 ? polys[i] : i < P0 + K ? a->qcp[i - P0] : a->pi2[i - P0 - K];
+        hipError_t e = hipMemcpyAsync(d_in + (size_t)i * n * 4, src, n * 32,
+                                      is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
     }
     hipLaunchKernelGGL(bnp::k_plonk_consts, dim3(1), dim3(1), 0, st, d_k, log_n, d_small, d_flag + 1);
@@ -674,9 +696,10 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
     rc = nlx_bn254_ntt_batch_coset(ctx, d_ev, P, log_n + 2, 0, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_IN, a->coset_shift);
     if (rc) return done(rc);
     // 3. the quotient's values on the coset
-    bnp::QuotientParams qp{d_ev, d_x, d_linv, d_k, d_t, log_n, a->pi ? 1u : 0u};
+    bnp::QuotientParams qp{d_ev, d_x, d_linv, d_k, d_t, log_n, a->pi ? 1u : 0u, K};
     ctx->begin_kernel("plonk_quotient", 32.0 * N4 * (P + 4));
-    hipLaunchKernelGGL(bnp::k_plonk_quotient, dim3((unsigned)((N4 + 255) / 256)), dim3(256), 0, st, qp);
+    if (commit) hipLaunchKernelGGL(bnp::k_plonk_quotient<true>, dim3((unsigned)((N4 + 255) / 256)), dim3(256), 0, st, qp);
+    else hipLaunchKernelGGL(bnp::k_plonk_quotient<false>, dim3((unsigned)((N4 + 255) / 256)), dim3(256), 0, st, qp);
     ctx->end_kernel();
     // 4. back to coefficients
     rc = nlx_bn254_ntt_batch_coset(ctx, d_t, 1, log_n + 2, 1, NLX_BN254_MONTGOMERY, a->coset_shift);
