@@ -273,6 +273,70 @@ int32_t nlx_bn254_groth16_quotient(nlx_ctx* ctx, uint32_t log_n, const uint64_t*
 int32_t nlx_bn254_kzg_open(nlx_ctx* ctx, const uint64_t* coeffs, uint64_t m, const uint64_t zeta[4], const uint64_t* srs,
                            uint64_t y_out[4], uint64_t* quotient_out, uint64_t proof_out[8]);
 
+/* ---- f.4, the Groth16 half: whole proofs from a proving key resident in HBM (gnark backend/groth16/bn254 ProvingKey and Prove;
+ * Go, not in the reference: the layout and the rules are recalled from gnark v0.9, parity with gnark-produced bytes unpinned -
+ * DESIGN.md section 19).  The descriptor carries gnark's ProvingKey as it lies in memory; every pointer may be host or device.
+ *   g1_a / g1_b / g2_b  G1.A, G1.B, G2.B: the queries FILTERED of their points at infinity (G1Affine: 8 words, G2Affine: 16 words,
+ *                       Montgomery) with their counts; infinity_a / infinity_b: InfinityA / InfinityB, one byte per wire (Go's
+ *                       []bool), non-zero = that wire's point was filtered out.  G2.B is filtered by InfinityB.
+ *   g1_k                G1.K, one point per private wire (n_wires - n_public of them)
+ *   g1_z                G1.Z, 2^log_n - 1 points
+ *   g1_alpha, g1_beta, g1_delta, g2_beta, g2_delta   the five single points
+ *   log_n               the domain's size; n_constraints <= 2^log_n; n_public counts the constant wire (wire 0, value 1);
+ *                       wire order: ONE, public, secret, internal
+ *   the R1CS (optional; all of it or none): three CSR matrices of n_constraints rows - x_row_ptr: n_constraints + 1 offsets,
+ *                       x_wire / x_coeff_id: one wire id and one index into `coeffs` per term - and the coefficient table
+ *                       (n_coeffs x 4 words, fr.Element Montgomery).  Without it nlx_bn254_r1cs_eval and a prove call that
+ *                       does not bring a, b, c return NLX_E_INVAL.
+ *   n_commitments       Bsb22 / Pedersen commitments (Proof.Commitments, CommitmentPok): must be 0, else NLX_E_UNSUPPORTED.
+ * Creation uploads once, converts every query to the bucket kernels' form once (the three wire queries and G1.K expanded to the
+ * wires' index space, the point at infinity at masked and public positions, so that one set of sorted digits serves all four),
+ * and classifies the R1CS: coefficients equal to 1 or -1 are marked (added or subtracted, no product), rows of more than 64
+ * terms go to a wave-per-row list.  NLX_E_RANGE: flags other than NLX_BN254_MONTGOMERY, log_n outside 1 .. 26, n_constraints >
+ * 2^log_n, a mask whose count of clear entries disagrees with its query's count, counts of G1.K / G1.Z / G2.B that disagree
+ * with the sizes, a wire id >= n_wires, a coefficient id outside the table, row pointers that decrease.  The key belongs to
+ * its context and must be destroyed before it. */
+typedef struct nlx_bn254_groth16_key nlx_bn254_groth16_key;
+typedef struct {
+    uint32_t log_n;
+    uint32_t flags;                     /* NLX_BN254_MONTGOMERY */
+    uint64_t n_wires, n_public, n_constraints;
+    const uint64_t* g1_a; uint64_t n_g1_a;
+    const uint64_t* g1_b; uint64_t n_g1_b;
+    const uint64_t* g2_b; uint64_t n_g2_b;
+    const uint64_t* g1_k; uint64_t n_g1_k;
+    const uint64_t* g1_z; uint64_t n_g1_z;
+    const uint8_t *infinity_a, *infinity_b;
+    const uint64_t *g1_alpha, *g1_beta, *g1_delta, *g2_beta, *g2_delta;
+    const uint64_t *a_row_ptr, *b_row_ptr, *c_row_ptr;
+    const uint32_t *a_wire, *b_wire, *c_wire;
+    const uint32_t *a_coeff_id, *b_coeff_id, *c_coeff_id;
+    const uint64_t* coeffs; uint64_t n_coeffs;
+    uint32_t n_commitments;
+} nlx_bn254_groth16_key_desc;
+int32_t nlx_bn254_groth16_key_create(nlx_ctx* ctx, const nlx_bn254_groth16_key_desc* desc, nlx_bn254_groth16_key** out);
+void nlx_bn254_groth16_key_destroy(nlx_bn254_groth16_key* key);
+/* out[0] = bytes the key keeps resident in HBM, out[1] = R1CS rows run one per lane, out[2] = rows run one per wave, out[3] =
+ * terms of the three matrices, out[4] = terms whose coefficient is 1 or -1, out[5] = the row-length threshold; the rest 0. */
+#define NLX_BN254_GROTH16_KEY_INFO_WORDS 8
+int32_t nlx_bn254_groth16_key_info(const nlx_bn254_groth16_key* key, uint64_t out[NLX_BN254_GROTH16_KEY_INFO_WORDS]);
+/* a = A w, b = B w, c = C w: three sparse matrix-vector products over Fr.  witness: n_wires x 4 words (Montgomery), host or
+ * device; a_out, b_out, c_out: 2^log_n x 4 words each, host or device, rows past n_constraints zero.  Kernel-timing name
+ * "bn254_r1cs_eval", units terms. */
+int32_t nlx_bn254_r1cs_eval(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, const uint64_t* witness, uint64_t* a_out, uint64_t* b_out,
+                            uint64_t* c_out);
+/* One proof.  a, b, c: the solver's values of A w, B w, C w on H (2^log_n x 4 words, host or device; gnark: solution.A/B/C), or
+ * all three NULL: computed from the key's matrices.  r, s: the blinding scalars, host, four Montgomery words each, below r.
+ * Before anything is committed: w[0] must be 1 and a_i b_i = c_i must hold on every row - otherwise NLX_E_INVAL (the message
+ * names the first failing row) and no output is written.  Then h = (a b - c) / Z_H on the device (coset shift 5, gnark's
+ * domain generator), the four MSMs over the wire vector on one digit decomposition and one set of sorted indices, G1.Z over h,
+ * and on the host Ar = sum w_i A_i + alpha + r delta, Bs = sum w_i B_i + beta + s delta (G2; Bs1 the same in G1),
+ * Krs = sum_private w_i K_i + sum_(i < n-1) h_i Z_i + s Ar + r Bs1 - r s delta.
+ * ar_out, krs_out: G1Affine words; bs_out: G2Affine words.  Kernel-timing name "bn254_groth16_msms". */
+int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, const uint64_t* witness, const uint64_t* a,
+                                const uint64_t* b, const uint64_t* c, const uint64_t r[4], const uint64_t s[4], uint64_t ar_out[8],
+                                uint64_t bs_out[16], uint64_t krs_out[8]);
+
 /* ---- a3: plonky2::fri::oracle::PolynomialBatch::{from_values, from_coeffs} ----
  * values / coeffs: n_cols x 2^log_n column-major, natural order.  The coset shift is the
  * field's multiplicative generator (plonky2 F::coset_shift()).  blinding / salting is not

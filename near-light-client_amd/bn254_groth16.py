@@ -1,0 +1,231 @@
+"""Row f.4, the Groth16 half: whole proofs over BN254 from a proving key resident in HBM - the host-side mirror of gnark's
+backend/groth16/bn254 `ProvingKey` and `Prove` (Go, not in the reference; layout and rules recalled from gnark v0.9, parity with
+gnark-produced bytes unpinned: DESIGN.md section 19).
+
+  ProvingKey(ctx, ...)   nlx_bn254_groth16_key_create: gnark's key as it lies in memory, uploaded and converted once
+  r1cs_eval(pk, w)       nlx_bn254_r1cs_eval: A w, B w, C w
+  prove(pk, w, r, s)     nlx_bn254_groth16_prove: the proof's three points (G1Affine / G2Affine / G1Affine words)
+  proof_bytes(...)       gnark's Proof.WriteTo without commitments, 164 bytes; g1_compress / g2_compress: gnark-crypto's Bytes()
+
+Every element is an fr.Element / fp.Element as it lies in memory (four little-endian words, Montgomery); arrays are numpy uint64
+or device tensors.  Parity: device bytes equal the big-integer model's (tools/groth16_model.py) and its trapdoor verifier accepts
+them (tests/test_gpu_bn254_groth16.py)."""
+import ctypes
+import secrets
+
+import numpy as np
+
+from . import batch as B
+from ._lib import dll, ptr
+
+R, Q = B.BN254_R, B.BN254_Q
+_MONT = (1 << 256) % R
+NLX_BN254_MONTGOMERY = 1
+KEY_INFO_WORDS = 8
+
+
+class _KeyDesc(ctypes.Structure):
+    """nlx_bn254_groth16_key_desc (include/nlx.h)"""
+    _fields_ = ([("log_n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_wires", ctypes.c_uint64), ("n_public", ctypes.c_uint64),
+                 ("n_constraints", ctypes.c_uint64)]
+                + [f for k in ("g1_a", "g1_b", "g2_b", "g1_k", "g1_z") for f in ((k, ctypes.c_void_p), ("n_" + k, ctypes.c_uint64))]
+                + [(k, ctypes.c_void_p) for k in ("infinity_a", "infinity_b", "g1_alpha", "g1_beta", "g1_delta", "g2_beta", "g2_delta",
+                                                  "a_row_ptr", "b_row_ptr", "c_row_ptr", "a_wire", "b_wire", "c_wire",
+                                                  "a_coeff_id", "b_coeff_id", "c_coeff_id", "coeffs")]
+                + [("n_coeffs", ctypes.c_uint64), ("n_commitments", ctypes.c_uint32)])
+
+
+def fr_words(x):
+    """an integer below r -> its fr.Element words (Montgomery)"""
+    m = int(x) % R * _MONT % R
+    return np.array([(m >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(4)], dtype=np.uint64)
+
+
+def fr_pack(values):
+    """integers below r -> (n, 4) uint64 fr.Element words (Montgomery)"""
+    out = np.zeros((len(values), 4), dtype=np.uint64)
+    for i, x in enumerate(values):
+        m = int(x) % R * _MONT % R
+        for w in range(4):
+            out[i, w] = (m >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
+    return out
+
+
+def fr_unpack(words):
+    """(n, 4) fr.Element words -> integers"""
+    minv = pow(_MONT, R - 2, R)
+    a = np.asarray(words, dtype=np.uint64).reshape(-1, 4)
+    return [sum(int(a[i, w]) << (64 * w) for w in range(4)) * minv % R for i in range(a.shape[0])]
+
+
+def _buf(a, dtype, width=None, size=None):
+    """(object kept alive, address, rows) of a numpy array or a contiguous device tensor.  width: the array is (rows, width);
+    width 0: one-dimensional; size: its total number of elements.  A wrong shape raises here: the library reads what the
+    descriptor's counts say and cannot see where the caller's buffer ends."""
+    if a is None:
+        return None, None, 0
+    if hasattr(a, "data_ptr"):
+        if not a.is_contiguous():
+            raise TypeError("expected a contiguous tensor")
+        if a.element_size() != np.dtype(dtype).itemsize or a.is_floating_point():
+            raise TypeError("expected %d-byte integer elements" % np.dtype(dtype).itemsize)
+        shape, count = tuple(a.shape), a.numel()
+    else:
+        a = np.ascontiguousarray(a, dtype=dtype)
+        shape, count = a.shape, a.size
+    if width == 0 and len(shape) != 1:
+        raise ValueError("expected a one-dimensional array, got shape %r" % (shape,))
+    if width and (len(shape) != 2 or shape[1] != width):
+        raise ValueError("expected shape (n, %d), got %r" % (width, shape))
+    if size is not None and count != size:
+        raise ValueError("expected %d elements, got %d" % (size, count))
+    return a, (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data), (shape[0] if shape else 0)
+
+
+class ProvingKey:
+    """nlx_bn254_groth16_key: gnark's groth16.ProvingKey resident on the device (owns the handle; close() or the context's
+    close() releases it).
+
+    g1_a, g1_b, g1_k, g1_z: (count, 8) G1Affine words; g2_b: (count, 16) G2Affine words - the queries filtered of their points at
+    infinity, as gnark keeps them; infinity_a, infinity_b: one byte (or bool) per wire, non-zero = filtered out; g1_alpha,
+    g1_beta, g1_delta (8 words), g2_beta, g2_delta (16 words).  r1cs (optional): {"A": (row_ptr, wire, coeff_id), "B": ...,
+    "C": ..., "coeffs": (n_coeffs, 4) fr.Element words} with row_ptr uint64, wire and coeff_id uint32.  Arrays are numpy or device
+    tensors.  n_commitments: gnark's Bsb22 / Pedersen commitments, unsupported (anything but 0 raises)."""
+
+    def __init__(self, ctx, log_n, n_wires, n_public, n_constraints, g1_a, g1_b, g2_b, g1_k, g1_z, infinity_a, infinity_b,
+                 g1_alpha, g1_beta, g1_delta, g2_beta, g2_delta, r1cs=None, n_commitments=0, flags=NLX_BN254_MONTGOMERY):
+        self.ctx, self.handle = ctx, None
+        self.log_n, self.n_wires, self.n_public, self.n_constraints = int(log_n), int(n_wires), int(n_public), int(n_constraints)
+        d = _KeyDesc()
+        d.log_n, d.flags, d.n_wires, d.n_public, d.n_constraints = self.log_n, int(flags), self.n_wires, self.n_public, self.n_constraints
+        d.n_commitments = int(n_commitments)
+        keep = []
+        for name, arr, width in (("g1_a", g1_a, 8), ("g1_b", g1_b, 8), ("g2_b", g2_b, 16), ("g1_k", g1_k, 8), ("g1_z", g1_z, 8)):
+            k, p, rows = _buf(arr, np.uint64, width)
+            keep.append(k)
+            setattr(d, name, p)
+            setattr(d, "n_" + name, rows)
+        for name, arr in (("infinity_a", infinity_a), ("infinity_b", infinity_b)):
+            k, p, _ = _buf(arr, np.uint8, 0, size=self.n_wires)
+            keep.append(k)
+            setattr(d, name, p)
+        for name, arr, count in (("g1_alpha", g1_alpha, 8), ("g1_beta", g1_beta, 8), ("g1_delta", g1_delta, 8), ("g2_beta", g2_beta, 16),
+                                 ("g2_delta", g2_delta, 16)):
+            k, p, _ = _buf(arr, np.uint64, size=count)
+            keep.append(k)
+            setattr(d, name, p)
+        if r1cs is not None:
+            for m in "ABC":
+                rows = {}
+                for field, arr, dt in zip(("row_ptr", "wire", "coeff_id"), r1cs[m], (np.uint64, np.uint32, np.uint32)):
+                    k, p, rows[field] = _buf(arr, dt, 0)
+                    keep.append(k)
+                    setattr(d, "%s_%s" % (m.lower(), field), p)
+                # the library finds the number of terms in row_ptr's last entry, which it validates against nothing but itself
+                if rows["row_ptr"] != self.n_constraints + 1 or rows["wire"] != rows["coeff_id"]:
+                    raise ValueError("matrix %s: row_ptr holds n_constraints + 1 offsets, wire and coeff_id one entry per term" % m)
+                last = int(r1cs[m][0][-1]) if rows["row_ptr"] else 0
+                if last > rows["wire"]:
+                    raise ValueError("matrix %s: row_ptr ends at %d, the matrix holds %d terms" % (m, last, rows["wire"]))
+            k, p, rows = _buf(r1cs["coeffs"], np.uint64, 4)
+            keep.append(k)
+            d.coeffs, d.n_coeffs = p, rows
+        h = ctypes.c_void_p()
+        ctx.check(dll.nlx_bn254_groth16_key_create(ctx.handle, ctypes.byref(d), ctypes.byref(h)))
+        self.handle = h
+        self.has_r1cs = r1cs is not None
+        ctx._adopt(self)
+
+    def info(self):
+        """what the key reports: resident bytes, and the SpMV's row split"""
+        out = np.zeros(KEY_INFO_WORDS, dtype=np.uint64)
+        self.ctx.check(dll.nlx_bn254_groth16_key_info(self.handle, out.ctypes.data))
+        names = ("resident_bytes", "lane_rows", "wave_rows", "terms", "unit_terms", "long_row_threshold")
+        return {k: int(out[i]) for i, k in enumerate(names)}
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            dll.nlx_bn254_groth16_key_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def r1cs_eval(pk, witness):
+    """A w, B w, C w.  witness: (n_wires, 4) fr.Element words, numpy or a device tensor; returns (3, 2^log_n, 4) of the same kind
+    (rows past n_constraints are zero)."""
+    n = 1 << pk.log_n
+    if hasattr(witness, "data_ptr"):
+        import torch
+        if tuple(witness.shape) != (pk.n_wires, 4) or not witness.is_contiguous():
+            raise ValueError("expected a contiguous (n_wires, 4) tensor")
+        out = torch.empty((3, n, 4), dtype=witness.dtype, device=witness.device)
+        w_ptr, o_ptr = witness.data_ptr(), out.data_ptr()
+    else:
+        witness = np.ascontiguousarray(witness, dtype=np.uint64)
+        if witness.shape != (pk.n_wires, 4):
+            raise ValueError("expected shape (n_wires, 4)")
+        out = np.zeros((3, n, 4), dtype=np.uint64)
+        w_ptr, o_ptr = witness.ctypes.data, out.ctypes.data
+    pk.ctx.check(dll.nlx_bn254_r1cs_eval(pk.ctx.handle, pk.handle, w_ptr, o_ptr, o_ptr + n * 32, o_ptr + 2 * n * 32))
+    return out
+
+
+def prove(pk, witness, r=None, s=None, abc=None):
+    """One proof: (ar, bs, krs) as 8 / 16 / 8 words.  r, s: the blinding scalars (integers below r; from `secrets` when not
+    given); abc: the solver's (a, b, c), each (2^log_n, 4) words, numpy or device - otherwise computed from the key's matrices."""
+    r = secrets.randbelow(R) if r is None else int(r)
+    s = secrets.randbelow(R) if s is None else int(s)
+    if not (0 <= r < R and 0 <= s < R):
+        raise ValueError("r and s must be below the group order")
+    wk, w_ptr, rows = _buf(witness, np.uint64, 4)
+    if rows != pk.n_wires:
+        raise ValueError("the witness has %d rows, the key %d wires" % (rows, pk.n_wires))
+    keep, ptrs = [], [None, None, None]
+    if abc is not None:
+        for i, v in enumerate(abc):
+            k, p, rows = _buf(v, np.uint64, 4)
+            if rows != 1 << pk.log_n:
+                raise ValueError("a, b, c hold 2^log_n rows")
+            keep.append(k)
+            ptrs[i] = p
+    rw, sw = fr_words(r), fr_words(s)
+    ar, bs, krs = np.zeros(8, dtype=np.uint64), np.zeros(16, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+    pk.ctx.check(dll.nlx_bn254_groth16_prove(pk.ctx.handle, pk.handle, w_ptr, ptrs[0], ptrs[1], ptrs[2], ptr(rw), ptr(sw),
+                                             ptr(ar), ptr(bs), ptr(krs)))
+    return ar, bs, krs
+
+
+def _lex_largest(y):
+    return int(y) > (Q - 1) // 2
+
+
+def g1_compress(words):
+    """G1Affine.Bytes(): x big-endian, 0b10 / 0b11 in the top two bits for the smaller / larger y, 0b01 for infinity"""
+    p = B.bn254_g1_unpack(words)
+    if p is None:
+        return bytes([0x40]) + bytes(31)
+    b = bytearray(p[0].to_bytes(32, "big"))
+    b[0] |= 0xC0 if _lex_largest(p[1]) else 0x80
+    return bytes(b)
+
+
+def g2_compress(words):
+    """G2Affine.Bytes(): X.A1 || X.A0 big-endian, flags as for G1; "largest" Y decided on Y.A1, on Y.A0 when Y.A1 is zero"""
+    p = B.bn254_g2_unpack(words)
+    if p is None:
+        return bytes([0x40]) + bytes(63)
+    (x0, x1), (y0, y1) = p
+    b = bytearray(x1.to_bytes(32, "big") + x0.to_bytes(32, "big"))
+    b[0] |= 0xC0 if _lex_largest(y0 if y1 == 0 else y1) else 0x80
+    return bytes(b)
+
+
+def proof_bytes(ar, bs, krs):
+    """gnark's Proof.WriteTo without commitments: Ar, Bs, Krs compressed, the empty Commitments slice (uint32 0, big-endian) and
+    CommitmentPok (a compressed point at infinity) - 164 bytes"""
+    return g1_compress(ar) + g2_compress(bs) + g1_compress(krs) + (0).to_bytes(4, "big") + bytes([0x40]) + bytes(31)

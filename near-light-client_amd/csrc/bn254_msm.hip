@@ -26,16 +26,13 @@
 #include <vector>
 #include "bn254_f29.hpp"
 #include "bn254_fp.hpp"
+#include "bn254_msm.hpp"
 #include "ctx.hpp"
 #include "transcript.hpp"
 #include "../../include/nlx.h"
 
 namespace nlx {
 namespace msm {
-
-using namespace bnf;
-typedef Fp<QP> Fq;
-typedef Fp<RP> Fr;
 
 constexpr int WINDOW_BITS = 16, N_WINDOWS = 16, N_BUCKETS = 1 << WINDOW_BITS;
 // The top window's digit has only 14 bits (scalars are below r < 2^254): its 12 388 buckets would hold five times the
@@ -44,97 +41,6 @@ constexpr int WINDOW_BITS = 16, N_WINDOWS = 16, N_BUCKETS = 1 << WINDOW_BITS;
 // reduction adds up before weighing them.
 constexpr int TOP_SUB_BITS = 2;
 
-// ---- host side (the short tail of an MSM, nlx_bn254_g1_sum): eight 32-bit limbs, bn254_fp.hpp ----
-struct H1 {   // Fq
-    typedef Fq T;
-    static constexpr int WORDS64 = 4;
-    static T zero() { return bnf::zero<QP>(); }
-    static T one() { return bnf::one<QP>(); }
-    static bool is_zero(const T& a) { return bnf::is_zero(a); }
-    static T add(const T& a, const T& b) { return bnf::add(a, b); }
-    static T sub(const T& a, const T& b) { return bnf::sub(a, b); }
-    static T mul(const T& a, const T& b) { return bnf::mul(a, b); }
-    static T sqr(const T& a) { return bnf::mul(a, a); }
-    static T neg(const T& a) { return bnf::neg(a); }
-    static T inv(const T& a) { return bnf::inv_host(a); }
-    static T load(const uint64_t* w) { return load_words<QP>(w); }
-    static void store(const T& a, uint64_t* w) { store_words(a, w); }
-    static T from_canonical(const uint32_t* w) {   // plain integer limbs -> Montgomery form
-        Fq x;
-        for (int l = 0; l < 8; l++) x.v[l] = w[l];
-        return to_mont(x);
-    }
-};
-struct H2 {   // Fq2 = Fq[u] / (u^2 + 1); gnark-crypto's E2{A0, A1}
-    struct T { Fq c0, c1; };
-    static constexpr int WORDS64 = 8;
-    static T zero() { return T{bnf::zero<QP>(), bnf::zero<QP>()}; }
-    static T one() { return T{bnf::one<QP>(), bnf::zero<QP>()}; }
-    static bool is_zero(const T& a) { return bnf::is_zero(a.c0) && bnf::is_zero(a.c1); }
-    static T add(const T& a, const T& b) { return T{bnf::add(a.c0, b.c0), bnf::add(a.c1, b.c1)}; }
-    static T sub(const T& a, const T& b) { return T{bnf::sub(a.c0, b.c0), bnf::sub(a.c1, b.c1)}; }
-    static T mul(const T& a, const T& b) {
-        const Fq t0 = bnf::mul(a.c0, b.c0), t1 = bnf::mul(a.c1, b.c1);
-        const Fq s = bnf::mul(bnf::add(a.c0, a.c1), bnf::add(b.c0, b.c1));
-        return T{bnf::sub(t0, t1), bnf::sub(bnf::sub(s, t0), t1)};
-    }
-    static T sqr(const T& a) { return mul(a, a); }
-    static T neg(const T& a) { return T{bnf::neg(a.c0), bnf::neg(a.c1)}; }
-    static T inv(const T& a) {   // conj(a) / (a0^2 + a1^2)
-        const Fq d = bnf::inv_host(bnf::add(bnf::mul(a.c0, a.c0), bnf::mul(a.c1, a.c1)));
-        return T{bnf::mul(a.c0, d), bnf::neg(bnf::mul(a.c1, d))};
-    }
-    static T load(const uint64_t* w) { return T{load_words<QP>(w), load_words<QP>(w + 4)}; }
-    static void store(const T& a, uint64_t* w) { store_words(a.c0, w); store_words(a.c1, w + 4); }
-    static T from_canonical(const uint32_t* w) { return T{H1::from_canonical(w), H1::from_canonical(w + 8)}; }
-};
-template <class H> struct AffineH { typename H::T x, y; };   // (0, 0) = the point at infinity (gnark-crypto's convention)
-template <class H> struct JacH { typename H::T x, y, z; };   // z = 0: the point at infinity
-template <class H> inline typename H::T hdbl(const typename H::T& a) { return H::add(a, a); }
-template <class H> inline JacH<H> hinf() { return JacH<H>{H::one(), H::one(), H::zero()}; }
-// dbl-2009-l (a = 0): 2M + 5S
-template <class H> inline JacH<H> hjdbl(const JacH<H>& p) {
-    typedef typename H::T T;
-    if (H::is_zero(p.z)) return p;
-    const T a = H::sqr(p.x), b = H::sqr(p.y), c = H::sqr(b);
-    const T d = hdbl<H>(H::sub(H::sub(H::sqr(H::add(p.x, b)), a), c));
-    const T e = H::add(hdbl<H>(a), a), f = H::sqr(e);
-    JacH<H> r;
-    r.x = H::sub(f, hdbl<H>(d));
-    r.y = H::sub(H::mul(e, H::sub(d, r.x)), hdbl<H>(hdbl<H>(hdbl<H>(c))));
-    r.z = hdbl<H>(H::mul(p.y, p.z));
-    return r;
-}
-// add-2007-bl: 11M + 5S; equal and opposite points are real cases
-template <class H> inline JacH<H> hjadd(const JacH<H>& p, const JacH<H>& q) {
-    typedef typename H::T T;
-    if (H::is_zero(p.z)) return q;
-    if (H::is_zero(q.z)) return p;
-    const T z1z1 = H::sqr(p.z), z2z2 = H::sqr(q.z);
-    const T u1 = H::mul(p.x, z2z2), u2 = H::mul(q.x, z1z1);
-    const T s1 = H::mul(H::mul(p.y, q.z), z2z2), s2 = H::mul(H::mul(q.y, p.z), z1z1);
-    const T h = H::sub(u2, u1);
-    T r = H::sub(s2, s1);
-    if (H::is_zero(h)) return H::is_zero(r) ? hjdbl<H>(p) : hinf<H>();
-    r = hdbl<H>(r);
-    const T i = H::sqr(hdbl<H>(h)), j = H::mul(h, i), v = H::mul(u1, i);
-    JacH<H> o;
-    o.x = H::sub(H::sub(H::sqr(r), j), hdbl<H>(v));
-    o.y = H::sub(H::mul(r, H::sub(v, o.x)), hdbl<H>(H::mul(s1, j)));
-    o.z = H::mul(H::sub(H::sub(H::sqr(H::add(p.z, q.z)), z1z1), z2z2), h);
-    return o;
-}
-template <class H> inline JacH<H> hfrom_affine(const AffineH<H>& p) {
-    return (H::is_zero(p.x) && H::is_zero(p.y)) ? hinf<H>() : JacH<H>{p.x, p.y, H::one()};
-}
-// Jacobian -> affine words (all zero for the point at infinity)
-template <class H> inline void hstore_affine(const JacH<H>& p, uint64_t* out) {
-    for (int i = 0; i < 2 * H::WORDS64; i++) out[i] = 0;
-    if (H::is_zero(p.z)) return;
-    const typename H::T zi = H::inv(p.z), zi2 = H::sqr(zi);
-    H::store(H::mul(p.x, zi2), out);
-    H::store(H::mul(p.y, H::mul(zi2, zi)), out + H::WORDS64);
-}
 
 // ---- the group law on the device's field representation (bn254_f29.hpp), written over a field policy F: F1 = Fq (loose
 // values; the bound of every intermediate is noted where it is not a product - products are < 2^255 whenever the two
@@ -227,15 +133,19 @@ template <class F>
 __device__ __forceinline__ JacT<F> jneg29(const JacT<F>& p) { return JacT<F>{p.x, F::tighten(F::template sub<4>(F::zero(), p.y)), p.z}; }
 
 // gnark-crypto G1Affine / G2Affine words -> the device form, once per point
+// (index != NULL: out[i] = points[index[i]], the point at infinity for index[i] = 0xFFFFFFFF - the Groth16 key's queries,
+// filtered of their points at infinity, expanded to the wires' index space)
 template <class F>
-__global__ __launch_bounds__(256) void k_msm_convert(const uint64_t* __restrict__ points, size_t n, PackedT<F>* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_msm_convert(const uint64_t* __restrict__ points, const uint32_t* __restrict__ index, size_t n,
+                                                     PackedT<F>* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     constexpr int W = F::WORDS;   // 32-bit words per coordinate
+    const size_t src = index ? index[i] : i;
     uint32_t w[2 * W];
 #pragma unroll
     for (int k = 0; k < W; k++) {
-        const uint64_t x = points[(size_t)W * i + k];
+        const uint64_t x = (index && src == 0xFFFFFFFFu) ? 0 : points[(size_t)W * src + k];
         w[2 * k] = (uint32_t)x;
         w[2 * k + 1] = (uint32_t)(x >> 32);
     }
@@ -435,15 +345,129 @@ __global__ __launch_bounds__(64) void k_g1_multiples(AffPacked base_packed, uint
 }  // namespace msm
 }  // namespace nlx
 
+// ---- the phases (bn254_msm.hpp) ----
+namespace nlx {
+namespace msm {
+
+// the hipcub sort's scratch size for n pairs (host arithmetic only: nothing is launched)
+static size_t sort_tmp_bytes(size_t n) {
+    size_t tmp_bytes = 0;
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint16_t*)nullptr, (uint16_t*)nullptr, (const uint32_t*)nullptr,
+                                             (uint32_t*)nullptr, (int)n, 0, WINDOW_BITS, (hipStream_t)nullptr);
+    return tmp_bytes ? tmp_bytes : 16;
+}
+// every device block of one decomposition; 0 or NLX_E_NOMEM with nothing left allocated
+static int32_t alloc_digits(nlx_ctx* ctx, size_t n, SortedDigits* out) {
+    const size_t pairs = n * N_WINDOWS, n_hist = (size_t)N_WINDOWS * N_BUCKETS;
+    out->n = n;
+    out->tmp[0] = ctx->alloc(pairs * 2);   // keys [window][n]
+    out->tmp[1] = ctx->alloc(n * 2);       // one window's sorted keys
+    out->tmp[2] = ctx->alloc(n * 4);       // 0 .. n - 1
+    out->tmp[3] = ctx->alloc(sort_tmp_bytes(n));
+    out->sorted = (uint32_t*)ctx->alloc(pairs * 4);
+    out->lo = (uint32_t*)ctx->alloc(n_hist * 2 * 4);   // range_lo | range_hi
+    out->hi = out->lo ? out->lo + n_hist : nullptr;
+    if (out->tmp[0] && out->tmp[1] && out->tmp[2] && out->tmp[3] && out->sorted && out->lo) return NLX_OK;
+    release_digits(ctx, out);   // nothing has been enqueued on these blocks
+    return ctx->fail(NLX_E_NOMEM, "MSM of %llu points: device memory for the digit keys / sorted indices", (unsigned long long)n);
+}
+// `out` may come allocated (alloc_digits: msm_run keeps the allocations out of its timed interval) or empty
+int32_t sort_digits(nlx_ctx* ctx, const uint64_t* d_scalars, size_t n, int montgomery, SortedDigits* out) {
+    hipStream_t st = ctx->stream;
+    if (!out->sorted) {
+        const int32_t arc = alloc_digits(ctx, n, out);
+        if (arc) return arc;
+    }
+    const size_t n_hist = (size_t)N_WINDOWS * N_BUCKETS, tmp_bytes = sort_tmp_bytes(n);
+    uint16_t* d_keys = (uint16_t*)out->tmp[0];
+    uint16_t* d_keys_sorted = (uint16_t*)out->tmp[1];
+    uint32_t* d_iota = (uint32_t*)out->tmp[2];
+    void* d_tmp = out->tmp[3];
+    int32_t rc = NLX_OK;
+    auto hip_ok = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && !rc) rc = ctx->hip_fail(e, what);
+        return e == hipSuccess;
+    };
+    const unsigned blocks_n = (unsigned)((n + 255) / 256);
+    hip_ok(hipMemsetAsync(out->lo, 0, n_hist * 2 * 4, st), "hipMemsetAsync");
+    hipLaunchKernelGGL(k_msm_digits, dim3(blocks_n), dim3(256), 0, st, d_scalars, n, montgomery, d_keys);
+    hipLaunchKernelGGL(k_msm_iota, dim3(blocks_n), dim3(256), 0, st, d_iota, n);
+    for (int w = 0; w < N_WINDOWS && !rc; w++) {
+        size_t tb = tmp_bytes;
+        hip_ok(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_keys + (size_t)w * n, d_keys_sorted, d_iota, out->sorted + (size_t)w * n,
+                                                  (int)n, 0, WINDOW_BITS, st), "hipcub::SortPairs");
+        hipLaunchKernelGGL(k_msm_ranges, dim3(blocks_n), dim3(256), 0, st, d_keys_sorted, n, (uint32_t)((size_t)w * n),
+                           out->lo + (size_t)w * N_BUCKETS, out->hi + (size_t)w * N_BUCKETS);
+    }
+    // the sort's temporaries stay allocated until release_digits: the caller releases after it has synchronised
+    if (rc) {
+        (void)hipStreamSynchronize(st);   // kernels above may still be running on these blocks
+        release_digits(ctx, out);
+    }
+    return rc;
+}
+void release_digits(nlx_ctx* ctx, SortedDigits* s) {
+    for (void* p : {(void*)s->sorted, (void*)s->lo, s->tmp[0], s->tmp[1], s->tmp[2], s->tmp[3]})
+        if (p) ctx->release(p);
+    *s = SortedDigits{};
+}
+
+constexpr int RED_LANES_G1 = 256, RED_LANES_G2 = 128;   // the block's partial sums live in LDS: 108 bytes per G1 point, 216 per G2 point
+template <int LANES> constexpr int n_window_sums() { return N_WINDOWS * (N_BUCKETS / (LANES * RED_CHUNK)); }
+
+size_t converted_point_bytes(int g2) { return g2 ? sizeof(PackedT<F2>) : sizeof(PackedT<F1>); }
+size_t bucket_bytes(int g2) { return (size_t)N_WINDOWS * N_BUCKETS * (g2 ? sizeof(JacT<F2>) : sizeof(JacT<F1>)); }
+size_t window_sum_bytes(int g2) {
+    return g2 ? n_window_sums<RED_LANES_G2>() * sizeof(JacWordsT<F2>) : n_window_sums<RED_LANES_G1>() * sizeof(JacWordsT<F1>);
+}
+void convert_points(nlx_ctx* ctx, const uint64_t* d_points, const uint32_t* d_index, size_t n, int g2, void* d_out) {
+    const unsigned blocks_n = (unsigned)((n + 255) / 256);
+    if (g2) hipLaunchKernelGGL(k_msm_convert<F2>, dim3(blocks_n), dim3(256), 0, ctx->stream, d_points, d_index, n, (PackedT<F2>*)d_out);
+    else hipLaunchKernelGGL(k_msm_convert<F1>, dim3(blocks_n), dim3(256), 0, ctx->stream, d_points, d_index, n, (PackedT<F1>*)d_out);
+}
+void bucket_reduce(nlx_ctx* ctx, const SortedDigits& s, const void* d_converted, int g2, void* d_buckets, void* d_window_sums) {
+    constexpr unsigned n_hist = N_WINDOWS * N_BUCKETS;
+    hipStream_t st = ctx->stream;
+    if (g2) {
+        hipLaunchKernelGGL(k_msm_buckets_g2, dim3(n_hist / 64), dim3(64), 0, st, (const PackedT<F2>*)d_converted, s.sorted, s.lo, s.hi, (JacT<F2>*)d_buckets);
+        hipLaunchKernelGGL((k_msm_reduce<F2, RED_LANES_G2>), dim3(n_window_sums<RED_LANES_G2>()), dim3(RED_LANES_G2), 0, st,
+                           (const JacT<F2>*)d_buckets, (JacWordsT<F2>*)d_window_sums);
+    } else {
+        hipLaunchKernelGGL(k_msm_buckets, dim3(n_hist / 64), dim3(64), 0, st, (const PackedT<F1>*)d_converted, s.sorted, s.lo, s.hi, (JacT<F1>*)d_buckets);
+        hipLaunchKernelGGL((k_msm_reduce<F1, RED_LANES_G1>), dim3(n_window_sums<RED_LANES_G1>()), dim3(RED_LANES_G1), 0, st,
+                           (const JacT<F1>*)d_buckets, (JacWordsT<F1>*)d_window_sums);
+    }
+}
+// the blocks' partial sums per window, then sum_w 2^(16 w) W_w
+template <class F, class H, int LANES>
+static JacH<H> window_tail(const void* window_sums) {
+    constexpr int RED_BLOCKS = N_BUCKETS / (LANES * RED_CHUNK);
+    const JacWordsT<F>* words = (const JacWordsT<F>*)window_sums;
+    JacH<H> acc = hinf<H>();
+    for (int w = N_WINDOWS - 1; w >= 0; w--) {
+        if (w != N_WINDOWS - 1)
+            for (int k = 0; k < WINDOW_BITS; k++) acc = hjdbl<H>(acc);
+        for (int k = 0; k < RED_BLOCKS; k++) {
+            const JacWordsT<F>& p = words[w * RED_BLOCKS + k];
+            acc = hjadd<H>(acc, JacH<H>{H::from_canonical(p.x), H::from_canonical(p.y), H::from_canonical(p.z)});   // z = 0 stays 0
+        }
+    }
+    return acc;
+}
+JacH<H1> window_tail_g1(const void* window_sums) { return window_tail<F1, H1, RED_LANES_G1>(window_sums); }
+JacH<H2> window_tail_g2(const void* window_sums) { return window_tail<F2, H2, RED_LANES_G2>(window_sums); }
+
+}  // namespace msm
+}  // namespace nlx
+
 using namespace nlx;
 
 namespace {
 
-// One MSM: F = the device field policy (bn254_f29.hpp), H = the host's, LANES = lanes per window-reduction block (the
-// block's partial sums live in LDS: 108 bytes per G1 point, 216 per G2 point).
-template <class F, class H, int LANES, class BucketKernel>
-int32_t msm_run(nlx_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t n, uint32_t flags, uint64_t* out,
-                BucketKernel bucket_kernel, const char* sample_name) {
+// One MSM: the four phases in a row on the caller's points and scalars
+template <class H>
+int32_t msm_run(nlx_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t n, uint32_t flags, uint64_t* out, int g2,
+                const char* sample_name) {
     using namespace nlx::msm;
     constexpr int OUT_WORDS = 2 * H::WORDS64;
     if (!ctx) return NLX_E_INVAL;
@@ -458,74 +482,42 @@ int32_t msm_run(nlx_ctx* ctx, const uint64_t* points, const uint64_t* scalars, u
     if (sp.status) return sp.status;
     Staged ss(ctx, scalars, (size_t)n * 32, true, false);
     if (ss.status) return ss.status;
-    const size_t pairs = (size_t)n * N_WINDOWS, n_hist = (size_t)N_WINDOWS * N_BUCKETS;
-    uint16_t* d_keys = (uint16_t*)ctx->alloc(pairs * 2);
-    uint16_t* d_keys_sorted = (uint16_t*)ctx->alloc((size_t)n * 2);
-    uint32_t* d_iota = (uint32_t*)ctx->alloc((size_t)n * 4);
-    uint32_t* d_sorted = (uint32_t*)ctx->alloc(pairs * 4);
-    uint32_t* d_lo = (uint32_t*)ctx->alloc(n_hist * 2 * 4);   // range_lo | range_hi
-    uint32_t* d_hi = d_lo ? d_lo + n_hist : nullptr;
-    JacT<F>* d_buckets = (JacT<F>*)ctx->alloc(n_hist * sizeof(JacT<F>));
-    PackedT<F>* d_pts = (PackedT<F>*)ctx->alloc((size_t)n * sizeof(PackedT<F>));   // the points in the kernels' field representation
-    constexpr int RED_BLOCKS = N_BUCKETS / (LANES * RED_CHUNK), N_WSUM = N_WINDOWS * RED_BLOCKS;
-    JacWordsT<F>* d_wsum = (JacWordsT<F>*)ctx->alloc(N_WSUM * sizeof(JacWordsT<F>));
-    size_t tmp_bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_keys, d_keys_sorted, d_iota, d_sorted, (int)n, 0, WINDOW_BITS, st);
-    void* d_tmp = ctx->alloc(tmp_bytes ? tmp_bytes : 16);
+    void* d_buckets = ctx->alloc(bucket_bytes(g2));
+    void* d_pts = ctx->alloc((size_t)n * converted_point_bytes(g2));   // the points in the kernels' field representation
+    void* d_wsum = ctx->alloc(window_sum_bytes(g2));
+    SortedDigits sd;
     auto release_all = [&]() {
-        for (void* p : {(void*)d_keys, (void*)d_keys_sorted, (void*)d_iota, (void*)d_sorted, (void*)d_lo, (void*)d_buckets, (void*)d_pts,
-                        (void*)d_wsum, d_tmp})
+        for (void* p : {d_buckets, d_pts, d_wsum})
             if (p) ctx->release(p);
+        release_digits(ctx, &sd);
     };
-    if (!d_keys || !d_keys_sorted || !d_iota || !d_sorted || !d_lo || !d_buckets || !d_pts || !d_wsum || !d_tmp) {
+    if (!d_buckets || !d_pts || !d_wsum) {
         release_all();
-        return ctx->fail(NLX_E_NOMEM, "MSM of %llu points: device memory for the digit keys / sorted indices / buckets", (unsigned long long)n);
+        return ctx->fail(NLX_E_NOMEM, "MSM of %llu points: device memory for the points / buckets", (unsigned long long)n);
     }
-    int32_t rc = NLX_OK;
-    auto hip_ok = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && !rc) rc = ctx->hip_fail(e, what);
-        return e == hipSuccess;
-    };
-    const unsigned blocks_n = (unsigned)((n + 255) / 256);
-    hip_ok(hipMemsetAsync(d_lo, 0, n_hist * 2 * 4, st), "hipMemsetAsync");
+    int32_t rc = alloc_digits(ctx, (size_t)n, &sd);
+    if (rc) {
+        release_all();
+        return rc;
+    }
     // algorithmic bytes of the whole job: every point and scalar once
     ctx->begin_kernel(sample_name, (32.0 + OUT_WORDS * 8.0) * (double)n, n);
-    hipLaunchKernelGGL(k_msm_digits, dim3(blocks_n), dim3(256), 0, st, ss.as<uint64_t>(), (size_t)n,
-                       (flags & NLX_BN254_MONTGOMERY) ? 1 : 0, d_keys);
-    hipLaunchKernelGGL(k_msm_iota, dim3(blocks_n), dim3(256), 0, st, d_iota, (size_t)n);
-    hipLaunchKernelGGL(k_msm_convert<F>, dim3(blocks_n), dim3(256), 0, st, sp.as<uint64_t>(), (size_t)n, d_pts);
-    for (int w = 0; w < N_WINDOWS && !rc; w++) {
-        size_t tb = tmp_bytes;
-        hip_ok(hipcub::DeviceRadixSort::SortPairs(d_tmp, tb, d_keys + (size_t)w * n, d_keys_sorted, d_iota, d_sorted + (size_t)w * n,
-                                                  (int)n, 0, WINDOW_BITS, st), "hipcub::SortPairs");
-        hipLaunchKernelGGL(k_msm_ranges, dim3(blocks_n), dim3(256), 0, st, d_keys_sorted, (size_t)n, (uint32_t)((size_t)w * n),
-                           d_lo + (size_t)w * N_BUCKETS, d_hi + (size_t)w * N_BUCKETS);
-    }
+    rc = sort_digits(ctx, ss.as<uint64_t>(), (size_t)n, (flags & NLX_BN254_MONTGOMERY) ? 1 : 0, &sd);
     if (!rc) {
-        hipLaunchKernelGGL(bucket_kernel, dim3((unsigned)(n_hist / 64)), dim3(64), 0, st, d_pts, d_sorted, d_lo, d_hi, d_buckets);
-        hipLaunchKernelGGL((k_msm_reduce<F, LANES>), dim3(N_WSUM), dim3(LANES), 0, st, d_buckets, d_wsum);
+        convert_points(ctx, sp.as<uint64_t>(), nullptr, (size_t)n, g2, d_pts);
+        bucket_reduce(ctx, sd, d_pts, g2, d_buckets, d_wsum);
     }
     ctx->end_kernel();
-    std::vector<JacWordsT<F>> words(N_WSUM);
-    if (!rc) rc = fetch(ctx, words.data(), d_wsum, (size_t)N_WSUM * sizeof(JacWordsT<F>));
-    hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize");
-    hip_ok(hipGetLastError(), "kernel launch");
+    std::vector<unsigned char> words(window_sum_bytes(g2));
+    if (!rc) rc = fetch(ctx, words.data(), d_wsum, words.size());
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess && !rc) rc = ctx->hip_fail(e, "hipStreamSynchronize");
+    e = hipGetLastError();
+    if (e != hipSuccess && !rc) rc = ctx->hip_fail(e, "kernel launch");
     release_all();
     if (rc) return rc;
-    // the blocks' partial sums per window, sum_w 2^(16 w) W_w, then to affine
-    std::vector<JacH<H>> part(N_WSUM), wsum(N_WINDOWS);
-    for (int k = 0; k < N_WSUM; k++)
-        part[k] = JacH<H>{H::from_canonical(words[k].x), H::from_canonical(words[k].y), H::from_canonical(words[k].z)};   // z = 0 stays 0
-    for (int w = 0; w < N_WINDOWS; w++) {
-        wsum[w] = part[w * RED_BLOCKS];
-        for (int k = 1; k < RED_BLOCKS; k++) wsum[w] = hjadd<H>(wsum[w], part[w * RED_BLOCKS + k]);
-    }
-    JacH<H> acc = wsum[N_WINDOWS - 1];
-    for (int w = N_WINDOWS - 2; w >= 0; w--) {
-        for (int k = 0; k < WINDOW_BITS; k++) acc = hjdbl<H>(acc);
-        acc = hjadd<H>(acc, wsum[w]);
-    }
-    hstore_affine<H>(acc, out);
+    if constexpr (H::WORDS64 == 4) hstore_affine<H>(window_tail_g1(words.data()), out);
+    else hstore_affine<H>(window_tail_g2(words.data()), out);
     return NLX_OK;
 }
 
@@ -546,11 +538,11 @@ int32_t affine_sum(const uint64_t* points, uint64_t n, uint64_t* out) {
 
 extern "C" int32_t nlx_bn254_msm_g1(nlx_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t n, uint32_t flags,
                                     uint64_t out[8]) NLX_TRY {
-    return msm_run<f29::F1, msm::H1, 256>(ctx, points, scalars, n, flags, out, msm::k_msm_buckets, "bn254_msm_g1");
+    return msm_run<msm::H1>(ctx, points, scalars, n, flags, out, 0, "bn254_msm_g1");
 } NLX_CATCH(ctx)
 extern "C" int32_t nlx_bn254_msm_g2(nlx_ctx* ctx, const uint64_t* points, const uint64_t* scalars, uint64_t n, uint32_t flags,
                                     uint64_t out[16]) NLX_TRY {
-    return msm_run<f29::F2, msm::H2, 128>(ctx, points, scalars, n, flags, out, msm::k_msm_buckets_g2, "bn254_msm_g2");
+    return msm_run<msm::H2>(ctx, points, scalars, n, flags, out, 1, "bn254_msm_g2");
 } NLX_CATCH(ctx)
 
 // Sum of n affine points on the host (gnark-crypto layouts as above): what joins the partial results of an MSM whose points
@@ -579,7 +571,7 @@ extern "C" int32_t nlx_bn254_g1_multiples(nlx_ctx* ctx, const uint64_t base[8], 
         hipError_t e = hipMemcpyAsync(d_base, base, 64, hipMemcpyHostToDevice, st);
         AffPacked* d_packed = (AffPacked*)(d_base + 8);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_msm_convert<f29::F1>, dim3(1), dim3(256), 0, st, d_base, (size_t)1, d_packed);
+            hipLaunchKernelGGL(k_msm_convert<f29::F1>, dim3(1), dim3(256), 0, st, d_base, (const uint32_t*)nullptr, (size_t)1, d_packed);
             e = hipMemcpyAsync(&packed, d_packed, sizeof(AffPacked), hipMemcpyDeviceToHost, st);
         }
         if (e == hipSuccess) e = hipStreamSynchronize(st);

@@ -25,3 +25,10 @@ import numpy as np
 pts = nlx.bn254_g1_pack([(1, 2), (1, 2)])
 ks = np.array([[3, 0, 0, 0], [4, 0, 0, 0]], dtype=np.uint64)
 print("msm 7G", nlx.bn254_g1_unpack(nlx.bn254_msm_g1(ctx, pts, ks)))
+G = nlx.bn254_groth16
+inf8, inf16 = np.zeros(8, dtype=np.uint64), np.zeros(16, dtype=np.uint64)
+one = np.array([1, 1], dtype=np.uint64)              # the circuit "w1 * w1 = w1" on the wires (ONE, w1); a key of points at infinity
+r1cs = {m: (np.array([0, 1], dtype=np.uint64), np.array([1], dtype=np.uint32), np.array([0], dtype=np.uint32)) for m in "ABC"}
+r1cs["coeffs"] = G.fr_pack([1])
+key = G.ProvingKey(ctx, 1, 2, 1, 1, inf8[None][:0], inf8[None][:0], inf16[None][:0], inf8[None], inf8[None], one, one, inf8, inf8, inf8, inf16, inf16, r1cs=r1cs)
+print("groth16", len(G.proof_bytes(*G.prove(key, G.fr_pack([1, 1])))))
