@@ -17,8 +17,8 @@
 // The point formulas in bn254_msm.hip state the bound of every intermediate.
 #pragma once
 #include <cstdint>
+#include "bn254_fp.hpp"   // the element in memory: eight 32-bit limbs
 #if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
 #define F29_HD __host__ __device__ __forceinline__
 #else
 #define F29_HD inline   // plain g++ build of the host test
@@ -258,6 +258,17 @@ F29_HD void to_canonical256(const Fe& a, uint32_t* w) {
         if (k + 1 < 8) w[k + 1] |= (uint32_t)(x >> 32);
     }
 }
+
+#if defined(__HIPCC__)
+// element i of an array of 32-byte elements (bnf::load / bnf::store), re-sliced: whatever value below 2^256 rests there.
+// The store writes the limbs as they are (a < 2^256); a caller that owes canonical words stores canonical<M>(a).
+__device__ __forceinline__ Fe load(const uint64_t* p, size_t i) { return from_words256(bnf::load<bnf::RP>(p, i).v); }
+__device__ __forceinline__ void store(uint64_t* p, size_t i, const Fe& a) {
+    bnf::Fp<bnf::RP> w;
+    to_words256(a, w.v);
+    bnf::store(p, i, w);
+}
+#endif
 
 // ---- field policies for the curve code (bn254_msm.hip): the group law is written once over `F::T` ----
 // F1: the base field itself, loose values with the bounds stated at each formula.

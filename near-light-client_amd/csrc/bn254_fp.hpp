@@ -1,16 +1,22 @@
 // 256-bit Montgomery arithmetic (R = 2^256, eight 32-bit limbs, CIOS) over a modulus picked by a parameter struct - BN254's
 // base field Fq (curve coordinates) and scalar field Fr - shared by host and device code of the MSM (bn254_msm.hip;
 // SURVEY.md §8 row f.4).  The element layout is gnark-crypto's fp.Element / fr.Element: four little-endian 64-bit words in
-// Montgomery form, so a Go caller's []G1Affine and []fr.Element can be handed over as they lie in memory.  The NTT
-// (bn254.hip) keeps its own copy of the Fr code with its hand-tuned butterflies.
+// Montgomery form, so a Go caller's []G1Affine and []fr.Element can be handed over as they lie in memory.  This is the only
+// eight-limb code: the NTT's host tables (bn254.hip), the Groth16 rows (bn254_groth16.hip) and every "is this word string a
+// residue" check (below_mod) use it; the hot kernels compute on bn254_f29.hpp's nine 29-bit limbs, which includes this header
+// for the 32-byte element in memory.  Builds with plain g++ as well (tests/native/bn254_fp_check.cpp).
 #pragma once
-#include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define BNF_HD __host__ __device__ __forceinline__
+#else
+#define BNF_HD inline   // plain g++ build of the host test
+#endif
 
 namespace nlx {
 namespace bnf {
-
-#define BNF_HD __host__ __device__ __forceinline__
 
 template <class P>
 struct Fp {
@@ -63,6 +69,10 @@ BNF_HD Fp<P> one() {
 #pragma unroll
     for (int i = 0; i < 8; i++) r.v[i] = P::one(i);
     return r;
+}
+// gnark-crypto's 2^28-th root of unity of Fr, 5^((r-1)/2^28), in Montgomery form: what the NTT's tables are powers of
+inline Fp<RP> root28() {
+    return Fp<RP>{{0x80d13d9cu, 0x636e7355u, 0x2445ffd6u, 0xa22bf374u, 0x1eb203d8u, 0x56452ac0u, 0x2963f9e7u, 0x1860ef94u}};
 }
 template <class P>
 BNF_HD bool is_zero(const Fp<P>& a) {
@@ -203,7 +213,49 @@ BNF_HD void store_words(const Fp<P>& a, uint64_t* w) {
 #pragma unroll
     for (int i = 0; i < 4; i++) w[i] = (uint64_t)a.v[2 * i] | ((uint64_t)a.v[2 * i + 1] << 32);
 }
+// is the integer of four little-endian words below the modulus?  Montgomery words (fp.Element / fr.Element) are residues, so
+// this is also "is it an element at all": the one range check behind every entry point that takes scalars from the caller.
+// It is !geq_mod(load_words<P>(w)) (the host test holds the two together), spelled on the 64-bit words the callers have in
+// hand: the PoseidonBN128 kernels check their inputs with it, and on 32-bit limbs they came out a register larger.
+template <class P>
+BNF_HD bool below_mod(const uint64_t* w) {
+#pragma unroll
+    for (int i = 3; i >= 0; i--) {
+        const uint64_t m = (uint64_t)P::mod(2 * i) | ((uint64_t)P::mod(2 * i + 1) << 32);
+        if (w[i] != m) return w[i] < m;
+    }
+    return false;
+}
 
+#if defined(__HIPCC__)
+// element i of an array of 32-byte elements (four words each, 32-byte aligned): two 128-bit accesses
+template <class P>
+__device__ __forceinline__ Fp<P> load(const uint64_t* p, size_t i) {
+    const uint4* q = reinterpret_cast<const uint4*>(p + 4 * i);
+    const uint4 a = q[0], b = q[1];
+    Fp<P> r;
+    r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
+    r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
+    return r;
+}
+template <class P>
+__device__ __forceinline__ void store(uint64_t* p, size_t i, const Fp<P>& r) {
+    uint4* q = reinterpret_cast<uint4*>(p + 4 * i);
+    q[0] = make_uint4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    q[1] = make_uint4(r.v[4], r.v[5], r.v[6], r.v[7]);
+}
+#endif
+
+// Montgomery-form power (host: the NTT's roots of unity)
+template <class P>
+inline Fp<P> pow_host(Fp<P> b, uint64_t e) {
+    Fp<P> r = one<P>();
+    for (; e; e >>= 1) {
+        if (e & 1) r = mul(r, b);
+        b = sqr(b);
+    }
+    return r;
+}
 // a^(p-2) by square-and-multiply (host side of the MSM: one inversion per result)
 template <class P>
 inline Fp<P> inv_host(const Fp<P>& a) {

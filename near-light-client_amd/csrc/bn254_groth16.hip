@@ -48,25 +48,13 @@ struct R1csDev {
     uint32_t log_n, n_constraints;
 };
 
-__device__ __forceinline__ Fr ld_fr(const uint64_t* p, size_t i) {
-    const uint4* q = reinterpret_cast<const uint4*>(p + 4 * i);
-    const uint4 a = q[0], b = q[1];
-    Fr r;
-    r.v[0] = a.x, r.v[1] = a.y, r.v[2] = a.z, r.v[3] = a.w, r.v[4] = b.x, r.v[5] = b.y, r.v[6] = b.z, r.v[7] = b.w;
-    return r;
-}
-__device__ __forceinline__ void st_fr(uint64_t* p, size_t i, const Fr& v) {
-    uint4* q = reinterpret_cast<uint4*>(p + 4 * i);
-    q[0] = make_uint4(v.v[0], v.v[1], v.v[2], v.v[3]);
-    q[1] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
-}
 __device__ __forceinline__ Fr term(const R1csDev& p, int m, uint32_t k, const uint64_t* __restrict__ witness, const Fr& acc) {
     const uint32_t code = p.code[m][k];
-    const Fr w = ld_fr(witness, p.wire[m][k]);
+    const Fr w = load<RP>(witness, p.wire[m][k]);
     const uint32_t kind = code >> TERM_ID_BITS;
     if (kind == TERM_PLUS) return add(acc, w);
     if (kind == TERM_MINUS) return sub(acc, w);
-    return add(acc, mul(w, ld_fr(p.coeffs, code & TERM_ID_MASK)));
+    return add(acc, mul(w, load<RP>(p.coeffs, code & TERM_ID_MASK)));
 }
 
 // lane t = matrix (t >> log_n), row (t & (N - 1)); rows past n_constraints are zero; long rows are the other kernel's
@@ -83,7 +71,7 @@ __global__ __launch_bounds__(256) void k_r1cs_rows(R1csDev p, const uint64_t* __
 #pragma unroll 1
         for (uint32_t k = lo; k < hi; k++) acc = term(p, m, k, witness, acc);
     }
-    st_fr(out, t, acc);
+    store(out, t, acc);
 }
 // one wave per long row: long_rows[j] = matrix << 30 | row
 __global__ __launch_bounds__(256) void k_r1cs_long_rows(R1csDev p, const uint32_t* __restrict__ long_rows, uint32_t n_long,
@@ -103,14 +91,14 @@ __global__ __launch_bounds__(256) void k_r1cs_long_rows(R1csDev p, const uint32_
         for (int i = 0; i < 8; i++) o.v[i] = (uint32_t)__shfl_down((int)acc.v[i], d, 64);
         acc = add(acc, o);
     }
-    if (lane == 0) st_fr(out, ((size_t)m << p.log_n) + row, acc);
+    if (lane == 0) store(out, ((size_t)m << p.log_n) + row, acc);
 }
 
 // a_i b_i = c_i on H: the first failing row (atomicMin over the waves that saw one)
 __global__ __launch_bounds__(256) void k_g16_check(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, const uint64_t* __restrict__ c,
                                                    size_t n, uint32_t* __restrict__ first_bad) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool bad = i < n && !equal(mul(ld_fr(a, i), ld_fr(b, i)), ld_fr(c, i));
+    const bool bad = i < n && !equal(mul(load<RP>(a, i), load<RP>(b, i)), load<RP>(c, i));
     if (bad) atomicMin(first_bad, (uint32_t)i);
 }
 
@@ -135,15 +123,6 @@ struct nlx_bn254_groth16_key {
 };
 
 namespace {
-
-bool fr_below_r(const uint64_t* w) {
-    static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
-    for (int i = 3; i >= 0; i--) {
-        if (w[i] < R[i]) return true;
-        if (w[i] > R[i]) return false;
-    }
-    return false;
-}
 
 // the caller's array on the host, wherever it lies
 template <class T>
@@ -225,7 +204,7 @@ int32_t key_r1cs(nlx_bn254_groth16_key* key, const nlx_bn254_groth16_key_desc* d
     store_words(bnf::neg(bnf::one<bnf::RP>()), MINUS_ONE);
     std::vector<uint8_t> kind((size_t)d->n_coeffs);
     for (uint64_t i = 0; i < d->n_coeffs; i++) {
-        if (!fr_below_r(&coeffs[4 * i])) return ctx->fail(NLX_E_RANGE, "coefficient %llu is not below r", (unsigned long long)i);
+        if (!bnf::below_mod<bnf::RP>(&coeffs[4 * i])) return ctx->fail(NLX_E_RANGE, "coefficient %llu is not below r", (unsigned long long)i);
         kind[i] = !memcmp(&coeffs[4 * i], ONE, 32) ? g16::TERM_PLUS : !memcmp(&coeffs[4 * i], MINUS_ONE, 32) ? g16::TERM_MINUS : g16::TERM_GENERAL;
     }
     rc = key_upload(key, coeffs, &key->r1cs.coeffs);
@@ -404,33 +383,30 @@ extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16
     if (!given && (a || b || c)) return ctx->fail(NLX_E_INVAL, "a, b, c come together or not at all");
     if (!given && !key->has_r1cs) return ctx->fail(NLX_E_INVAL, "a, b, c are NULL and the key was built without its R1CS matrices");
     if (is_device_ptr(r) || is_device_ptr(s)) return ctx->fail(NLX_E_INVAL, "r and s are host values");
-    if (!fr_below_r(r) || !fr_below_r(s)) return ctx->fail(NLX_E_RANGE, "r or s is not below the group order");
+    if (!bnf::below_mod<bnf::RP>(r) || !bnf::below_mod<bnf::RP>(s)) return ctx->fail(NLX_E_RANGE, "r or s is not below the group order");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)1 << key->log_n, nw = (size_t)key->n_wires;
     Staged sw(ctx, witness, nw * 32, true, false);
     if (sw.status) return sw.status;
     const uint64_t* d_w = sw.as<uint64_t>();
-    std::vector<void*> tmp;
     SortedDigits wires_sorted[g16::G16_WIRE_SORTS], h_sorted;
-    auto done = [&](int32_t code) {
-        (void)hipStreamSynchronize(st);
-        for (void* p : tmp) ctx->release(p);
-        for (auto& sd : wires_sorted) release_digits(ctx, &sd);
-        release_digits(ctx, &h_sorted);
-        return code;
-    };
-    auto dev = [&](size_t bytes) {
-        void* p = ctx->alloc(bytes);
-        if (p) tmp.push_back(p);
-        return p;
-    };
+    struct ReleaseSorted {   // runs after `scratch` below (declared later, destroyed first) has synchronised the stream
+        nlx_ctx* ctx;
+        SortedDigits *wires, *h;
+        ~ReleaseSorted() {
+            for (int i = 0; i < g16::G16_WIRE_SORTS; i++) release_digits(ctx, wires + i);
+            release_digits(ctx, h);
+        }
+    } release_sorted{ctx, wires_sorted, &h_sorted};
+    Scratch scratch(ctx);
+    auto dev = [&](size_t bytes) { return scratch.alloc(bytes); };
     uint64_t* d_abc = (uint64_t*)dev(3 * n * 32);
     uint64_t* d_h = (uint64_t*)dev(n * 32);
     uint32_t* d_bad = (uint32_t*)dev(64);
     void* d_buckets = dev(bucket_bytes(1));   // one block serves all five bucket passes (the stream runs them in order)
     unsigned char* d_wsum = (unsigned char*)dev(4 * window_sum_bytes(0) + window_sum_bytes(1));
-    if (!d_abc || !d_h || !d_bad || !d_buckets || !d_wsum) return done(ctx->fail(NLX_E_NOMEM, "Groth16 proof: device memory"));
+    if (!d_abc || !d_h || !d_bad || !d_buckets || !d_wsum) return ctx->fail(NLX_E_NOMEM, "Groth16 proof: device memory");
     // the solver's a, b, c, or the key's matrices times the witness
     hipError_t e = hipSuccess;
     if (given) {
@@ -451,18 +427,18 @@ extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16
     if (e == hipSuccess) e = hipMemcpyAsync(w0, d_w, 32, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "Groth16 proof: a, b, c"));
+    if (e != hipSuccess) return ctx->hip_fail(e, "Groth16 proof: a, b, c");
     uint64_t ONE[4];
     store_words(bnf::one<RP>(), ONE);
-    if (memcmp(w0, ONE, 32)) return done(ctx->fail(NLX_E_INVAL, "the witness does not start with the constant wire 1"));
-    if (first_bad != 0xFFFFFFFFu) return done(ctx->fail(NLX_E_INVAL, "the witness does not satisfy the circuit: a b != c at row %u", first_bad));
+    if (memcmp(w0, ONE, 32)) return ctx->fail(NLX_E_INVAL, "the witness does not start with the constant wire 1");
+    if (first_bad != 0xFFFFFFFFu) return ctx->fail(NLX_E_INVAL, "the witness does not satisfy the circuit: a b != c at row %u", first_bad);
     // h, device-resident (gnark's domain generator 5 as the coset shift)
     Fr five = bnf::zero<RP>();
     five.v[0] = 5;
     uint64_t shift[4];
     store_words(to_mont(five), shift);
     int32_t rc = nlx_bn254_groth16_quotient(ctx, key->log_n, d_abc, d_abc + n * 4, d_abc + 2 * n * 4, shift, d_h);
-    if (rc) return done(rc);
+    if (rc) return rc;
     // the MSMs: four queries over the wire vector on one set of sorted indices, G1.Z over h on its own
     const void* query[4] = {key->a, key->b1, key->b2, key->k};
     const int query_g2[4] = {0, 0, 1, 0};
@@ -485,14 +461,14 @@ extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16
         if (!rc) bucket_reduce(ctx, h_sorted, key->z, 0, d_buckets, wsum_at[4]);
     }
     ctx->end_kernel();
-    if (rc) return done(rc);
+    if (rc) return rc;
     std::vector<unsigned char> words(4 * window_sum_bytes(0) + window_sum_bytes(1));
     rc = fetch(ctx, words.data(), d_wsum, words.size());
     if (!rc) {
         e = hipGetLastError();
         if (e != hipSuccess) rc = ctx->hip_fail(e, "kernel launch");
     }
-    if (rc) return done(rc);
+    if (rc) return rc;
     // the tail, on the host
     const size_t off1 = window_sum_bytes(0), off2 = 2 * off1, off3 = off2 + window_sum_bytes(1), off4 = off3 + off1;
     const JacH<H1> msm_a = window_tail_g1(words.data()), msm_b1 = window_tail_g1(words.data() + off1), msm_k = window_tail_g1(words.data() + off3);
@@ -510,5 +486,5 @@ extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16
     hstore_affine<H1>(ar, ar_out);
     hstore_affine<H2>(bs, bs_out);
     hstore_affine<H1>(krs, krs_out);
-    return done(NLX_OK);
+    return NLX_OK;
 } NLX_CATCH(ctx)

@@ -26,6 +26,7 @@
 // product of two data values needs the factor 2^5 put back (x32).
 #include <algorithm>
 #include <cstring>
+#include <deque>
 #include <vector>
 #include "ctx.hpp"
 #include "bn254_f29.hpp"
@@ -36,20 +37,8 @@ namespace bnp {
 using f29::Fe;
 typedef f29::RMod RM;
 
-__device__ __forceinline__ Fe ld(const uint64_t* p, size_t i) {
-    const uint4* q = reinterpret_cast<const uint4*>(p + 4 * i);
-    const uint4 a = q[0], b = q[1];
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    return f29::from_words256(w);
-}
-__device__ __forceinline__ void st(uint64_t* p, size_t i, const Fe& v) {   // canonical: what gnark keeps in memory
-    const Fe c = f29::canonical<RM>(v);
-    uint32_t w[8];
-    f29::to_words256(c, w);
-    uint4* q = reinterpret_cast<uint4*>(p + 4 * i);
-    q[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    q[1] = make_uint4(w[4], w[5], w[6], w[7]);
-}
+__device__ __forceinline__ Fe ld(const uint64_t* p, size_t i) { return f29::load(p, i); }
+__device__ __forceinline__ void st(uint64_t* p, size_t i, const Fe& v) { f29::store(p, i, f29::canonical<RM>(v)); }   // canonical: what gnark keeps in memory
 __device__ __forceinline__ Fe mul(const Fe& a, const Fe& b) { return f29::mul<RM>(a, b); }
 __device__ __forceinline__ Fe add(const Fe& a, const Fe& b) { return f29::tighten<RM>(f29::add(a, b)); }
 __device__ __forceinline__ Fe sub(const Fe& a, const Fe& b) { return f29::tighten<RM>(f29::sub<4, RM>(a, b)); }
@@ -407,38 +396,36 @@ using namespace nlx;
 
 namespace {
 // H_j in place over seq (len elements, optionally read backwards); d_zpow: the powers z^(64^k), device, 4 words each
-int32_t horner_scan(nlx_ctx* ctx, uint64_t* seq, size_t len, int rev, const uint64_t* d_zpow, uint32_t level, std::vector<void*>& tmp) {
+int32_t horner_scan(nlx_ctx* ctx, uint64_t* seq, size_t len, int rev, const uint64_t* d_zpow, uint32_t level, Scratch& scratch) {
     hipStream_t st = ctx->stream;
     const size_t runs = (len + bnp::SCAN_RUN - 1) / bnp::SCAN_RUN;
     if (runs <= 1) {
         hipLaunchKernelGGL(bnp::k_horner_final, dim3(1), dim3(64), 0, st, seq, len, rev, d_zpow + 4 * level, (const uint64_t*)nullptr);
         return NLX_OK;
     }
-    uint64_t* d_runs = (uint64_t*)ctx->alloc(runs * 32);
+    uint64_t* d_runs = scratch.alloc_as<uint64_t>(runs * 32);
     if (!d_runs) return NLX_E_NOMEM;
-    tmp.push_back(d_runs);
     const unsigned blocks = (unsigned)((runs + 63) / 64);
     hipLaunchKernelGGL(bnp::k_horner_local, dim3(blocks), dim3(64), 0, st, seq, len, rev, d_zpow + 4 * level, d_runs);
-    const int32_t rc = horner_scan(ctx, d_runs, runs, 0, d_zpow, level + 1, tmp);
+    const int32_t rc = horner_scan(ctx, d_runs, runs, 0, d_zpow, level + 1, scratch);
     if (rc) return rc;
     hipLaunchKernelGGL(bnp::k_horner_final, dim3(blocks), dim3(64), 0, st, seq, len, rev, d_zpow + 4 * level, d_runs);
     return NLX_OK;
 }
 
 // inclusive product scan of seq (I-form) in place; to_d on the outermost level only
-int32_t mul_scan(nlx_ctx* ctx, uint64_t* seq, size_t len, int to_d, std::vector<void*>& tmp) {
+int32_t mul_scan(nlx_ctx* ctx, uint64_t* seq, size_t len, int to_d, Scratch& scratch) {
     hipStream_t st = ctx->stream;
     const size_t runs = (len + bnp::SCAN_RUN - 1) / bnp::SCAN_RUN;
     if (runs <= 1) {
         hipLaunchKernelGGL(bnp::k_mulscan_final, dim3(1), dim3(64), 0, st, seq, len, (const uint64_t*)nullptr, to_d);
         return NLX_OK;
     }
-    uint64_t* d_runs = (uint64_t*)ctx->alloc(runs * 32);
+    uint64_t* d_runs = scratch.alloc_as<uint64_t>(runs * 32);
     if (!d_runs) return NLX_E_NOMEM;
-    tmp.push_back(d_runs);
     const unsigned blocks = (unsigned)((runs + 63) / 64);
     hipLaunchKernelGGL(bnp::k_mulscan_local, dim3(blocks), dim3(64), 0, st, seq, len, d_runs);
-    const int32_t rc = mul_scan(ctx, d_runs, runs, 0, tmp);
+    const int32_t rc = mul_scan(ctx, d_runs, runs, 0, scratch);
     if (rc) return rc;
     hipLaunchKernelGGL(bnp::k_mulscan_final, dim3(blocks), dim3(64), 0, st, seq, len, d_runs, to_d);
     return NLX_OK;
@@ -458,111 +445,83 @@ int32_t nlx_bn254_plonk_grand_product(nlx_ctx* ctx, uint32_t log_n, const uint64
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)1 << log_n;
-    std::vector<void*> tmp;
-    auto done = [&](int32_t code) {
-        (void)hipStreamSynchronize(st);
-        for (void* p : tmp) ctx->release(p);
-        return code;
-    };
-    const uint64_t* in[6] = {l, r, o, s1, s2, s3};
-    const uint64_t* dev[6];
-    for (int i = 0; i < 6; i++) {
-        if (is_device_ptr(in[i])) { dev[i] = in[i]; continue; }
-        uint64_t* d = (uint64_t*)ctx->alloc(n * 32);
-        if (!d) return done(NLX_E_NOMEM);
-        tmp.push_back(d);
-        hipError_t e = hipMemcpyAsync(d, in[i], n * 32, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
-        dev[i] = d;
-    }
-    uint64_t* d_z = is_device_ptr(z_out) ? z_out : (uint64_t*)ctx->alloc(n * 32);
-    uint64_t* d_small = (uint64_t*)ctx->alloc(4 * 32 + 32 + 64);
-    if (d_z && d_z != z_out) tmp.push_back(d_z);
-    if (d_small) tmp.push_back(d_small);
-    if (!d_z || !d_small) return done(NLX_E_NOMEM);
+    Scratch scratch(ctx);
+    Staged sl(ctx, l, n * 32, true, false), sr(ctx, r, n * 32, true, false), so(ctx, o, n * 32, true, false);
+    Staged ss1(ctx, s1, n * 32, true, false), ss2(ctx, s2, n * 32, true, false), ss3(ctx, s3, n * 32, true, false);
+    Staged sz(ctx, z_out, n * 32, false, true);
+    for (const Staged* s : {&sl, &sr, &so, &ss1, &ss2, &ss3, &sz})
+        if (s->status) return s->status;
+    uint64_t* d_z = sz.as<uint64_t>();
+    uint64_t* d_small = scratch.alloc_as<uint64_t>(4 * 32 + 32 + 64);
+    if (!d_small) return NLX_E_NOMEM;
     uint64_t h[16];
     memcpy(h, beta, 32); memcpy(h + 4, gamma, 32); memcpy(h + 8, k1, 32); memcpy(h + 12, k2, 32);
     hipError_t e = hipMemcpyAsync(d_small, h, sizeof h, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // h leaves scope
+    if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
     uint32_t* d_flag = (uint32_t*)(d_small + 20);
-    bnp::GrandProductParams gp{dev[0], dev[1], dev[2], dev[3], dev[4], dev[5], d_small, d_z, d_small + 16, log_n};
+    bnp::GrandProductParams gp{sl.as<uint64_t>(), sr.as<uint64_t>(), so.as<uint64_t>(), ss1.as<uint64_t>(), ss2.as<uint64_t>(), ss3.as<uint64_t>(),
+                               d_small, d_z, d_small + 16, log_n};
     hipLaunchKernelGGL(bnp::k_gp_ratios, dim3((unsigned)(((n + bnp::GP_RUN - 1) / bnp::GP_RUN + 63) / 64)), dim3(64), 0, st, gp);
-    int32_t rc = mul_scan(ctx, d_z, n, 1, tmp);
-    if (rc) return done(rc);
+    int32_t rc = mul_scan(ctx, d_z, n, 1, scratch);
+    if (rc) return rc;
     hipLaunchKernelGGL(bnp::k_gp_closes, dim3(1), dim3(1), 0, st, d_z, n, d_small + 16, d_flag);
     uint32_t flag = 0;
     e = hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && d_z != z_out) e = hipMemcpyAsync(z_out, d_z, n * 32, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "copy out"));
+    if (e == hipSuccess && sz.finish()) return sz.status;
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // flag is a local
+    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
     hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return done(ctx->hip_fail(le, "kernel launch"));
+    if (le != hipSuccess) return ctx->hip_fail(le, "kernel launch");
     if (closes) *closes = flag ? 0 : 1;
-    return done(NLX_OK);
+    return NLX_OK;
 } NLX_CATCH(ctx)
 
-// a host scalar handed over as fr.Element words (Montgomery residue): any value below r is a residue, anything else is not an
-// fr.Element and the 29-bit-limb arithmetic's bounds would not hold for it
-static bool fr_words_below_r(const uint64_t* w) {
-    static const uint64_t R[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
-    for (int i = 3; i >= 0; i--) {
-        if (w[i] < R[i]) return true;
-        if (w[i] > R[i]) return false;
-    }
-    return false;
-}
-
+// Host scalars come as fr.Element words (Montgomery residues): bnf::below_mod<RP> refuses anything that is not one - the
+// 29-bit-limb arithmetic's bounds would not hold for it.
 int32_t nlx_bn254_groth16_quotient(nlx_ctx* ctx, uint32_t log_n, const uint64_t* a, const uint64_t* b, const uint64_t* c,
                                    const uint64_t coset_shift[4], uint64_t* h_out) NLX_TRY {
     if (!ctx) return NLX_E_INVAL;
     if (!a || !b || !c || !coset_shift || !h_out) return ctx->fail(NLX_E_INVAL, "NULL argument");
     if (log_n < 1 || log_n > 28) return ctx->fail(NLX_E_RANGE, "log_n must be in [1, 28]");
     if (is_device_ptr(coset_shift)) return ctx->fail(NLX_E_INVAL, "the coset shift is a host value");
-    if (!fr_words_below_r(coset_shift)) return ctx->fail(NLX_E_RANGE, "the coset shift is not below r");
+    if (!bnf::below_mod<bnf::RP>(coset_shift)) return ctx->fail(NLX_E_RANGE, "the coset shift is not below r");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)1 << log_n;
-    std::vector<void*> tmp;
-    auto done = [&](int32_t code) {
-        (void)hipStreamSynchronize(st);
-        for (void* p : tmp) ctx->release(p);
-        return code;
-    };
-    uint64_t* d_abc = (uint64_t*)ctx->alloc(3 * n * 32);
-    uint64_t* d_small = (uint64_t*)ctx->alloc(96);   // shift | 1 / (shift^n - 1) | flag
-    if (d_abc) tmp.push_back(d_abc);
-    if (d_small) tmp.push_back(d_small);
-    if (!d_abc || !d_small) return done(NLX_E_NOMEM);
+    Scratch scratch(ctx);
+    uint64_t* d_abc = scratch.alloc_as<uint64_t>(3 * n * 32);   // the call's own copy: a, b, c are transformed in place, the caller's are not
+    uint64_t* d_small = scratch.alloc_as<uint64_t>(96);         // shift | 1 / (shift^n - 1) | flag
+    if (!d_abc || !d_small) return NLX_E_NOMEM;
     const uint64_t* in[3] = {a, b, c};
     for (int i = 0; i < 3; i++) {
         hipError_t e = hipMemcpyAsync(d_abc + (size_t)i * n * 4, in[i], n * 32, is_device_ptr(in[i]) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
+        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
     }
     hipError_t e = hipMemcpy(d_small, coset_shift, 32, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpy"));
+    if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpy");
     hipLaunchKernelGGL(bnp::k_g16_const, dim3(1), dim3(1), 0, st, d_small, log_n, d_small + 4, (uint32_t*)(d_small + 8));
     {
         uint32_t bad = 0;
         e = hipMemcpyAsync(&bad, d_small + 8, 4, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
-        if (bad) return done(ctx->fail(NLX_E_INVAL, "coset shift lies in the evaluation subgroup (x^n - 1 vanishes on the coset)"));
+        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
+        if (bad) return ctx->fail(NLX_E_INVAL, "coset shift lies in the evaluation subgroup (x^n - 1 vanishes on the coset)");
     }
     // FFTInverse(DIF) -> FFT(DIT, OnCoset): no reordering pass; then a b - c over the coset's constant x^n - 1
     int32_t rc = nlx_bn254_ntt_batch_coset(ctx, d_abc, 3, log_n, 1, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_OUT, nullptr);
     if (!rc) rc = nlx_bn254_ntt_batch_coset(ctx, d_abc, 3, log_n, 0, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_IN, coset_shift);
-    if (rc) return done(rc);
+    if (rc) return rc;
     hipLaunchKernelGGL(bnp::k_g16_pointwise, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_abc, d_abc + n * 4, d_abc + 2 * n * 4,
                        d_small + 4, d_abc, n);
     rc = nlx_bn254_ntt_batch_coset(ctx, d_abc, 1, log_n, 1, NLX_BN254_MONTGOMERY, coset_shift);
-    if (rc) return done(rc);
+    if (rc) return rc;
     e = hipMemcpyAsync(h_out, d_abc, n * 32, is_device_ptr(h_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "copy out"));
+    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
     hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return done(ctx->hip_fail(le, "kernel launch"));
-    return done(NLX_OK);
+    if (le != hipSuccess) return ctx->hip_fail(le, "kernel launch");
+    return NLX_OK;
 } NLX_CATCH(ctx)
 
 int32_t nlx_bn254_fr_lincomb(nlx_ctx* ctx, uint64_t m, uint32_t n_terms, const uint64_t* const* polys, const uint64_t* scalars,
@@ -573,39 +532,30 @@ int32_t nlx_bn254_fr_lincomb(nlx_ctx* ctx, uint64_t m, uint32_t n_terms, const u
     if (is_device_ptr(polys) || is_device_ptr(scalars)) return ctx->fail(NLX_E_INVAL, "the pointer array and the scalars are host arrays");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    std::vector<void*> tmp;
-    auto done = [&](int32_t code) {
-        (void)hipStreamSynchronize(st);
-        for (void* p : tmp) ctx->release(p);
-        return code;
-    };
+    Scratch scratch(ctx);
     bnp::LincombParams lp{};
+    std::deque<Staged> sp;   // the polynomials are read in place
     for (uint32_t t = 0; t < n_terms; t++) {
-        if (!polys[t]) return done(ctx->fail(NLX_E_INVAL, "NULL polynomial"));
-        if (is_device_ptr(polys[t])) { lp.polys[t] = polys[t]; continue; }
-        uint64_t* d = (uint64_t*)ctx->alloc(m * 32);
-        if (!d) return done(NLX_E_NOMEM);
-        tmp.push_back(d);
-        hipError_t e = hipMemcpyAsync(d, polys[t], m * 32, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
-        lp.polys[t] = d;
+        if (!polys[t]) return ctx->fail(NLX_E_INVAL, "NULL polynomial");
+        sp.emplace_back(ctx, polys[t], m * 32, true, false);
+        if (sp[t].status) return sp[t].status;
+        lp.polys[t] = sp[t].as<uint64_t>();
     }
-    uint64_t* d_sc = (uint64_t*)ctx->alloc((size_t)n_terms * 32);
-    uint64_t* d_out = is_device_ptr(out) ? out : (uint64_t*)ctx->alloc(m * 32);
-    if (d_sc) tmp.push_back(d_sc);
-    if (d_out && d_out != out) tmp.push_back(d_out);
-    if (!d_sc || !d_out) return done(NLX_E_NOMEM);
+    Staged sout(ctx, out, m * 32, false, true);
+    if (sout.status) return sout.status;
+    uint64_t* d_sc = scratch.alloc_as<uint64_t>((size_t)n_terms * 32);
+    if (!d_sc) return NLX_E_NOMEM;
     hipError_t e = hipMemcpy(d_sc, scalars, (size_t)n_terms * 32, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpy"));
+    if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpy");
     hipLaunchKernelGGL(bnp::k_to_iform, dim3(1), dim3(64), 0, st, d_sc, n_terms);
-    lp.sc_i = d_sc; lp.out = d_out; lp.m = m; lp.n_terms = n_terms;
+    lp.sc_i = d_sc; lp.out = sout.as<uint64_t>(); lp.m = m; lp.n_terms = n_terms;
     hipLaunchKernelGGL(bnp::k_lincomb, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, lp);
-    if (d_out != out) e = hipMemcpyAsync(out, d_out, m * 32, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "copy out"));
+    if (sout.finish()) return sout.status;
+    e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
     hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return done(ctx->hip_fail(le, "kernel launch"));
-    return done(NLX_OK);
+    if (le != hipSuccess) return ctx->hip_fail(le, "kernel launch");
+    return NLX_OK;
 } NLX_CATCH(ctx)
 
 int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_args* a, uint64_t* t_out, int32_t* high_chunk_is_zero) NLX_TRY {
@@ -621,7 +571,7 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
         if (!a->blinding || is_device_ptr(a->blinding)) return ctx->fail(NLX_E_INVAL, "the blinding scalars are host values (nine elements of four words)");
         if (a->log_n < 3) return ctx->fail(NLX_E_RANGE, "a blinded quotient needs log_n >= 3 (3 n + 6 coefficients on 4 n points)");
         for (int i = 0; i < 9; i++)
-            if (!fr_words_below_r(a->blinding + 4 * i)) return ctx->fail(NLX_E_RANGE, "a blinding scalar is not below r");
+            if (!bnf::below_mod<bnf::RP>(a->blinding + 4 * i)) return ctx->fail(NLX_E_RANGE, "a blinding scalar is not below r");
     }
     // n_commit, qcp, pi2 lie behind the struct a caller of the earlier ABI allocated: read only under the flag
     const uint32_t K = commit ? a->n_commit : 0;
@@ -636,18 +586,14 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
         for (const uint64_t* q : sc)
             if (!q || is_device_ptr(q)) return ctx->fail(NLX_E_INVAL, "the challenges and shifts are host values (four words each)");
         for (const uint64_t* q : sc)
-            if (!fr_words_below_r(q)) return ctx->fail(NLX_E_RANGE, "a challenge or shift is not below r (fr.Element words are residues)");
+            if (!bnf::below_mod<bnf::RP>(q)) return ctx->fail(NLX_E_RANGE, "a challenge or shift is not below r (fr.Element words are residues)");
     }
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     const uint32_t log_n = a->log_n, P0 = a->pi ? 13 : 12, P = P0 + 2 * K;   // in ev after (pi): qcp_0 .. pi2_0 ..
     const size_t n = (size_t)1 << log_n, N4 = 4 * n;
-    std::vector<void*> tmp;
-    auto dalloc = [&](size_t bytes) -> uint64_t* {
-        void* p = ctx->alloc(bytes);
-        if (p) tmp.push_back(p);
-        return (uint64_t*)p;
-    };
+    Scratch scratch(ctx);
+    auto dalloc = [&](size_t bytes) { return scratch.alloc_as<uint64_t>(bytes); };
     int32_t rc = NLX_OK;
     uint64_t* d_in = dalloc((size_t)P * n * 32);
     uint64_t* d_ev = dalloc((size_t)P * N4 * 32);
@@ -655,12 +601,7 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
     uint64_t* d_linv = dalloc(N4 * 32);
     uint64_t* d_t = dalloc(N4 * 32);
     uint64_t* d_small = dalloc(6 * 32 + sizeof(bnp::Consts) + 64 + 9 * 32);
-    auto done = [&](int32_t code) {
-        (void)hipStreamSynchronize(st);
-        for (void* p : tmp) ctx->release(p);
-        return code;
-    };
-    if (!d_in || !d_ev || !d_x || !d_linv || !d_t || !d_small) return done(NLX_E_NOMEM);
+    if (!d_in || !d_ev || !d_x || !d_linv || !d_t || !d_small) return NLX_E_NOMEM;
     bnp::Consts* d_k = (bnp::Consts*)(d_small + 6 * 4);
     uint32_t* d_flag = (uint32_t*)((char*)d_k + sizeof(bnp::Consts));
     uint64_t* d_blind = (uint64_t*)((char*)d_flag + 64);
@@ -672,29 +613,29 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
         if (e == hipSuccess && blinded) e = hipMemcpyAsync(d_blind, a->blinding, 9 * 32, hipMemcpyHostToDevice, st);   // caller-owned: outlives the sync below
         if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 8, st);   // [0] high chunk non-zero, [1] Z_H vanishes on the coset
         if (e == hipSuccess) e = hipStreamSynchronize(st);   // h leaves scope
-        if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
+        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
     }
     for (uint32_t i = 0; i < P; i++) {
         const uint64_t* src = i < P0 ? polys[i] : i < P0 + K ? a->qcp[i - P0] : a->pi2[i - P0 - K];
         hipError_t e = hipMemcpyAsync(d_in + (size_t)i * n * 4, src, n * 32,
                                       is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpyAsync"));
+        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
     }
     hipLaunchKernelGGL(bnp::k_plonk_consts, dim3(1), dim3(1), 0, st, d_k, log_n, d_small, d_flag + 1);
     hipLaunchKernelGGL(bnp::k_plonk_domain, dim3((unsigned)(((N4 + bnp::DOMAIN_RUN - 1) / bnp::DOMAIN_RUN + 63) / 64)), dim3(64), 0, st, d_k, log_n, d_x, d_linv);
     // 1. FFTInverse(DIF): values on H -> coefficients in bit-reversed order
     rc = nlx_bn254_ntt_batch_coset(ctx, d_in, P, log_n, 1, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_OUT, nullptr);
-    if (rc) return done(rc);
+    if (rc) return rc;
     // 2. zero-padded to 4n in bit-reversed order (coefficient at position p of n sits at 4 p of 4n), then FFT(DIT, OnCoset)
     {
         hipError_t e = hipMemsetAsync(d_ev, 0, (size_t)P * N4 * 32, st);
         for (uint32_t i = 0; i < P && e == hipSuccess; i++)
             e = hipMemcpy2DAsync(d_ev + (size_t)i * N4 * 4, 128, d_in + (size_t)i * n * 4, 32, 32, n, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpy2DAsync"));
+        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpy2DAsync");
     }
     if (blinded) hipLaunchKernelGGL(bnp::k_plonk_blind, dim3(1), dim3(64), 0, st, d_ev, d_blind, log_n);
     rc = nlx_bn254_ntt_batch_coset(ctx, d_ev, P, log_n + 2, 0, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_IN, a->coset_shift);
-    if (rc) return done(rc);
+    if (rc) return rc;
     // 3. the quotient's values on the coset
     bnp::QuotientParams qp{d_ev, d_x, d_linv, d_k, d_t, log_n, a->pi ? 1u : 0u, K};
     ctx->begin_kernel("plonk_quotient", 32.0 * N4 * (P + 4));
@@ -703,23 +644,23 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
     ctx->end_kernel();
     // 4. back to coefficients
     rc = nlx_bn254_ntt_batch_coset(ctx, d_t, 1, log_n + 2, 1, NLX_BN254_MONTGOMERY, a->coset_shift);
-    if (rc) return done(rc);
+    if (rc) return rc;
     // coefficients that must vanish: 3 n .. 4 n - 1 (3 n + 6 .. with blinding: the blinded wires raise the quotient's degree by six)
     const size_t t_keep = blinded ? 3 * n + 6 : 3 * n;
     hipLaunchKernelGGL(bnp::k_any_nonzero, dim3((unsigned)(((N4 - t_keep) * 4 + 255) / 256)), dim3(256), 0, st, d_t + t_keep * 4, (N4 - t_keep) * 4, d_flag);
     uint32_t flags[2] = {0, 0};
     hipError_t e = hipMemcpyAsync(flags, d_flag, 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "copy out"));
-    if (flags[1]) return done(ctx->fail(NLX_E_INVAL, "coset shift lies in the evaluation subgroup (x^n - 1 vanishes on the coset)"));
+    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
+    if (flags[1]) return ctx->fail(NLX_E_INVAL, "coset shift lies in the evaluation subgroup (x^n - 1 vanishes on the coset)");
     e = hipMemcpyAsync(t_out, d_t, (blinded ? N4 : 3 * n) * 32, is_device_ptr(t_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "copy out"));
+    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
     hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return done(ctx->hip_fail(le, "kernel launch"));
+    if (le != hipSuccess) return ctx->hip_fail(le, "kernel launch");
     const uint32_t flag = flags[0];
     if (high_chunk_is_zero) *high_chunk_is_zero = flag ? 0 : 1;
-    return done(NLX_OK);
+    return NLX_OK;
 } NLX_CATCH(ctx)
 
 int32_t nlx_bn254_kzg_open(nlx_ctx* ctx, const uint64_t* coeffs, uint64_t m, const uint64_t zeta[4], const uint64_t* srs,
@@ -731,39 +672,32 @@ int32_t nlx_bn254_kzg_open(nlx_ctx* ctx, const uint64_t* coeffs, uint64_t m, con
     if (is_device_ptr(zeta) || is_device_ptr(y_out)) return ctx->fail(NLX_E_INVAL, "the point and the value are host words");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    std::vector<void*> tmp;
-    auto done = [&](int32_t code) {
-        (void)hipStreamSynchronize(st);
-        for (void* p : tmp) ctx->release(p);
-        return code;
-    };
-    uint64_t* d_h = (uint64_t*)ctx->alloc(m * 32);
-    uint64_t* d_z = (uint64_t*)ctx->alloc(32 + 8 * 32);
-    if (d_h) tmp.push_back(d_h);
-    if (d_z) tmp.push_back(d_z);
-    if (!d_h || !d_z) return done(NLX_E_NOMEM);
+    Scratch scratch(ctx);
+    uint64_t* d_h = scratch.alloc_as<uint64_t>(m * 32);   // the call's own copy: the scan runs in place, the caller's coefficients stay
+    uint64_t* d_z = scratch.alloc_as<uint64_t>(32 + 8 * 32);
+    if (!d_h || !d_z) return NLX_E_NOMEM;
     hipError_t e = hipMemcpyAsync(d_h, coeffs, m * 32, is_device_ptr(coeffs) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpy(d_z, zeta, 32, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "hipMemcpy"));
+    if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpy");
     uint32_t levels = 1;
     for (uint64_t len = m; len > bnp::SCAN_RUN; len = (len + bnp::SCAN_RUN - 1) / bnp::SCAN_RUN) levels++;
     hipLaunchKernelGGL(bnp::k_horner_powers, dim3(1), dim3(1), 0, st, d_z, d_z + 4, levels);
     // H_j = p_{m-1-j} + zeta H_{j-1}: the array read from the top coefficient down; afterwards position i holds h_i with
     // h_0 = p(zeta) and q_{i-1} = h_i: the quotient is the array shifted down by one
-    int32_t rc = horner_scan(ctx, d_h, m, 1, d_z + 4, 0, tmp);
-    if (rc) return done(rc);
+    int32_t rc = horner_scan(ctx, d_h, m, 1, d_z + 4, 0, scratch);
+    if (rc) return rc;
     e = hipMemcpyAsync(y_out, d_h, 32, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && quotient_out)
         e = hipMemcpyAsync(quotient_out, d_h + 4, (m - 1) * 32, is_device_ptr(quotient_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return done(ctx->hip_fail(e, "copy out"));
+    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
     hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return done(ctx->hip_fail(le, "kernel launch"));
+    if (le != hipSuccess) return ctx->hip_fail(le, "kernel launch");
     if (proof_out) {
         rc = nlx_bn254_msm_g1(ctx, srs, d_h + 4, m - 1, NLX_BN254_MONTGOMERY, proof_out);
-        if (rc) return done(rc);
+        if (rc) return rc;
     }
-    return done(NLX_OK);
+    return NLX_OK;
 } NLX_CATCH(ctx)
 
 }  // extern "C"

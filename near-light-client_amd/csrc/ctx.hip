@@ -184,6 +184,19 @@ Staged::~Staged() {
     }
 }
 
+void* Scratch::alloc(size_t bytes) {
+    void* p = ctx->alloc(bytes);
+    if (p) blocks.push_back(p);
+    return p;
+}
+
+hipError_t Scratch::drain() {
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    for (void* p : blocks) ctx->release(p);
+    blocks.clear();
+    return e;
+}
+
 }  // namespace nlx
 
 extern "C" {

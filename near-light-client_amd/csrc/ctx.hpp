@@ -132,8 +132,24 @@ struct Staged {
     bool out;
     int32_t status = 0;
     Staged(nlx_ctx* c, const void* user_ptr, size_t nbytes, bool copy_in, bool copy_out);
+    Staged(const Staged&) = delete;   // a copy would release the block twice
+    Staged& operator=(const Staged&) = delete;
     ~Staged();
     int32_t finish();  // enqueue copy-out (if any); caller synchronises
     template <class T> T* as() { return reinterpret_cast<T*>(dev); }
+};
+// RAII device scratch of one call: blocks of the context's allocator that go back to it when the call returns, by whichever
+// path - after the stream has been synchronised, so that nothing queued still works on them and no host local that a queued
+// copy reads has left scope.
+struct Scratch {
+    nlx_ctx* ctx;
+    std::vector<void*> blocks;
+    explicit Scratch(nlx_ctx* c) : ctx(c) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { if (!blocks.empty()) (void)drain(); }   // nothing handed out: nothing to wait for
+    void* alloc(size_t bytes);   // nullptr: out of device memory
+    template <class T> T* alloc_as(size_t bytes) { return reinterpret_cast<T*>(alloc(bytes)); }
+    hipError_t drain();          // synchronise the stream and give the blocks back now; the synchronise's status
 };
 }  // namespace nlx

@@ -236,11 +236,8 @@ F29_HD void to_words(const Fe& a, uint64_t* out) {
 }
 // is the integer of four little-endian words below r (canonical)?
 F29_HD bool lt_r(uint64_t w0, uint64_t w1, uint64_t w2, uint64_t w3) {
-    constexpr uint64_t R0 = 0x43e1f593f0000001ull, R1 = 0x2833e84879b97091ull, R2 = 0xb85045b68181585dull, R3 = 0x30644e72e131a029ull;
-    if (w3 != R3) return w3 < R3;
-    if (w2 != R2) return w2 < R2;
-    if (w1 != R1) return w1 < R1;
-    return w0 < R0;
+    const uint64_t w[4] = {w0, w1, w2, w3};
+    return bnf::below_mod<bnf::RP>(w);
 }
 
 }  // namespace pbn

@@ -94,6 +94,52 @@ def test_f29_field_code_built_for_the_host(tmp_path):
             assert got == a * pow(rp, -1, q) % q
 
 
+def test_fp_field_code_built_for_the_host(tmp_path):
+    """csrc/bn254_fp.hpp (the eight-limb Montgomery arithmetic behind the MSM's tail, the NTT's tables, the Groth16 rows and every
+    range check of a caller's scalars), compiled with g++: for both moduli, every operation equals the big-integer computation
+    on random operands and on 0, 1, p - 1 and R mod p, and below_mod draws the line exactly at p, word by word"""
+    import os
+    import subprocess
+    import bn254_py as bn
+    from conftest import ROOT
+    exe = str(tmp_path / "fpcheck")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-Wno-unknown-pragmas", "-fsanitize=undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "near-light-client_amd", "csrc"), os.path.join(ROOT, "tests", "native", "bn254_fp_check.cpp"), "-o", exe],
+                   check=True, capture_output=True)
+    big_r = 1 << 256
+    rng = random.Random(8)
+    cases = []
+    for name, p in (("q", bn.Q), ("r", bn.R)):
+        special = [0, 1, p - 1, big_r % p]
+        ops = [rng.randrange(p) for _ in range(200)] + special
+        for a in ops:
+            for op in ("add", "sub", "mul"):
+                cases.append((name, op, a, rng.choice(ops)))
+            for op in ("neg", "tomont", "frommont", "inv"):
+                cases.append((name, op, a, 0))
+            cases.append((name, "pow", a, rng.choice([rng.getrandbits(64), rng.randrange(1 << 16), 0, 1, 2, (1 << 64) - 1])))
+        for a in special:
+            for b in special:
+                for op in ("add", "sub", "mul"):
+                    cases.append((name, op, a, b))
+        # the comparison: around p, the top of the range, and p with exactly one of its four words one above or below
+        for v in [p - 1, p, p + 1, big_r - 1, 0] + [p + s * (1 << (64 * k)) for k in range(4) for s in (1, -1)]:
+            cases.append((name, "below", v, 0))
+    text = "".join("%s %s %x %x\n" % c for c in cases)
+    out = subprocess.run([exe], input=text, text=True, capture_output=True, check=True).stdout.split()
+    assert len(out) == len(cases)
+    for (name, op, a, b), line in zip(cases, out):
+        p = bn.Q if name == "q" else bn.R
+        r_inv = pow(big_r, -1, p)
+        got = int(line, 16)
+        want = {"add": lambda: (a + b) % p, "sub": lambda: (a - b) % p, "neg": lambda: -a % p, "mul": lambda: a * b * r_inv % p,
+                "tomont": lambda: a * big_r % p, "frommont": lambda: a * r_inv % p,
+                "inv": lambda: pow(a, -1, p) * big_r * big_r % p if a else 0,                  # (x R)^-1 in Montgomery form: R / x
+                "pow": lambda: pow(a * r_inv, b, p) * big_r % p,                               # (x R)^b: x^b R
+                "below": lambda: 1 if a < p else 0}[op]()
+        assert got == want, (name, op, hex(a), hex(b))
+
+
 def test_g1_sum_on_the_host(nlx):
     """nlx_bn254_g1_sum (host code of the MSM's tail, no GPU): sums of G1Affine words equal the model's, infinity included"""
     import bn254_py as bn

@@ -45,6 +45,9 @@ def test_quotient_chain_equals_model(nlx, ctx, bn, log_n, with_pi):
     dev = {k: torch.from_numpy(v.view(np.int64)).cuda() for k, v in packed.items()}
     t2, ok2 = nlx.bn254_plonk_quotient(ctx, dev, *sc)
     assert ok2 and np.array_equal(t2, t)
+    # the chain transforms a copy of its own: a caller's device-resident polynomials are not modified
+    for k, v in packed.items():
+        assert np.array_equal(dev[k].cpu().numpy().view(np.uint64), v), k
     # the identity the verifier checks, at a random point: (gate + alpha perm + alpha^2 L1 (z - 1))(zeta) = t(zeta) Z_H(zeta)
     zeta = rng.randrange(bn.R)
     co = {k: bn.ntt(v, inverse=True) for k, v in p.items()}
@@ -171,6 +174,15 @@ def test_groth16_quotient_equals_model(nlx, ctx, bn, log_n):
     pack = lambda v: nlx.bn254_pack([_mont(bn, v)])[0]
     got = [bn.from_montgomery(x) for x in nlx.bn254_unpack(nlx.bn254_plonk.groth16_quotient(ctx, pack(a), pack(b), pack(c))[None])[0]]
     assert got == bn.groth16_quotient(a, b, c) and got[-1] == 0
+    if log_n in (1, 4):
+        # the same from device-resident a, b, c - which the call leaves as they were (it transforms a copy of its own)
+        import torch
+        host = [pack(v) for v in (a, b, c)]
+        dev = [torch.from_numpy(v.view(np.int64)).cuda() for v in host]
+        h_dev = nlx.bn254_plonk.groth16_quotient(ctx, *dev)
+        assert [bn.from_montgomery(x) for x in nlx.bn254_unpack(h_dev[None])[0]] == got
+        for d, v in zip(dev, host):
+            assert np.array_equal(d.cpu().numpy().view(np.uint64), v)
     zeta = rng.randrange(bn.R)
     A, Bp, C = (bn.eval_poly(bn.ntt(v, inverse=True), zeta) for v in (a, b, c))
     assert (A * Bp - C) % bn.R == bn.eval_poly(got, zeta) * (pow(zeta, n, bn.R) - 1) % bn.R
