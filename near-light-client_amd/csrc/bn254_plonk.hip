@@ -593,14 +593,13 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
     const uint32_t log_n = a->log_n, P0 = a->pi ? 13 : 12, P = P0 + 2 * K;   // in ev after (pi): qcp_0 .. pi2_0 ..
     const size_t n = (size_t)1 << log_n, N4 = 4 * n;
     Scratch scratch(ctx);
-    auto dalloc = [&](size_t bytes) { return scratch.alloc_as<uint64_t>(bytes); };
     int32_t rc = NLX_OK;
-    uint64_t* d_in = dalloc((size_t)P * n * 32);
-    uint64_t* d_ev = dalloc((size_t)P * N4 * 32);
-    uint64_t* d_x = dalloc(N4 * 32);
-    uint64_t* d_linv = dalloc(N4 * 32);
-    uint64_t* d_t = dalloc(N4 * 32);
-    uint64_t* d_small = dalloc(6 * 32 + sizeof(bnp::Consts) + 64 + 9 * 32);
+    uint64_t* d_in = scratch.alloc_as<uint64_t>((size_t)P * n * 32);
+    uint64_t* d_ev = scratch.alloc_as<uint64_t>((size_t)P * N4 * 32);
+    uint64_t* d_x = scratch.alloc_as<uint64_t>(N4 * 32);
+    uint64_t* d_linv = scratch.alloc_as<uint64_t>(N4 * 32);
+    uint64_t* d_t = scratch.alloc_as<uint64_t>(N4 * 32);
+    uint64_t* d_small = scratch.alloc_as<uint64_t>(6 * 32 + sizeof(bnp::Consts) + 64 + 9 * 32);
     if (!d_in || !d_ev || !d_x || !d_linv || !d_t || !d_small) return NLX_E_NOMEM;
     bnp::Consts* d_k = (bnp::Consts*)(d_small + 6 * 4);
     uint32_t* d_flag = (uint32_t*)((char*)d_k + sizeof(bnp::Consts));

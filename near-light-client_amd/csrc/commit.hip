@@ -237,21 +237,15 @@ int32_t nlx_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, size_t n_leaves, 
     size_t words = merkle_digest_words(n_leaves, cap_height);
     Staged in(ctx, leaves, n_leaves * leaf_len * 8, true, false);
     if (in.status) return in.status;
-    uint64_t* d_dig = nullptr;
-    bool own_dig = false;
-    if (digests_out && is_device_ptr(digests_out)) {
-        d_dig = digests_out;
-    } else {
-        d_dig = (uint64_t*)ctx->alloc(words * 8);
-        if (!d_dig) return NLX_E_NOMEM;
-        own_dig = true;
-    }
+    Scratch scratch(ctx);
+    const bool own_dig = !(digests_out && is_device_ptr(digests_out));
+    uint64_t* d_dig = own_dig ? scratch.alloc_as<uint64_t>(words * 8) : digests_out;
+    if (!d_dig) return NLX_E_NOMEM;
     launch_hash_leaves_rowmajor(ctx->stream, in.as<uint64_t>(), (uint32_t)leaf_len, n_leaves, d_dig);
     const uint64_t* d_cap = launch_merkle_levels(ctx->stream, d_dig, n_leaves, cap_height);
     int32_t rc = copy_out(ctx, cap_out, d_cap, ((size_t)32) << cap_height);
     if (!rc && own_dig && digests_out) rc = copy_out(ctx, digests_out, d_dig, words * 8);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (own_dig) ctx->release(d_dig);
+    hipError_t e = scratch.drain();
     if (rc) return rc;
     if (e != hipSuccess) return ctx->hip_fail(e, "hipStreamSynchronize");
     return NLX_OK;
@@ -482,13 +476,13 @@ int32_t nlx_commit_eval_at(nlx_commit* c, const uint64_t zeta[2], uint64_t* out_
     Staged so(ctx, out_ext, (size_t)c->n_cols * 16, false, true);
     if (sz.status) return sz.status;
     if (so.status) return so.status;
-    uint64_t* scratch = (uint64_t*)ctx->alloc(eval_scratch_words(c->n_cols, c->log_n) * 8);
-    if (!scratch) return NLX_E_NOMEM;
-    launch_eval_br(ctx->stream, c->coeffs_br, c->n(), c->n_cols, c->log_n, sz.as<uint64_t>(), so.as<uint64_t>(), scratch);
-    ctx->release(scratch);
-    int32_t rc = so.finish();
-    if (rc) return rc;
-    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    Scratch scratch(ctx);
+    uint64_t* d_eval = scratch.alloc_as<uint64_t>(eval_scratch_words(c->n_cols, c->log_n) * 8);
+    if (!d_eval) return NLX_E_NOMEM;
+    launch_eval_br(ctx->stream, c->coeffs_br, c->n(), c->n_cols, c->log_n, sz.as<uint64_t>(), so.as<uint64_t>(), d_eval);
+    NLX_RC(so.finish());
+    const hipError_t e = scratch.drain();
+    if (e != hipSuccess) return ctx->hip_fail(e, "hipStreamSynchronize(ctx->stream)");
     return NLX_OK;
 } NLX_CATCH(nullptr)
 

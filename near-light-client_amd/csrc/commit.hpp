@@ -1,5 +1,6 @@
 // Device-resident polynomial batch commitment (plonky2::fri::oracle::PolynomialBatch).
 #pragma once
+#include <memory>
 #include "ctx.hpp"
 
 struct nlx_commit {
@@ -38,6 +39,18 @@ enum class CommitInput { ValuesNatural, CoeffsNatural, CoeffsBitrev };
 int32_t commit_build(nlx_ctx* ctx, const uint64_t* d_in, size_t in_stride, CommitInput kind, uint32_t n_cols,
                      uint32_t log_n, uint32_t rate_bits, uint32_t cap_height, nlx_commit** out, uint32_t leaf_group = 0,
                      uint32_t batch_cols = 0, uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS, uint32_t* d_bad = nullptr);
+// A commitment one call owns.  nlx_commit_destroy only hands the tables back to the allocator: an owner is declared BEFORE the
+// call's Scratch, so that the stream is drained first (destruction runs in reverse order).
+struct CommitDeleter { void operator()(nlx_commit* c) const { nlx_commit_destroy(c); } };
+using CommitPtr = std::unique_ptr<nlx_commit, CommitDeleter>;
+inline int32_t commit_build(nlx_ctx* ctx, const uint64_t* d_in, size_t in_stride, CommitInput kind, uint32_t n_cols, uint32_t log_n,
+                            uint32_t rate_bits, uint32_t cap_height, CommitPtr& out, uint32_t leaf_group = 0, uint32_t batch_cols = 0,
+                            uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS, uint32_t* d_bad = nullptr) {
+    nlx_commit* c = nullptr;
+    const int32_t rc = commit_build(ctx, d_in, in_stride, kind, n_cols, log_n, rate_bits, cap_height, &c, leaf_group, batch_cols, hasher, d_bad);
+    out.reset(c);
+    return rc;
+}
 // batch k of a commitment as a commitment of its own (non-owning): its columns of the shared tables, its tree, its cap
 nlx_commit commit_view(const nlx_commit* c, uint32_t k);
 

@@ -133,7 +133,7 @@ void nlx_ctx::end_kernel() {
 }
 
 namespace nlx {
-std::atomic<int> batch_spawn_fault_after{-1};   // fault injection for nlx_batch_prove (prover.hip), armed by nlx_abi_selftest
+std::atomic<int> batch_spawn_fault_after{-1};   // fault injection for the batch provers' job pool (prove_common.hpp), armed by nlx_abi_selftest
 
 bool is_device_ptr(const void* p) {
     if (!p) return false;
@@ -197,6 +197,13 @@ hipError_t Scratch::drain() {
     return e;
 }
 
+int32_t Scratch::finish(int32_t rc) {
+    const hipError_t e = drain(), le = hipGetLastError();
+    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
+    if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");
+    return rc;
+}
+
 }  // namespace nlx
 
 extern "C" {
@@ -216,7 +223,7 @@ int32_t nlx_abi_selftest(int32_t kind) NLX_TRY {
     }
     if (kind == 1) throw std::runtime_error("nlx_abi_selftest");
     if (kind == 2) throw 42;
-    if (kind >= 3 && kind <= 5) {   // fault injection for nlx_batch_prove's thread start-up: 3 = the second worker fails, 4 = the first, 5 = off
+    if (kind >= 3 && kind <= 5) {   // fault injection for the batch provers' thread start-up (prove_common.hpp): 3 = the second worker fails, 4 = the first, 5 = off
         nlx::batch_spawn_fault_after = kind == 3 ? 1 : kind == 4 ? 0 : -1;
         return NLX_OK;
     }

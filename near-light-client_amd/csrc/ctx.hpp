@@ -118,6 +118,12 @@ inline void on_exception(nlx_ctx* ctx, const char* what) noexcept {
         hipError_t e__ = (call);                             \
         if (e__ != hipSuccess) return (ctx)->hip_fail(e__, #call); \
     } while (0)
+// the same for a call that returns one of the library's own codes (the failing callee has set the error text)
+#define NLX_RC(call)                     \
+    do {                                 \
+        const int32_t rc__ = (call);     \
+        if (rc__) return rc__;           \
+    } while (0)
 
 namespace nlx {
 bool is_device_ptr(const void* p);
@@ -151,5 +157,8 @@ struct Scratch {
     void* alloc(size_t bytes);   // nullptr: out of device memory
     template <class T> T* alloc_as(size_t bytes) { return reinterpret_cast<T*>(alloc(bytes)); }
     hipError_t drain();          // synchronise the stream and give the blocks back now; the synchronise's status
+    // The tail every call shares: drain(), then hipGetLastError().  `rc` is what the call's body returned; the first failure wins,
+    // then the synchronise's, then a kernel launch's.
+    int32_t finish(int32_t rc);
 };
 }  // namespace nlx

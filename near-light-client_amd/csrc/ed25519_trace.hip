@@ -235,12 +235,13 @@ extern "C" int32_t nlx_ed25519_bind_round(nlx_ctx* ctx, const uint64_t* trace, u
     if (tr.status) return tr.status;
     Staged so(ctx, acc_out, 2 * n * 8, false, true);
     if (so.status) return so.status;
-    gl::Ext* d_fp = (gl::Ext*)ctx->alloc((size_t)n_slots * sizeof(gl::Ext));
+    std::vector<gl::Ext> fp_h(n_slots), start(n_slots);   // `start` becomes the source of a queued copy: it outlives the scratch
+    Scratch scratch(ctx);
+    gl::Ext* d_fp = scratch.alloc_as<gl::Ext>((size_t)n_slots * sizeof(gl::Ext));
     if (!d_fp) return NLX_E_NOMEM;
     const gl::Ext g{gamma[0] % gl::P, gamma[1] % gl::P};
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(k_ed_bind_slot, dim3((n_slots + 63) / 64), dim3(64), 0, st, tr.as<uint64_t>(), n_slots, g, d_fp);
-    std::vector<gl::Ext> fp_h(n_slots), start(n_slots);
     int32_t rc = fetch(ctx, fp_h.data(), d_fp, (size_t)n_slots * sizeof(gl::Ext));
     if (!rc) {
         // the slots' start values: acc_(s+1) = acc_s gamma^96 + fp_s (a few thousand extension multiplications, on the host)
@@ -260,12 +261,7 @@ extern "C" int32_t nlx_ed25519_bind_round(nlx_ctx* ctx, const uint64_t* trace, u
                            so.as<uint64_t>());
         rc = so.finish();
     }
-    hipError_t e = hipStreamSynchronize(st);
-    ctx->release(d_fp);
-    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-    hipError_t le = hipGetLastError();
-    if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");
-    return rc;
+    return scratch.finish(rc);
 } NLX_CATCH(ctx)
 
 
@@ -281,15 +277,16 @@ extern "C" int32_t nlx_ed25519_trace(nlx_ctx* ctx, const uint64_t* slots, uint32
     Staged st(ctx, trace_out, (size_t)ed::N_COLS0 * n * 8, false, true);
     if (st.status) return st.status;
     const size_t bytes = (size_t)n_slots * sizeof(ed::Slot) + (n + n_slots) * sizeof(ed::Point) + 16;
-    char* d = (char*)ctx->alloc(bytes);
+    uint32_t bad = 0xFFFFFFFFu;   // written by a queued copy: declared before the scratch that drains the stream
+    Scratch scratch(ctx);
+    char* d = scratch.alloc_as<char>(bytes);
     if (!d) return NLX_E_NOMEM;
     ed::Slot* d_slots = (ed::Slot*)d;
     ed::Point* d_in = (ed::Point*)(d + (size_t)n_slots * sizeof(ed::Slot));
     ed::Point* d_fin = d_in + n;
     uint32_t* d_bad = (uint32_t*)(d_fin + n_slots);
-    uint32_t bad = 0xFFFFFFFFu;
     hipError_t e0 = hipMemcpyAsync(d_bad, &bad, 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e0 != hipSuccess) { ctx->release(d); return ctx->hip_fail(e0, "hipMemcpyAsync"); }
+    if (e0 != hipSuccess) return ctx->hip_fail(e0, "hipMemcpyAsync");
     // four lanes per slot (k_ed_scan4); k_ed_scan, one lane per slot, is the same walk written sequentially (kept: the reference
     // the quad version is checked against in tests/native and the form the row emitter's recomputation mirrors)
     hipLaunchKernelGGL(k_ed_scan4, dim3((n_slots + SCAN4_SLOTS_PER_BLOCK - 1) / SCAN4_SLOTS_PER_BLOCK), dim3(64), 0, ctx->stream,
@@ -297,12 +294,7 @@ extern "C" int32_t nlx_ed25519_trace(nlx_ctx* ctx, const uint64_t* slots, uint32
     hipLaunchKernelGGL(k_ed_rows, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_slots, d_in, d_fin, n_slots,
                        st.as<uint64_t>(), d_bad);
     e0 = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->stream);
-    int32_t rc = st.finish();
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    ctx->release(d);
-    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-    hipError_t le = hipGetLastError();
-    if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");
+    int32_t rc = scratch.finish(st.finish());
     if (!rc && e0 != hipSuccess) rc = ctx->hip_fail(e0, "hipMemcpyAsync");
     if (!rc && bad != 0xFFFFFFFFu)
         rc = ctx->fail(NLX_E_INVAL, "slot %u: the statement is false (the signature does not verify, A / R is not on the curve, "

@@ -60,10 +60,5 @@ extern "C" int32_t nlx_fp25519_chip_trace(nlx_ctx* ctx, const uint64_t* a, const
     if (st.status) return st.status;
     hipLaunchKernelGGL(k_fp25519_chip_trace, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, sa.as<uint64_t>(),
                        sb.as<uint64_t>(), log_rows, st.as<uint64_t>());
-    int32_t rc = st.finish();
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-    hipError_t le = hipGetLastError();
-    if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");
-    return rc;
+    return Scratch(ctx).finish(st.finish());   // no device temporaries: only the shared tail
 } NLX_CATCH(ctx)

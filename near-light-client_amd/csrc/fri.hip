@@ -21,12 +21,7 @@ void coset_tables_host(unsigned log_n, unsigned bits, uint64_t* h) {
     }
 }
 
-#define FRI_CHECK(x) do { int32_t rc__ = (x); if (rc__) return rc__; } while (0)
-#define FRI_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return ctx->hip_fail(e__, #call); } while (0)
-#define FRI_ALLOC(p) do { if (!(p)) return NLX_E_NOMEM; } while (0)
-
-int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w, std::vector<void*>& scratch,
-                  const std::function<void(const char*)>& stage) {
+int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w, Scratch& scratch, StageClock& clock) {
     hipStream_t st = ctx->stream;
     const unsigned log_n = a.log_n, log_L = a.log_n + a.rate_bits, cap_h = a.cap_height;
     const size_t L = (size_t)1 << log_L, capw = (size_t)4 << cap_h;
@@ -35,19 +30,14 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
     uint32_t n_open = 0;
     for (uint32_t o = 0; o < NO; o++) n_open += oracles[o]->n_cols;
     std::vector<uint64_t> cap(capw);
-    auto dalloc = [&](size_t bytes) -> uint64_t* {
-        void* p = ctx->alloc(bytes);
-        if (p) scratch.push_back(p);
-        return (uint64_t*)p;
-    };
 
-    stage("fri_combine");
+    clock.stage("fri_combine");
     uint64_t fri_alpha[2];
     ch.ext_challenge(fri_alpha);
-    uint64_t* d_fri_alpha_pows = dalloc((size_t)n_open * 16);
-    uint64_t* d_fri_a = dalloc(L * 16);
-    uint64_t* d_fri_b = dalloc((L >> a.arity_bits) * 16 + 256);
-    FRI_ALLOC(d_fri_alpha_pows && d_fri_a && d_fri_b);
+    uint64_t* d_fri_alpha_pows = scratch.alloc_as<uint64_t>((size_t)n_open * 16);
+    uint64_t* d_fri_a = scratch.alloc_as<uint64_t>(L * 16);
+    uint64_t* d_fri_b = scratch.alloc_as<uint64_t>((L >> a.arity_bits) * 16 + 256);
+    if (!d_fri_alpha_pows || !d_fri_a || !d_fri_b) return NLX_E_NOMEM;
     launch_ext_pow_table(st, d_fri_alpha_pows, fri_alpha, n_open);
     {
         // reduced openings C0 = sum alpha^i open0_i (zeta batch), C1 = sum alpha^i open1_i (g zeta batch)
@@ -90,15 +80,15 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
         fp.log_n = log_n; fp.rate_bits = a.rate_bits;
         uint64_t* d_comb = nullptr;
         if (const size_t words = fri_combine_scratch_words(fp)) {
-            d_comb = dalloc(words * 8);
-            FRI_ALLOC(d_comb);
+            d_comb = scratch.alloc_as<uint64_t>(words * 8);
+            if (!d_comb) return NLX_E_NOMEM;
         }
         ctx->begin_kernel("fri_combine", 8.0 * L * n_open + 16.0 * L);
         launch_fri_combine(st, fp, d_comb);
         ctx->end_kernel();
     }
     // commit phase: layer values ping-pong between d_fri_a / d_fri_b; digests kept per layer
-    stage("fri_commit_phase");
+    clock.stage("fri_commit_phase");
     std::vector<uint64_t*> layer_values(NR + 1), layer_digests(NR);
     std::vector<unsigned> layer_log_n(NR + 1);
     layer_values[0] = d_fri_a;
@@ -107,8 +97,8 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
     for (uint32_t r = 0; r < NR; r++) {
         const unsigned ln = layer_log_n[r];
         const size_t n_leaves = (size_t)1 << (ln - a.arity_bits + a.rate_bits);
-        uint64_t* dg = dalloc(merkle_digest_words(n_leaves, cap_h) * 8);
-        FRI_ALLOC(dg);
+        uint64_t* dg = scratch.alloc_as<uint64_t>(merkle_digest_words(n_leaves, cap_h) * 8);
+        if (!dg) return NLX_E_NOMEM;
         layer_digests[r] = dg;
         const uint64_t* d_cap;
         if (a.hasher == NLX_HASHER_POSEIDON_BN128) {
@@ -124,13 +114,13 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
             else launch_fri_leaves(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg);
             d_cap = launch_merkle_levels(st, dg, n_leaves, cap_h);
         }
-        FRI_CHECK(fetch(ctx, cap.data(), d_cap, capw * 8));
+        NLX_RC(fetch(ctx, cap.data(), d_cap, capw * 8));
         w.u64s(cap.data(), capw);
         if (observe_hash(a.hasher, ch, cap.data(), capw / 4)) return ctx->fail(NLX_E_RANGE, "FRI: a commit-phase cap digest is not canonical");
         uint64_t beta[2];
         ch.ext_challenge(beta);
-        uint64_t* nxt = (r == 0) ? d_fri_b : dalloc(((size_t)16 << (ln - a.arity_bits + a.rate_bits)) + 256);
-        FRI_ALLOC(nxt);
+        uint64_t* nxt = (r == 0) ? d_fri_b : scratch.alloc_as<uint64_t>(((size_t)16 << (ln - a.arity_bits + a.rate_bits)) + 256);
+        if (!nxt) return NLX_E_NOMEM;
         launch_fri_fold(st, layer_values[r], nxt, ln, a.rate_bits, a.arity_bits, beta, gl::inv(shift),
                         ctx->tables.inv[ln + a.rate_bits], a.d_wA_inv);
         layer_values[r + 1] = nxt;
@@ -139,15 +129,15 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
     }
     // final polynomial
     const uint32_t final_len = 1u << layer_log_n[NR];
-    uint64_t* d_final = dalloc((size_t)final_len * 16 + 256);
-    FRI_ALLOC(d_final);
+    uint64_t* d_final = scratch.alloc_as<uint64_t>((size_t)final_len * 16 + 256);
+    if (!d_final) return NLX_E_NOMEM;
     launch_fri_final_coeffs(st, layer_values[NR], layer_log_n[NR], a.rate_bits, shift, d_final, final_len);
     std::vector<uint64_t> final_poly((size_t)final_len * 2);
-    FRI_CHECK(fetch(ctx, final_poly.data(), d_final, final_poly.size() * 8));
+    NLX_RC(fetch(ctx, final_poly.data(), d_final, final_poly.size() * 8));
     ch.observe(final_poly.data(), final_poly.size());
 
     // proof of work
-    stage("fri_pow");
+    clock.stage("fri_pow");
     uint64_t pow_witness = 0;
     {
         PowParams pp{};
@@ -156,16 +146,16 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
         pp.pos = ch.n_in;
         pp.bits = a.pow_bits;
         pp.max_rounds = (uint64_t)1 << 24;
-        unsigned long long* d_best = (unsigned long long*)dalloc(256);
-        FRI_ALLOC(d_best);
+        unsigned long long* d_best = scratch.alloc_as<unsigned long long>(256);
+        if (!d_best) return NLX_E_NOMEM;
         launch_pow_grind(st, pp, d_best);
-        FRI_CHECK(fetch(ctx, &pow_witness, d_best, 8));
+        NLX_RC(fetch(ctx, &pow_witness, d_best, 8));
         if (pow_witness == ~0ull) return ctx->fail(NLX_E_RANGE, "proof of work: no witness found");
         ch.observe(pow_witness);
         (void)ch.challenge();
     }
     // query phase
-    stage("fri_queries");
+    clock.stage("fri_queries");
     const uint32_t NQ = a.n_queries;
     std::vector<uint64_t> qidx(NQ);
     for (uint32_t q = 0; q < NQ; q++) qidx[q] = ch.challenge() % L;
@@ -186,10 +176,10 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
             ev_off[r] = off; off += (size_t)NQ * 2 * arity;
             fp_off[r] = off; off += (size_t)NQ * fplen[r] * 4;
         }
-        uint64_t* d_ans = dalloc(off * 8 + 256);
-        uint64_t* d_idx = dalloc((size_t)(NR + 1) * NQ * 8 + 256);
-        FRI_ALLOC(d_ans && d_idx);
-        FRI_HIP(hipMemcpyAsync(d_idx, qidx.data(), (size_t)NQ * 8, hipMemcpyHostToDevice, st));
+        uint64_t* d_ans = scratch.alloc_as<uint64_t>(off * 8 + 256);
+        uint64_t* d_idx = scratch.alloc_as<uint64_t>((size_t)(NR + 1) * NQ * 8 + 256);
+        if (!d_ans || !d_idx) return NLX_E_NOMEM;
+        NLX_HIP(ctx, hipMemcpyAsync(d_idx, qidx.data(), (size_t)NQ * 8, hipMemcpyHostToDevice, st));
         for (uint32_t o = 0; o < NO; o++) {
             launch_gather_rows(st, oracles[o]->lde, L, oracles[o]->n_cols, log_n, a.rate_bits, d_idx, NQ, d_ans + rows_off[o]);
             launch_gather_paths(st, oracles[o]->digests, log_L, cap_h, d_idx, NQ, d_ans + paths_off[o]);
@@ -205,7 +195,7 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
             launch_gather_paths(st, layer_digests[r], lg, cap_h, idx_r, NQ, d_ans + fp_off[r]);
         }
         std::vector<uint64_t> ans(off);
-        FRI_CHECK(fetch(ctx, ans.data(), d_ans, off * 8));
+        NLX_RC(fetch(ctx, ans.data(), d_ans, off * 8));
         for (uint32_t q = 0; q < NQ; q++) {
             for (uint32_t o = 0; o < NO; o++) {
                 const uint32_t ncol = oracles[o]->n_cols;

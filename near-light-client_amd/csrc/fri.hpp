@@ -5,9 +5,8 @@
 //   batch 1: the first nz[o] columns of every oracle o (in oracle order), opened at g * zeta
 // (+ an optional trailing column group of one oracle that closes both batches: FriProveArgs::tail_cols)
 #pragma once
-#include <functional>
-#include <vector>
 #include "commit.hpp"
+#include "prove_common.hpp"
 #include "transcript.hpp"
 
 namespace nlx {
@@ -33,10 +32,9 @@ struct FriProveArgs {
 };
 
 // Draws fri_alpha, runs combine / commit phase / proof of work / queries and appends the FriProof
-// (commit_phase_merkle_caps, query_round_proofs, final_poly, pow_witness) to `w`.  Device buffers are
-// pushed onto `scratch` (the caller releases them after synchronising); `stage` marks timing stages.
-int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w, std::vector<void*>& scratch,
-                  const std::function<void(const char*)>& stage);
+// (commit_phase_merkle_caps, query_round_proofs, final_poly, pow_witness) to `w`.  Device buffers come
+// from the caller's `scratch` (work on them may still be queued on return); `clock` marks timing stages.
+int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w, Scratch& scratch, StageClock& clock);
 
 // Small device tables used above (and by the quotient kernels): fills `h` with
 // coset_base[R] | zh_inv[R] | w_R_inv_pows[R] | chunk_scale[R] for the 2^bits cosets of the size-n subgroup

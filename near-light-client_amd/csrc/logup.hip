@@ -229,7 +229,9 @@ extern "C" int32_t nlx_logup_multiplicities(nlx_ctx* ctx, uint64_t* trace, uint3
     const size_t n = (size_t)1 << log_n;
     Staged tr(ctx, trace, (size_t)n_cols * n * 8, true, true);
     if (tr.status) return tr.status;
-    uint32_t* d_cols = (uint32_t*)ctx->alloc((size_t)n_lookups * 4 + 16);
+    uint32_t err = 0;   // written by a queued copy: declared before the scratch that drains the stream
+    Scratch scratch(ctx);
+    uint32_t* d_cols = scratch.alloc_as<uint32_t>((size_t)n_lookups * 4 + 16);
     if (!d_cols) return NLX_E_NOMEM;
     uint32_t* d_err = d_cols + n_lookups;
     hipStream_t st = ctx->stream;
@@ -237,7 +239,6 @@ extern "C" int32_t nlx_logup_multiplicities(nlx_ctx* ctx, uint64_t* trace, uint3
     hipError_t e = hipMemcpyAsync(d_cols, cols, (size_t)n_lookups * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(mult, 0, n * 8 * table_cols, st);
-    uint32_t err = 0;
     if (e == hipSuccess) {
         const size_t total = (size_t)n_lookups << log_n;
         const unsigned blocks = (unsigned)(total < ((size_t)512 << 12) ? (total + 4095) / 4096 : 512);  // >= 4096 cells per block
@@ -246,8 +247,7 @@ extern "C" int32_t nlx_logup_multiplicities(nlx_ctx* ctx, uint64_t* trace, uint3
         e = hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st);
     }
     if (e == hipSuccess) rc = tr.finish();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    ctx->release(d_cols);
+    if (e == hipSuccess) e = scratch.drain();
     if (e != hipSuccess) return ctx->hip_fail(e, "nlx_logup_multiplicities");
     if (!rc && err) rc = ctx->fail(NLX_E_RANGE, "a looked-up cell is outside the table [0, 2^%u)", table_bits);
     return rc;
@@ -271,7 +271,8 @@ extern "C" int32_t nlx_logup_round(nlx_ctx* ctx, const uint64_t* trace, uint32_t
     Staged so(ctx, out, (size_t)n_out * n * 8, false, true);
     if (so.status) return so.status;
     const size_t scan_words = add_scan_scratch_words(n, 2);
-    uint64_t* d_scratch = (uint64_t*)ctx->alloc(scan_words * 8 + (size_t)n_lookups * 4);
+    Scratch scratch(ctx);
+    uint64_t* d_scratch = scratch.alloc_as<uint64_t>(scan_words * 8 + (size_t)n_lookups * 4);
     if (!d_scratch) return NLX_E_NOMEM;
     uint32_t* d_cols = (uint32_t*)(d_scratch + scan_words);
     hipStream_t st = ctx->stream;
@@ -287,9 +288,8 @@ extern "C" int32_t nlx_logup_round(nlx_ctx* ctx, const uint64_t* trace, uint32_t
         hipLaunchKernelGGL(k_logup_rowsum, dim3(blocks), dim3(256), 0, st, p);
         launch_add_scan(st, p.out + (size_t)(2 * H + 2 * table_cols) * n, n, n, 2, d_scratch);
         rc = so.finish();
-        e = hipStreamSynchronize(st);
+        e = scratch.drain();
     }
-    ctx->release(d_scratch);
     if (e != hipSuccess) return ctx->hip_fail(e, "nlx_logup_round");
     hipError_t le = hipGetLastError();
     if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");

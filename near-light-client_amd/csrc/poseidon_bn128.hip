@@ -337,7 +337,8 @@ int32_t nlx_poseidon_bn128_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, si
     if (in.status) return in.status;
     Staged dig(ctx, digests_out ? (void*)digests_out : nullptr, words * 8, false, digests_out != nullptr);
     if (dig.status) return dig.status;
-    uint64_t* d_dig = digests_out ? dig.as<uint64_t>() : (uint64_t*)ctx->alloc(words * 8);
+    Scratch scratch(ctx);
+    uint64_t* d_dig = digests_out ? dig.as<uint64_t>() : scratch.alloc_as<uint64_t>(words * 8);
     if (!d_dig) return NLX_E_NOMEM;
     RangeFlag bad(ctx);
     int32_t rc = bad.d ? NLX_OK : NLX_E_NOMEM;
@@ -355,10 +356,9 @@ int32_t nlx_poseidon_bn128_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, si
             if (e != hipSuccess) rc = ctx->hip_fail(e, "hipMemcpyAsync(cap)");
         }
         if (!rc && digests_out) rc = dig.finish();
-        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        const hipError_t e = scratch.drain();
         if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
     }
-    if (!digests_out) ctx->release(d_dig);
     return rc;
 } NLX_CATCH(ctx)
 

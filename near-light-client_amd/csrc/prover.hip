@@ -11,11 +11,8 @@
 // Merkle caps (512 B), openings (~4.5 KB), the final polynomial and the query answers cross
 // PCIe.  It is not a fallback for any device stage.
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
-#include <thread>
 #include <vector>
 #include "commit.hpp"
 #include "gl.hpp"
@@ -98,7 +95,7 @@ struct nlx_circuit {
     std::vector<nlx_gate_desc> gates;
     std::vector<uint64_t> k_is;
     uint32_t n_consts_all = 0, n_cs = 0, n_zs = 0, n_q = 0, n_fri_rounds = 0, n_terms = 0, max_gate_constraints = 0;
-    nlx_commit* cs = nullptr;           // constants + sigmas commitment
+    CommitPtr cs;                       // constants + sigmas commitment
     uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS;   // the config's Hasher: every Merkle tree of the proof, and how digests enter the transcript
     uint32_t* d_bad = nullptr;          // BN128: the leaf kernels' range word (never set: oracles of <= 4 columns are refused at build)
     std::vector<uint64_t> cs_cap;       // host copy
@@ -127,18 +124,14 @@ struct nlx_circuit {
     int32_t* d_idx_of = nullptr;      // [tables][65536]
     uint32_t* d_mult = nullptr;       // multiplicity counters of all tables, then the error word
     size_t mult_words = 0;
-    // stage timing
-    hipEvent_t ev[NLX_MAX_STAGES + 1]{};
-    const char* stage_names[NLX_MAX_STAGES]{};
-    uint32_t n_stages = 0;
-    bool timed = false;
+    StageClock clock;
     size_t n() const { return (size_t)1 << d.degree_bits; }
     size_t L() const { return (size_t)1 << (d.degree_bits + d.rate_bits); }
 };
 
 namespace {
 // every commitment of a circuit's proofs carries the circuit's hasher
-int32_t commit_for(nlx_circuit* c, const uint64_t* d_in, CommitInput kind, uint32_t n_cols, nlx_commit** out) {
+int32_t commit_for(nlx_circuit* c, const uint64_t* d_in, CommitInput kind, uint32_t n_cols, CommitPtr& out) {
     return commit_build(c->ctx, d_in, c->n(), kind, n_cols, c->d.degree_bits, c->d.rate_bits, c->d.cap_height, out, 0, 0, c->hasher, c->d_bad);
 }
 
@@ -286,7 +279,7 @@ int32_t circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t
         hipError_t e1 = hipMemcpyAsync(d_vals, constants, cb, is_device_ptr(constants) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
         hipError_t e2 = hipMemcpyAsync((uint8_t*)d_vals + cb, sigmas, sb, is_device_ptr(sigmas) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
         if (e1 != hipSuccess || e2 != hipSuccess) { ctx->release(d_vals); return fail(ctx->hip_fail(e1 != hipSuccess ? e1 : e2, "hipMemcpyAsync")); }
-        rc = commit_for(c, d_vals, CommitInput::ValuesNatural, c->n_cs, &c->cs);
+        rc = commit_for(c, d_vals, CommitInput::ValuesNatural, c->n_cs, c->cs);
         if (rc) { ctx->release(d_vals); return fail(rc); }
         c->d_sigma_values = (uint64_t*)ctx->alloc(sb);
         if (!c->d_sigma_values) { ctx->release(d_vals); return fail(NLX_E_NOMEM); }
@@ -447,8 +440,8 @@ int32_t circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t
         parts.push_back(d.degree_bits);
         hash_no_pad_host(parts.data(), parts.size(), c->d.circuit_digest);
     }
-    for (int i = 0; i <= NLX_MAX_STAGES; i++)
-        if (hipEventCreate(&c->ev[i]) != hipSuccess) return fail(ctx->fail(NLX_E_HIP, "hipEventCreate failed"));
+    rc = c->clock.create(ctx);
+    if (rc) return fail(rc);
     *out = c;
     return NLX_OK;
 }
@@ -476,7 +469,6 @@ void nlx_circuit_destroy(nlx_circuit* c) NLX_TRY {
     nlx_ctx* ctx = c->ctx;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (c->cs) nlx_commit_destroy(c->cs);
     ctx->release(c->d_sigma_values);
     ctx->release(c->d_gates);
     ctx->release(c->d_work);
@@ -487,9 +479,7 @@ void nlx_circuit_destroy(nlx_circuit* c) NLX_TRY {
     ctx->release(c->d_mult);
     ctx->release(c->d_tabs);
     ctx->release(c->d_bad);
-    for (int i = 0; i <= NLX_MAX_STAGES; i++)
-        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    delete c;
+    delete c;   // and with it the constants + sigmas commitment and the stage clock's events
 } NLX_CATCH_VOID(nullptr)
 
 int32_t nlx_circuit_digest(const nlx_circuit* c, uint64_t out[4]) NLX_TRY {
@@ -524,7 +514,8 @@ int32_t nlx_pow_grind(nlx_ctx* ctx, const uint64_t state[12], uint32_t pos, uint
     if (!state || !nonce_out) return ctx->fail(NLX_E_INVAL, "NULL argument");
     if (pos >= 8 || bits > 40) return ctx->fail(NLX_E_RANGE, "pos must be < 8 and bits <= 40");
     (void)hipSetDevice(ctx->device);
-    unsigned long long* d_best = (unsigned long long*)ctx->alloc(256);
+    Scratch scratch(ctx);
+    unsigned long long* d_best = scratch.alloc_as<unsigned long long>(256);
     if (!d_best) return NLX_E_NOMEM;
     PowParams pp{};
     for (int i = 0; i < 12; i++) pp.state[i] = state[i];
@@ -533,27 +524,14 @@ int32_t nlx_pow_grind(nlx_ctx* ctx, const uint64_t state[12], uint32_t pos, uint
     pp.max_rounds = (uint64_t)1 << 24;
     launch_pow_grind(ctx->stream, pp, d_best);
     uint64_t best = 0;
-    int32_t rc = fetch(ctx, &best, d_best, 8);
-    ctx->release(d_best);
-    if (rc) return rc;
+    NLX_RC(fetch(ctx, &best, d_best, 8, &scratch));
     if (best == ~0ull) return ctx->fail(NLX_E_RANGE, "proof of work: no witness found");
     *nonce_out = best;
     return NLX_OK;
 } NLX_CATCH(ctx)
 
 int32_t nlx_prove_stage_times(const nlx_circuit* c, uint32_t* n_stages, const char** names_out, float* ms_out) NLX_TRY {
-    if (!c || !n_stages) return NLX_E_INVAL;
-    if (!c->timed) { *n_stages = 0; return NLX_OK; }
-    *n_stages = c->n_stages;
-    for (uint32_t i = 0; i < c->n_stages; i++) {
-        if (names_out) names_out[i] = c->stage_names[i];
-        if (ms_out) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]) != hipSuccess) ms = -1.f;
-            ms_out[i] = ms;
-        }
-    }
-    return NLX_OK;
+    return c ? c->clock.times(n_stages, names_out, ms_out) : NLX_E_INVAL;
 } NLX_CATCH(nullptr)
 
 }  // extern "C"
@@ -561,47 +539,33 @@ int32_t nlx_prove_stage_times(const nlx_circuit* c, uint32_t* n_stages, const ch
 namespace {
 
 // a8: Z and partial-product polynomials from the wires' subgroup values (device), committed.
-// Temporaries are handed to `defer` (released by the caller after it has synchronised) or, without one,
-// released here after a stream synchronisation.
+// Everything is only enqueued; the temporaries come from the caller's `scratch` and go back when the caller drains it.
 // With lookup tables the same commitment carries, after them, every challenge round's RE and partial-sum polynomials
 // (compute_all_lookup_polys); d_deltas = the rounds' (A, B, alpha, delta) on the device.
 int32_t zs_stage(nlx_circuit* c, const uint64_t* d_wire_values, const uint64_t betas[2], const uint64_t gammas[2],
-                 const uint64_t* d_deltas, nlx_commit** cz, std::vector<void*>* defer) {
+                 const uint64_t* d_deltas, CommitPtr& cz, Scratch& scratch) {
     nlx_ctx* ctx = c->ctx;
     const nlx_circuit_desc& d = c->d;
     const unsigned log_n = d.degree_bits;
     const size_t n = c->n();
-    uint64_t* d_zs = (uint64_t*)ctx->alloc((size_t)c->n_zs * n * 8);
-    uint64_t* d_zs_scratch = (uint64_t*)ctx->alloc(zs_scratch_words(log_n, d.num_challenges) * 8);
-    int32_t rc = NLX_OK;
-    if (!d_zs || !d_zs_scratch) rc = NLX_E_NOMEM;
-    if (!rc) {
-        ZsParams zp{};
-        zp.wires = d_wire_values;
-        zp.wires_stride = n;
-        zp.sigmas = c->d_sigma_values;
-        zp.k_is = c->d_k_is;
-        zp.w_n_table = ctx->tables.fwd[log_n];
-        for (int i = 0; i < 2; i++) { zp.betas[i] = betas[i]; zp.gammas[i] = gammas[i]; }
-        zp.out = d_zs;
-        zp.log_n = log_n; zp.routed = d.num_routed_wires; zp.chunk = d.quotient_degree_factor; zp.nc = d.num_challenges;
-        zp.npp = d.num_partial_products;
-        launch_zs(ctx->stream, zp, d_zs_scratch);
-        if (c->n_lk_polys)
-            launch_lookup_polys(ctx->stream, c->lk, c->d_tabs, c->h_tabs.data(), d_wire_values, n, d.num_challenges, d_deltas,
-                                d_zs + (size_t)c->n_zpp * n);
-        rc = commit_for(c, d_zs, CommitInput::ValuesNatural, c->n_zs, cz);
-    }
-    // commit_build only enqueues: the inputs must outlive the stream work
-    if (defer) {
-        if (d_zs) defer->push_back(d_zs);
-        if (d_zs_scratch) defer->push_back(d_zs_scratch);
-    } else {
-        (void)hipStreamSynchronize(ctx->stream);
-        ctx->release(d_zs);
-        ctx->release(d_zs_scratch);
-    }
-    return rc;
+    uint64_t* d_zs = scratch.alloc_as<uint64_t>((size_t)c->n_zs * n * 8);
+    uint64_t* d_zs_scratch = scratch.alloc_as<uint64_t>(zs_scratch_words(log_n, d.num_challenges) * 8);
+    if (!d_zs || !d_zs_scratch) return NLX_E_NOMEM;
+    ZsParams zp{};
+    zp.wires = d_wire_values;
+    zp.wires_stride = n;
+    zp.sigmas = c->d_sigma_values;
+    zp.k_is = c->d_k_is;
+    zp.w_n_table = ctx->tables.fwd[log_n];
+    for (int i = 0; i < 2; i++) { zp.betas[i] = betas[i]; zp.gammas[i] = gammas[i]; }
+    zp.out = d_zs;
+    zp.log_n = log_n; zp.routed = d.num_routed_wires; zp.chunk = d.quotient_degree_factor; zp.nc = d.num_challenges;
+    zp.npp = d.num_partial_products;
+    launch_zs(ctx->stream, zp, d_zs_scratch);
+    if (c->n_lk_polys)
+        launch_lookup_polys(ctx->stream, c->lk, c->d_tabs, c->h_tabs.data(), d_wire_values, n, d.num_challenges, d_deltas,
+                            d_zs + (size_t)c->n_zpp * n);
+    return commit_for(c, d_zs, CommitInput::ValuesNatural, c->n_zs, cz);
 }
 
 // The quotient degree check (BN128 circuits; the Goldilocks entries keep returning a proof, as they always have).
@@ -643,8 +607,7 @@ int32_t quotient_degree_check(nlx_circuit* c, const uint64_t* d_qchunks) {
 // a9: quotient polynomials (compute_quotient_polys) from the three LDE tables, committed from coefficients.
 int32_t quotient_stage(nlx_circuit* c, const nlx_commit* cw, const nlx_commit* cz, const uint64_t betas[2],
                        const uint64_t gammas[2], const uint64_t alphas[2], const uint64_t pih[4],
-                       const uint64_t* d_deltas, const uint64_t* d_lut_polys, nlx_commit** cq,
-                       const std::function<void(const char*)>& stage, std::vector<void*>* defer) {
+                       const uint64_t* d_deltas, const uint64_t* d_lut_polys, CommitPtr& cq, StageClock& clock, Scratch& scratch) {
     nlx_ctx* ctx = c->ctx;
     const nlx_circuit_desc& d = c->d;
     hipStream_t st = ctx->stream;
@@ -653,71 +616,235 @@ int32_t quotient_stage(nlx_circuit* c, const nlx_commit* cw, const nlx_commit* c
     const uint32_t nc = d.num_challenges, npp = d.num_partial_products;
     // one alpha power per vanishing term (GateAcc reads ap[T0 + k]): Z(1) terms, permutation terms, lookup terms, gate constraints
     c->n_terms = nc + nc * (npp + 1) + nc * c->n_lk_terms + c->max_gate_constraints;
-    uint64_t* d_alpha_pows = (uint64_t*)ctx->alloc((size_t)2 * c->n_terms * 8);
-    uint64_t* d_qvals = (uint64_t*)ctx->alloc((size_t)nc * L * 8);
-    uint64_t* d_qchunks = (uint64_t*)ctx->alloc((size_t)nc * L * 8);
-    int32_t rc = NLX_OK;
-    if (!d_alpha_pows || !d_qvals || !d_qchunks) rc = NLX_E_NOMEM;
-    if (!rc) {
-        launch_pow_table(st, d_alpha_pows, alphas[0], alphas[1], c->n_terms, c->n_terms);
-        QuotientParams qp{};
-        qp.cs = c->cs->lde; qp.wires = cw->lde; qp.zs = cz->lde;
-        qp.gates = c->d_gates; qp.k_is = c->d_k_is; qp.coset_base = c->d_coset_base;
-        qp.w_n_table = ctx->tables.fwd[log_n];
-        qp.zh_inv = c->d_zh_inv; qp.l0_scaled = c->d_l0_scaled; qp.alpha_pows = d_alpha_pows;
-        qp.out = d_qvals;
-        for (int i = 0; i < 2; i++) { qp.betas[i] = betas[i]; qp.gammas[i] = gammas[i]; }
-        for (int i = 0; i < 4; i++) qp.pih[i] = pih[i];
-        qp.alpha_stride = c->n_terms;
-        qp.num_wires = d.num_wires; qp.work = c->d_work; qp.work_stride = c->work_stride;
-        qp.log_n = log_n; qp.rate_bits = d.rate_bits; qp.n_gates = d.num_gates; qp.n_selectors = d.num_selectors;
-        qp.n_consts_all = c->n_consts_all; qp.routed = d.num_routed_wires; qp.chunk = d.quotient_degree_factor; qp.nc = nc; qp.npp = npp;
-        qp.gate_const0 = d.num_selectors + c->n_lk_sel;
-        qp.n_lk_terms = c->n_lk_terms;
-        if (c->n_lk_terms) {
-            // check_lookup_constraints_batch: the lookup terms' share of both alpha sums goes into d_qvals first, k_quotient adds it
-            LookupTermsParams lp{};
-            lp.cs = c->cs->lde; lp.wires = cw->lde; lp.zs = cz->lde;
-            lp.deltas = d_deltas; lp.lut_polys = d_lut_polys; lp.alpha_pows = d_alpha_pows; lp.out = d_qvals;
-            lp.alpha_stride = c->n_terms; lp.t_lk = nc + nc * (npp + 1);
-            lp.log_n = log_n; lp.rate_bits = d.rate_bits; lp.nc = nc; lp.sel0 = d.num_selectors; lp.lk0 = c->n_zpp;
-            lp.n_lk_terms = c->n_lk_terms; lp.s = c->lk;
-            ctx->begin_kernel("lookup_terms", 8.0 * L * (c->n_lk_sel + d.num_routed_wires + 2.0 * c->n_lk_polys + nc));
-            launch_lookup_terms(st, lp);
-            ctx->end_kernel();
-            qp.accumulate = 1;
-        }
-        ctx->begin_kernel("quotient", 8.0 * L * (c->n_cs + d.num_wires + c->n_zs + nc) + 8.0 * L * nc);
-        for (uint32_t g : c->poseidon_gates) {   // their part 2 ahead of the main kernel, which adds the rest
-            launch_quotient_poseidon(st, qp, g, qp.accumulate != 0);
-            qp.accumulate = 1;
-        }
-        launch_quotient(st, qp);
+    uint64_t* d_alpha_pows = scratch.alloc_as<uint64_t>((size_t)2 * c->n_terms * 8);
+    uint64_t* d_qvals = scratch.alloc_as<uint64_t>((size_t)nc * L * 8);
+    uint64_t* d_qchunks = scratch.alloc_as<uint64_t>((size_t)nc * L * 8);
+    if (!d_alpha_pows || !d_qvals || !d_qchunks) return NLX_E_NOMEM;
+    launch_pow_table(st, d_alpha_pows, alphas[0], alphas[1], c->n_terms, c->n_terms);
+    QuotientParams qp{};
+    qp.cs = c->cs->lde; qp.wires = cw->lde; qp.zs = cz->lde;
+    qp.gates = c->d_gates; qp.k_is = c->d_k_is; qp.coset_base = c->d_coset_base;
+    qp.w_n_table = ctx->tables.fwd[log_n];
+    qp.zh_inv = c->d_zh_inv; qp.l0_scaled = c->d_l0_scaled; qp.alpha_pows = d_alpha_pows;
+    qp.out = d_qvals;
+    for (int i = 0; i < 2; i++) { qp.betas[i] = betas[i]; qp.gammas[i] = gammas[i]; }
+    for (int i = 0; i < 4; i++) qp.pih[i] = pih[i];
+    qp.alpha_stride = c->n_terms;
+    qp.num_wires = d.num_wires; qp.work = c->d_work; qp.work_stride = c->work_stride;
+    qp.log_n = log_n; qp.rate_bits = d.rate_bits; qp.n_gates = d.num_gates; qp.n_selectors = d.num_selectors;
+    qp.n_consts_all = c->n_consts_all; qp.routed = d.num_routed_wires; qp.chunk = d.quotient_degree_factor; qp.nc = nc; qp.npp = npp;
+    qp.gate_const0 = d.num_selectors + c->n_lk_sel;
+    qp.n_lk_terms = c->n_lk_terms;
+    if (c->n_lk_terms) {
+        // check_lookup_constraints_batch: the lookup terms' share of both alpha sums goes into d_qvals first, k_quotient adds it
+        LookupTermsParams lp{};
+        lp.cs = c->cs->lde; lp.wires = cw->lde; lp.zs = cz->lde;
+        lp.deltas = d_deltas; lp.lut_polys = d_lut_polys; lp.alpha_pows = d_alpha_pows; lp.out = d_qvals;
+        lp.alpha_stride = c->n_terms; lp.t_lk = nc + nc * (npp + 1);
+        lp.log_n = log_n; lp.rate_bits = d.rate_bits; lp.nc = nc; lp.sel0 = d.num_selectors; lp.lk0 = c->n_zpp;
+        lp.n_lk_terms = c->n_lk_terms; lp.s = c->lk;
+        ctx->begin_kernel("lookup_terms", 8.0 * L * (c->n_lk_sel + d.num_routed_wires + 2.0 * c->n_lk_polys + nc));
+        launch_lookup_terms(st, lp);
         ctx->end_kernel();
-        stage("quotient_intt");
-        launch_intt_dif_cosets(st, ctx->tables, d_qvals, nc, log_n, d.rate_bits, c->d_inv_scale_br);
-        launch_quotient_chunks(st, d_qvals, d_qchunks, log_n, d.rate_bits, nc, c->d_wR_inv, c->d_chunk_scale);
-        stage("commit_quotient");
-        rc = commit_for(c, d_qchunks, CommitInput::CoeffsBitrev, c->n_q, cq);
-        if (!rc && c->hasher == NLX_HASHER_POSEIDON_BN128) {
-            rc = quotient_degree_check(c, d_qchunks);
-            if (rc) {   // no commitment leaves a refused stage (its kernels are drained first)
-                (void)hipStreamSynchronize(st);
-                nlx_commit_destroy(*cq);
-                *cq = nullptr;
+        qp.accumulate = 1;
+    }
+    ctx->begin_kernel("quotient", 8.0 * L * (c->n_cs + d.num_wires + c->n_zs + nc) + 8.0 * L * nc);
+    for (uint32_t g : c->poseidon_gates) {   // their part 2 ahead of the main kernel, which adds the rest
+        launch_quotient_poseidon(st, qp, g, qp.accumulate != 0);
+        qp.accumulate = 1;
+    }
+    launch_quotient(st, qp);
+    ctx->end_kernel();
+    clock.stage("quotient_intt");
+    launch_intt_dif_cosets(st, ctx->tables, d_qvals, nc, log_n, d.rate_bits, c->d_inv_scale_br);
+    launch_quotient_chunks(st, d_qvals, d_qchunks, log_n, d.rate_bits, nc, c->d_wR_inv, c->d_chunk_scale);
+    clock.stage("commit_quotient");
+    NLX_RC(commit_for(c, d_qchunks, CommitInput::CoeffsBitrev, c->n_q, cq));
+    // a refused stage hands no commitment out: its owner gives it back, after the caller's scratch has drained the stream
+    return c->hasher == NLX_HASHER_POSEIDON_BN128 ? quotient_degree_check(c, d_qchunks) : NLX_OK;
+}
+
+// What one nlx_prove call holds until its stream work has drained.  Members go in reverse order: the scratch first - which
+// synchronises -, then the host sources of the asynchronous copies, then the commitments.
+struct ProveCall {
+    CommitPtr cw, cz, cq;
+    uint64_t deltas[8] = {}, lut_polys[2 * 16] = {};
+    OpeningPoints points;
+    Scratch scratch;
+    explicit ProveCall(nlx_ctx* ctx) : scratch(ctx) {}
+};
+
+int32_t prove_stages(nlx_circuit* c, ProveCall& pc, const uint64_t* wires, const uint64_t* public_inputs, Writer& w, size_t* proof_len) {
+    nlx_ctx* ctx = c->ctx;
+    const nlx_circuit_desc& d = c->d;
+    hipStream_t st = ctx->stream;
+    const size_t n = c->n();
+    const unsigned log_n = d.degree_bits, cap_h = d.cap_height;
+    const uint32_t nc = d.num_challenges, npp = d.num_partial_products;
+    const uint32_t NR = c->n_fri_rounds;
+    const size_t capw = (size_t)4 << cap_h;
+    Scratch& scratch = pc.scratch;
+    CommitPtr &cw = pc.cw, &cz = pc.cz, &cq = pc.cq;
+    Challenger ch;
+    std::vector<uint64_t> cap(capw);
+    uint64_t pih[4];
+    std::vector<uint64_t> h_pis(public_inputs, public_inputs + d.num_public_inputs);
+    hash_no_pad_host(h_pis.data(), h_pis.size(), pih);
+
+    c->clock.begin(st);
+    c->clock.stage("commit_wires");
+    // ---- 2. wires commitment ----
+    Staged sw(ctx, wires, (size_t)d.num_wires * n * 8, true, false);
+    NLX_RC(sw.status);
+    // prover::set_lookup_wires, the first thing prove_with_partition_witness does to the witness it is handed: multiplicity
+    // wires and padding slots, on the device copy (a device witness is written in place, as upstream's PartitionWitness is)
+    if (d.num_luts)
+        launch_set_lookup_wires(st, c->lk, c->d_tabs, c->h_tabs.data(), sw.as<uint64_t>(), n, c->d_mult, c->mult_words,
+                                c->d_mult + c->mult_words);
+    NLX_RC(commit_for(c, sw.as<uint64_t>(), CommitInput::ValuesNatural, d.num_wires, cw));
+    NLX_RC(fetch(ctx, cap.data(), cw->cap, capw * 8));
+    if (d.num_luts) {
+        uint32_t bad = 0;
+        NLX_RC(fetch(ctx, &bad, c->d_mult + c->mult_words, 4));
+        if (bad) return ctx->fail(NLX_E_INVAL, "a looked-up input is not in its table (set_lookup_wires)");
+    }
+    w.u64s(cap.data(), capw);
+    NLX_RC(observe_hash(c->hasher, ch, d.circuit_digest, 1));
+    ch.observe(pih, 4);   // InnerHasher: Goldilocks Poseidon under both configs
+    NLX_RC(observe_hash(c->hasher, ch, cap.data(), capw / 4));
+    uint64_t betas[2] = {0, 0}, gammas[2] = {0, 0}, alphas[2] = {0, 0};
+    for (uint32_t i = 0; i < nc; i++) betas[i] = ch.challenge();
+    for (uint32_t i = 0; i < nc; i++) gammas[i] = ch.challenge();
+    // lookup challenges: deltas = betas ++ gammas ++ 2 nc more, NUM_COINS_LOOKUP = 4 per round (A, B, alpha, delta)
+    // deltas and lut_polys are the SOURCES of asynchronous host-to-device copies: they live in the call's state, past its drain
+    uint64_t* const deltas = pc.deltas;
+    uint64_t* const lut_polys = pc.lut_polys;
+    uint64_t* d_deltas = nullptr;   // deltas[4 nc] | lut_polys[nc tables]
+    if (d.num_luts) {
+        for (uint32_t i = 0; i < nc; i++) { deltas[i] = betas[i]; deltas[nc + i] = gammas[i]; }
+        for (uint32_t i = 0; i < 2 * nc; i++) deltas[2 * nc + i] = ch.challenge();
+        d_deltas = scratch.alloc_as<uint64_t>((size_t)(8 + 2 * 16) * 8);
+        if (!d_deltas) return NLX_E_NOMEM;
+        NLX_HIP(ctx, hipMemcpyAsync(d_deltas, deltas, sizeof pc.deltas, hipMemcpyHostToDevice, st));
+    }
+
+    // ---- 4. partial products and Z ----
+    c->clock.stage("zs_partial_products");
+    NLX_RC(zs_stage(c, sw.as<uint64_t>(), betas, gammas, d_deltas, cz, scratch));
+    if (d.num_luts) {
+        // vanishing_poly::get_lut_poly per (round, table), on the host while the device builds the Zs commitment: the pairs
+        // (inp + B out) as coefficients in delta, first entry highest, zero-padded to whole table rows
+        for (uint32_t ci = 0; ci < nc; ci++)
+            for (uint32_t t = 0; t < d.num_luts; t++) {
+                const uint32_t len = c->lut_sizes[t], slots = c->lk.n_lut_slots;
+                const uint32_t degree = slots * ((len + slots - 1) / slots);
+                const uint16_t* pr = &c->lut_pairs[2 * (size_t)c->lut_offsets[t]];
+                const uint64_t B = deltas[4 * ci + 1], dl = deltas[4 * ci + 3];
+                uint64_t acc = 0;
+                for (uint32_t i = 0; i < len; i++) acc = gl::add(gl::mul(acc, dl), gl::add((uint64_t)pr[2 * i], gl::mul(B, (uint64_t)pr[2 * i + 1])));
+                acc = gl::mul(acc, gl::pow(dl, degree - len));
+                lut_polys[ci * d.num_luts + t] = acc;
             }
+        NLX_HIP(ctx, hipMemcpyAsync(d_deltas + 8, lut_polys, sizeof(uint64_t) * nc * d.num_luts, hipMemcpyHostToDevice, st));
+    }
+    NLX_RC(fetch(ctx, cap.data(), cz->cap, capw * 8));
+    w.u64s(cap.data(), capw);
+    NLX_RC(observe_hash(c->hasher, ch, cap.data(), capw / 4));
+    for (uint32_t i = 0; i < nc; i++) alphas[i] = ch.challenge();
+
+    // ---- 5. quotient ----
+    c->clock.stage("quotient_eval");
+    NLX_RC(quotient_stage(c, cw.get(), cz.get(), betas, gammas, alphas, pih, d_deltas, d_deltas ? d_deltas + 8 : nullptr, cq, c->clock, scratch));
+    NLX_RC(fetch(ctx, cap.data(), cq->cap, capw * 8));
+    w.u64s(cap.data(), capw);
+    NLX_RC(observe_hash(c->hasher, ch, cap.data(), capw / 4));
+
+    // ---- 6. openings ----
+    c->clock.stage("openings");
+    uint64_t zeta[2], gzeta[2];
+    ch.ext_challenge(zeta);
+    {
+        const uint64_t g = gl::root_of_unity(log_n);
+        gzeta[0] = gl::mul(zeta[0], g);
+        gzeta[1] = gl::mul(zeta[1], g);
+    }
+    const nlx_commit* oracles[4] = {c->cs.get(), cw.get(), cz.get(), cq.get()};
+    const uint32_t n_open = c->n_cs + d.num_wires + c->n_zs + c->n_q;
+    const OpeningPoints& pts = pc.points;
+    NLX_RC(pc.points.upload(scratch, zeta, gzeta, log_n));
+    const uint32_t nlk = c->n_lk_polys, n_next = nc + nlk;
+    uint64_t* d_open = scratch.alloc_as<uint64_t>((size_t)(n_open + n_next) * 16);
+    uint64_t* d_eval_scratch = scratch.alloc_as<uint64_t>(eval_scratch_words(d.num_wires > c->n_cs ? d.num_wires : c->n_cs, log_n) * 8);
+    if (!d_open || !d_eval_scratch) return NLX_E_NOMEM;
+    {
+        uint32_t off = 0;
+        for (int o = 0; o < 4; o++) {
+            launch_eval_br(st, oracles[o]->coeffs_br, n, oracles[o]->n_cols, log_n, pts.zeta(), d_open + 2 * (size_t)off,
+                           d_eval_scratch, pts.zeta_pows());
+            off += oracles[o]->n_cols;
         }
+        launch_eval_br(st, cz->coeffs_br, n, nc, log_n, pts.gzeta(), d_open + 2 * (size_t)n_open, d_eval_scratch,
+                       pts.gzeta_pows());
+        if (nlk)  // lookup_zs_next: the lookup polynomials (columns n_zpp.. of the Zs commitment) at g zeta
+            launch_eval_br(st, cz->coeffs_br + (size_t)c->n_zpp * n, n, nlk, log_n, pts.gzeta(),
+                           d_open + 2 * (size_t)(n_open + nc), d_eval_scratch, pts.gzeta_pows());
+        NLX_HIP(ctx, hipStreamSynchronize(st));
     }
-    if (defer) {
-        for (void* q : {(void*)d_alpha_pows, (void*)d_qvals, (void*)d_qchunks})
-            if (q) defer->push_back(q);
-    } else {
-        (void)hipStreamSynchronize(st);
-        ctx->release(d_alpha_pows);
-        ctx->release(d_qvals);
-        ctx->release(d_qchunks);
+    std::vector<uint64_t> open((size_t)(n_open + n_next) * 2);
+    NLX_RC(fetch(ctx, open.data(), d_open, open.size() * 8));
+    if (nlk) {
+        // CommonCircuitData::fri_all_polys lists the lookup polynomials LAST in the zeta batch (after the quotient chunks):
+        // move their openings from the middle (commitment order) to the end, then everything below reads FRI order
+        uint64_t* zs0 = open.data() + 2 * (size_t)(c->n_cs + d.num_wires);
+        std::vector<uint64_t> lkv(zs0 + 2 * (size_t)c->n_zpp, zs0 + 2 * (size_t)c->n_zs);
+        memmove(zs0 + 2 * (size_t)c->n_zpp, zs0 + 2 * (size_t)c->n_zs, 2 * (size_t)c->n_q * 8);
+        memcpy(zs0 + 2 * (size_t)(c->n_zpp + c->n_q), lkv.data(), lkv.size() * 8);
     }
-    return rc;
+    {
+        // OpeningSet wire order: constants, plonk_sigmas, wires, plonk_zs, plonk_zs_next, partial_products, quotient_polys
+        const uint64_t* o_cs = open.data();
+        const uint64_t* o_w = o_cs + 2 * (size_t)c->n_cs;
+        const uint64_t* o_zs = o_w + 2 * (size_t)d.num_wires;
+        const uint64_t* o_pp = o_zs + 2 * (size_t)nc;
+        const uint64_t* o_q = o_zs + 2 * (size_t)c->n_zpp;
+        const uint64_t* o_lk = o_q + 2 * (size_t)c->n_q;
+        const uint64_t* o_next = open.data() + 2 * (size_t)n_open;
+        w.u64s(o_cs, 2 * (size_t)c->n_cs);
+        w.u64s(o_w, 2 * (size_t)d.num_wires);
+        w.u64s(o_zs, 2 * (size_t)nc);
+        w.u64s(o_next, 2 * (size_t)nc);
+        w.u64s(o_lk, 2 * (size_t)nlk);                    // lookup_zs, lookup_zs_next (read_opening_set order)
+        w.u64s(o_next + 2 * (size_t)nc, 2 * (size_t)nlk);
+        w.u64s(o_pp, 2 * (size_t)nc * npp);
+        w.u64s(o_q, 2 * (size_t)c->n_q);
+        ch.observe(open.data(), 2 * (size_t)n_open);
+        ch.observe(o_next, 2 * (size_t)n_next);
+    }
+
+    // ---- 7. FRI ----
+    {
+        FriProveArgs fa;
+        for (int o = 0; o < 4; o++) fa.oracles[o] = oracles[o];
+        fa.n_oracles = 4;
+        fa.nz[2] = nc;  // plonk_zs_next: the first nc columns of the Zs / partial-products oracle
+        fa.tail_oracle = 2;  // the lookup polynomials: its last nlk columns, a group of their own at the end of both batches
+        fa.tail_cols = nlk;
+        for (int i = 0; i < 2; i++) { fa.zeta[i] = zeta[i]; fa.gzeta[i] = gzeta[i]; }
+        fa.open0 = open.data();
+        fa.open1 = open.data() + 2 * (size_t)n_open;
+        fa.log_n = log_n; fa.rate_bits = d.rate_bits; fa.cap_height = cap_h; fa.arity_bits = d.fri_arity_bits;
+        fa.pow_bits = d.fri_pow_bits; fa.n_queries = d.fri_num_queries; fa.n_rounds = NR;
+        fa.d_coset_base = c->d_coset_base;
+        fa.d_wA_inv = c->d_wA_inv;
+        fa.hasher = c->hasher;
+        NLX_RC(fri_prove(ctx, fa, ch, w, scratch, c->clock));
+    }
+    w.usize(d.num_public_inputs);  // write_proof_with_public_inputs: write_usize(len), then the field vec
+    w.u64s(h_pis.data(), h_pis.size());
+    c->clock.end();
+    if (w.overflow) return ctx->fail(NLX_E_RANGE, "proof buffer too small (need %zu bytes)", nlx_proof_max_bytes(c));
+    *proof_len = w.len;
+    return NLX_OK;
 }
 
 }  // namespace
@@ -728,281 +855,24 @@ int32_t nlx_prove(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_
                   size_t proof_cap, size_t* proof_len) NLX_TRY {
     if (!c) return NLX_E_INVAL;
     nlx_ctx* ctx = c->ctx;
-    const nlx_circuit_desc& d = c->d;
-    if (!wires || !proof_out || !proof_len || (!public_inputs && d.num_public_inputs))
+    if (!wires || !proof_out || !proof_len || (!public_inputs && c->d.num_public_inputs))
         return ctx->fail(NLX_E_INVAL, "NULL argument");
     *proof_len = 0;
     (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const size_t n = c->n();
-    const unsigned log_n = d.degree_bits, cap_h = d.cap_height;
-    const uint32_t nc = d.num_challenges, npp = d.num_partial_products;
-    const uint32_t NR = c->n_fri_rounds;
-    const size_t capw = (size_t)4 << cap_h;
-    int32_t rc = NLX_OK;
-
-    // everything allocated here is released at `done`
-    std::vector<void*> scratch;
-    auto dalloc = [&](size_t bytes) -> uint64_t* {
-        void* p = ctx->alloc(bytes);
-        if (p) scratch.push_back(p);
-        return (uint64_t*)p;
-    };
-    nlx_commit *cw = nullptr, *cz = nullptr, *cq = nullptr;
-    c->n_stages = 0;
-    c->timed = false;
-    auto stage = [&](const char* name) {
-        if (c->n_stages < NLX_MAX_STAGES) {
-            (void)hipEventRecord(c->ev[c->n_stages], st);
-            c->stage_names[c->n_stages++] = name;
-        }
-    };
     Writer w{proof_out, 0, proof_cap};
-    Challenger ch;
-    std::vector<uint64_t> cap(capw);
-    uint64_t pih[4];
-    std::vector<uint64_t> h_pis(public_inputs, public_inputs + d.num_public_inputs);
-    hash_no_pad_host(h_pis.data(), h_pis.size(), pih);
-
-#define CHECK(x) do { rc = (x); if (rc) goto done; } while (0)
-#define HIPCHK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { rc = ctx->hip_fail(e__, #call); goto done; } } while (0)
-#define CHECK_ALLOC(p) do { if (!(p)) { rc = NLX_E_NOMEM; goto done; } } while (0)
-    {
-        // ---- 2. wires commitment ----
-        stage("commit_wires");
-        Staged sw(ctx, wires, (size_t)d.num_wires * n * 8, true, false);
-        CHECK(sw.status);
-        // prover::set_lookup_wires, the first thing prove_with_partition_witness does to the witness it is handed: multiplicity
-        // wires and padding slots, on the device copy (a device witness is written in place, as upstream's PartitionWitness is)
-        if (d.num_luts)
-            launch_set_lookup_wires(st, c->lk, c->d_tabs, c->h_tabs.data(), sw.as<uint64_t>(), n, c->d_mult, c->mult_words,
-                                    c->d_mult + c->mult_words);
-        CHECK(commit_for(c, sw.as<uint64_t>(), CommitInput::ValuesNatural, d.num_wires, &cw));
-        CHECK(fetch(ctx, cap.data(), cw->cap, capw * 8));
-        if (d.num_luts) {
-            uint32_t bad = 0;
-            CHECK(fetch(ctx, &bad, c->d_mult + c->mult_words, 4));
-            if (bad) { rc = ctx->fail(NLX_E_INVAL, "a looked-up input is not in its table (set_lookup_wires)"); goto done; }
-        }
-        w.u64s(cap.data(), capw);
-        CHECK(observe_hash(c->hasher, ch, d.circuit_digest, 1));
-        ch.observe(pih, 4);   // InnerHasher: Goldilocks Poseidon under both configs
-        CHECK(observe_hash(c->hasher, ch, cap.data(), capw / 4));
-        uint64_t betas[2] = {0, 0}, gammas[2] = {0, 0}, alphas[2] = {0, 0};
-        for (uint32_t i = 0; i < nc; i++) betas[i] = ch.challenge();
-        for (uint32_t i = 0; i < nc; i++) gammas[i] = ch.challenge();
-        // lookup challenges: deltas = betas ++ gammas ++ 2 nc more, NUM_COINS_LOOKUP = 4 per round (A, B, alpha, delta)
-        // deltas and lut_polys are the SOURCES of asynchronous host-to-device copies: both live until the function returns (the
-        // fetch() of the Zs cap below synchronises the stream after the second copy is enqueued; nothing here relies on the
-        // runtime staging a pageable source at call time)
-        uint64_t deltas[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        uint64_t lut_polys[2 * 16] = {};
-        uint64_t* d_deltas = nullptr;   // deltas[4 nc] | lut_polys[nc tables]
-        if (d.num_luts) {
-            for (uint32_t i = 0; i < nc; i++) { deltas[i] = betas[i]; deltas[nc + i] = gammas[i]; }
-            for (uint32_t i = 0; i < 2 * nc; i++) deltas[2 * nc + i] = ch.challenge();
-            d_deltas = dalloc((size_t)(8 + 2 * 16) * 8);
-            CHECK_ALLOC(d_deltas);
-            HIPCHK(hipMemcpyAsync(d_deltas, deltas, sizeof deltas, hipMemcpyHostToDevice, st));
-        }
-
-        // ---- 4. partial products and Z ----
-        stage("zs_partial_products");
-        CHECK(zs_stage(c, sw.as<uint64_t>(), betas, gammas, d_deltas, &cz, &scratch));
-        if (d.num_luts) {
-            // vanishing_poly::get_lut_poly per (round, table), on the host while the device builds the Zs commitment: the pairs
-            // (inp + B out) as coefficients in delta, first entry highest, zero-padded to whole table rows
-            for (uint32_t ci = 0; ci < nc; ci++)
-                for (uint32_t t = 0; t < d.num_luts; t++) {
-                    const uint32_t len = c->lut_sizes[t], slots = c->lk.n_lut_slots;
-                    const uint32_t degree = slots * ((len + slots - 1) / slots);
-                    const uint16_t* pr = &c->lut_pairs[2 * (size_t)c->lut_offsets[t]];
-                    const uint64_t B = deltas[4 * ci + 1], dl = deltas[4 * ci + 3];
-                    uint64_t acc = 0;
-                    for (uint32_t i = 0; i < len; i++) acc = gl::add(gl::mul(acc, dl), gl::add((uint64_t)pr[2 * i], gl::mul(B, (uint64_t)pr[2 * i + 1])));
-                    acc = gl::mul(acc, gl::pow(dl, degree - len));
-                    lut_polys[ci * d.num_luts + t] = acc;
-                }
-            HIPCHK(hipMemcpyAsync(d_deltas + 8, lut_polys, sizeof(uint64_t) * nc * d.num_luts, hipMemcpyHostToDevice, st));
-        }
-        CHECK(fetch(ctx, cap.data(), cz->cap, capw * 8));
-        w.u64s(cap.data(), capw);
-        CHECK(observe_hash(c->hasher, ch, cap.data(), capw / 4));
-        for (uint32_t i = 0; i < nc; i++) alphas[i] = ch.challenge();
-
-        // ---- 5. quotient ----
-        stage("quotient_eval");
-        CHECK(quotient_stage(c, cw, cz, betas, gammas, alphas, pih, d_deltas, d_deltas ? d_deltas + 8 : nullptr, &cq, stage, &scratch));
-        CHECK(fetch(ctx, cap.data(), cq->cap, capw * 8));
-        w.u64s(cap.data(), capw);
-        CHECK(observe_hash(c->hasher, ch, cap.data(), capw / 4));
-
-        // ---- 6. openings ----
-        stage("openings");
-        uint64_t zeta[2], gzeta[2];
-        ch.ext_challenge(zeta);
-        {
-            const uint64_t g = gl::root_of_unity(log_n);
-            gzeta[0] = gl::mul(zeta[0], g);
-            gzeta[1] = gl::mul(zeta[1], g);
-        }
-        const nlx_commit* oracles[4] = {c->cs, cw, cz, cq};
-        const uint32_t n_open = c->n_cs + d.num_wires + c->n_zs + c->n_q;
-        uint64_t* d_points = dalloc(2048);
-        const uint32_t nlk = c->n_lk_polys, n_next = nc + nlk;
-        uint64_t* d_open = dalloc((size_t)(n_open + n_next) * 16);
-        uint64_t* d_eval_scratch = dalloc(eval_scratch_words(d.num_wires > c->n_cs ? d.num_wires : c->n_cs, log_n) * 8);
-        CHECK_ALLOC(d_points && d_open && d_eval_scratch);
-        {
-            // zeta^(2^k) and (g zeta)^(2^k), k < log_n, computed on the host (zeta is known here) so the
-            // evaluation kernels start immediately
-            uint64_t pts[4 + 2 * 2 * 32] = {zeta[0], zeta[1], gzeta[0], gzeta[1]};
-            gl::Ext za{zeta[0], zeta[1]}, zb{gzeta[0], gzeta[1]};
-            for (unsigned k = 0; k < 32; k++) {
-                pts[4 + 2 * k] = za.a; pts[4 + 2 * k + 1] = za.b;
-                pts[4 + 64 + 2 * k] = zb.a; pts[4 + 64 + 2 * k + 1] = zb.b;
-                if (k + 1 < log_n) { za = gl::mul(za, za); zb = gl::mul(zb, zb); }
-            }
-            HIPCHK(hipMemcpyAsync(d_points, pts, sizeof pts, hipMemcpyHostToDevice, st));
-            uint32_t off = 0;
-            for (int o = 0; o < 4; o++) {
-                launch_eval_br(st, oracles[o]->coeffs_br, n, oracles[o]->n_cols, log_n, d_points, d_open + 2 * (size_t)off,
-                               d_eval_scratch, d_points + 4);
-                off += oracles[o]->n_cols;
-            }
-            launch_eval_br(st, cz->coeffs_br, n, nc, log_n, d_points + 2, d_open + 2 * (size_t)n_open, d_eval_scratch,
-                           d_points + 4 + 64);
-            if (nlk)  // lookup_zs_next: the lookup polynomials (columns n_zpp.. of the Zs commitment) at g zeta
-                launch_eval_br(st, cz->coeffs_br + (size_t)c->n_zpp * n, n, nlk, log_n, d_points + 2,
-                               d_open + 2 * (size_t)(n_open + nc), d_eval_scratch, d_points + 4 + 64);
-            HIPCHK(hipStreamSynchronize(st));
-        }
-        std::vector<uint64_t> open((size_t)(n_open + n_next) * 2);
-        CHECK(fetch(ctx, open.data(), d_open, open.size() * 8));
-        if (nlk) {
-            // CommonCircuitData::fri_all_polys lists the lookup polynomials LAST in the zeta batch (after the quotient chunks):
-            // move their openings from the middle (commitment order) to the end, then everything below reads FRI order
-            uint64_t* zs0 = open.data() + 2 * (size_t)(c->n_cs + d.num_wires);
-            std::vector<uint64_t> lkv(zs0 + 2 * (size_t)c->n_zpp, zs0 + 2 * (size_t)c->n_zs);
-            memmove(zs0 + 2 * (size_t)c->n_zpp, zs0 + 2 * (size_t)c->n_zs, 2 * (size_t)c->n_q * 8);
-            memcpy(zs0 + 2 * (size_t)(c->n_zpp + c->n_q), lkv.data(), lkv.size() * 8);
-        }
-        {
-            // OpeningSet wire order: constants, plonk_sigmas, wires, plonk_zs, plonk_zs_next, partial_products, quotient_polys
-            const uint64_t* o_cs = open.data();
-            const uint64_t* o_w = o_cs + 2 * (size_t)c->n_cs;
-            const uint64_t* o_zs = o_w + 2 * (size_t)d.num_wires;
-            const uint64_t* o_pp = o_zs + 2 * (size_t)nc;
-            const uint64_t* o_q = o_zs + 2 * (size_t)c->n_zpp;
-            const uint64_t* o_lk = o_q + 2 * (size_t)c->n_q;
-            const uint64_t* o_next = open.data() + 2 * (size_t)n_open;
-            w.u64s(o_cs, 2 * (size_t)c->n_cs);
-            w.u64s(o_w, 2 * (size_t)d.num_wires);
-            w.u64s(o_zs, 2 * (size_t)nc);
-            w.u64s(o_next, 2 * (size_t)nc);
-            w.u64s(o_lk, 2 * (size_t)nlk);                    // lookup_zs, lookup_zs_next (read_opening_set order)
-            w.u64s(o_next + 2 * (size_t)nc, 2 * (size_t)nlk);
-            w.u64s(o_pp, 2 * (size_t)nc * npp);
-            w.u64s(o_q, 2 * (size_t)c->n_q);
-            ch.observe(open.data(), 2 * (size_t)n_open);
-            ch.observe(o_next, 2 * (size_t)n_next);
-        }
-
-        // ---- 7. FRI ----
-        {
-            FriProveArgs fa;
-            for (int o = 0; o < 4; o++) fa.oracles[o] = oracles[o];
-            fa.n_oracles = 4;
-            fa.nz[2] = nc;  // plonk_zs_next: the first nc columns of the Zs / partial-products oracle
-            fa.tail_oracle = 2;  // the lookup polynomials: its last nlk columns, a group of their own at the end of both batches
-            fa.tail_cols = nlk;
-            for (int i = 0; i < 2; i++) { fa.zeta[i] = zeta[i]; fa.gzeta[i] = gzeta[i]; }
-            fa.open0 = open.data();
-            fa.open1 = open.data() + 2 * (size_t)n_open;
-            fa.log_n = log_n; fa.rate_bits = d.rate_bits; fa.cap_height = cap_h; fa.arity_bits = d.fri_arity_bits;
-            fa.pow_bits = d.fri_pow_bits; fa.n_queries = d.fri_num_queries; fa.n_rounds = NR;
-            fa.d_coset_base = c->d_coset_base;
-            fa.d_wA_inv = c->d_wA_inv;
-            fa.hasher = c->hasher;
-            CHECK(fri_prove(ctx, fa, ch, w, scratch, stage));
-        }
-        w.usize(d.num_public_inputs);  // write_proof_with_public_inputs: write_usize(len), then the field vec
-        w.u64s(h_pis.data(), h_pis.size());
-        stage("end");
-        c->n_stages--;  // "end" only closes the last interval
-        c->timed = true;
-        if (w.overflow) { rc = ctx->fail(NLX_E_RANGE, "proof buffer too small (need %zu bytes)", nlx_proof_max_bytes(c)); goto done; }
-        *proof_len = w.len;
-    }
-done:
-    {
-        hipError_t e = hipStreamSynchronize(st);
-        if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-        hipError_t le = hipGetLastError();
-        if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");
-    }
-    for (void* p : scratch) ctx->release(p);
-    if (cw) nlx_commit_destroy(cw);
-    if (cz) nlx_commit_destroy(cz);
-    if (cq) nlx_commit_destroy(cq);
-#undef CHECK
-#undef HIPCHK
-#undef CHECK_ALLOC
-    return rc;
+    ProveCall pc(ctx);
+    return pc.scratch.finish(prove_stages(c, pc, wires, public_inputs, w, proof_len));
 } NLX_CATCH(nullptr)
-
-// test hook nlx::batch_spawn_fault_after (armed by nlx_abi_selftest kind 3 / 4, ctx.hip): pretend that starting worker thread
-// number >= this fails; -1 = off
 
 int32_t nlx_batch_prove(nlx_circuit* const* workers, uint32_t n_workers, nlx_prove_job* jobs, size_t n_jobs) NLX_TRY {
-    if (!workers || n_workers == 0 || (!jobs && n_jobs)) return NLX_E_INVAL;
-    for (uint32_t w = 0; w < n_workers; w++) {
-        if (!workers[w]) return NLX_E_INVAL;
-        for (uint32_t v = 0; v < w; v++)
-            if (workers[v]->ctx == workers[w]->ctx) return workers[w]->ctx->fail(NLX_E_INVAL, "nlx_batch_prove: workers must use distinct contexts");
-    }
-    std::atomic<size_t> next{0};
-    auto run = [&](nlx_circuit* c) {
-        (void)hipSetDevice(c->ctx->device);
-        for (;;) {
-            const size_t j = next.fetch_add(1);
-            if (j >= n_jobs) return;
-            nlx_prove_job& job = jobs[j];
-            job.proof_len = 0;
-            job.status = nlx_prove(c, job.wires, job.public_inputs, job.proof_out, job.proof_cap, &job.proof_len);
-        }
-    };
-    if (n_workers == 1) {
-        run(workers[0]);
-    } else {
-        // a std::thread that is still joinable when it is destroyed calls std::terminate: if creating worker w fails
-        // (std::system_error: no more threads), the workers already started are left to drain the queue and are JOINED before the
-        // error leaves this function as a return code (NLX_CATCH); the jobs they proved keep their status
-        std::vector<std::thread> threads;
-        threads.reserve(n_workers);
-        bool spawn_failed = false;
-        for (uint32_t w = 0; w < n_workers; w++) {
-            try {
-                if (batch_spawn_fault_after >= 0 && (int)w >= batch_spawn_fault_after) throw std::system_error(std::make_error_code(std::errc::resource_unavailable_try_again));
-                threads.emplace_back(run, workers[w]);
-            } catch (...) {
-                spawn_failed = true;
-                break;
-            }
-        }
-        if (spawn_failed && threads.empty()) run(workers[0]);   // nobody started: the calling thread does the work
-        for (auto& t : threads) t.join();
-        if (spawn_failed) workers[0]->ctx->fail(NLX_OK, "nlx_batch_prove: could not start every worker thread; the jobs were proved by the ones that started");
-    }
-    for (size_t j = 0; j < n_jobs; j++)
-        if (jobs[j].status != NLX_OK) return jobs[j].status;
-    return NLX_OK;
+    return batch_prove("nlx_batch_prove", workers, n_workers, jobs, n_jobs, [](nlx_circuit* c, nlx_prove_job& job) {
+        return nlx_prove(c, job.wires, job.public_inputs, job.proof_out, job.proof_cap, &job.proof_len);
+    });
 } NLX_CATCH(nullptr)
-
 
 // ---- stage-level entry points (the fine seam of INTEGRATION.md §3) ----
 
-const nlx_commit* nlx_circuit_constants_sigmas(const nlx_circuit* c) NLX_TRY { return c ? c->cs : nullptr; } NLX_CATCH_VALUE(nullptr, nullptr)
+const nlx_commit* nlx_circuit_constants_sigmas(const nlx_circuit* c) NLX_TRY { return c ? c->cs.get() : nullptr; } NLX_CATCH_VALUE(nullptr, nullptr)
 
 int32_t nlx_partial_products_and_zs(nlx_circuit* c, const uint64_t* wires, const uint64_t betas[2], const uint64_t gammas[2],
                                     nlx_commit** zs_out) NLX_TRY {
@@ -1014,10 +884,11 @@ int32_t nlx_partial_products_and_zs(nlx_circuit* c, const uint64_t* wires, const
     if (c->d.num_luts) return ctx->fail(NLX_E_UNSUPPORTED, "circuits with lookup tables are proved through nlx_prove (the stage calls carry no lookup challenges)");
     Staged sw(ctx, wires, (size_t)c->d.num_wires * c->n() * 8, true, false);
     if (sw.status) return sw.status;
-    int32_t rc = zs_stage(c, sw.as<uint64_t>(), betas, gammas, nullptr, zs_out, nullptr);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-    return rc;
+    CommitPtr cz;
+    Scratch scratch(ctx);
+    NLX_RC(scratch.finish(zs_stage(c, sw.as<uint64_t>(), betas, gammas, nullptr, cz, scratch)));
+    *zs_out = cz.release();
+    return NLX_OK;
 } NLX_CATCH(nullptr)
 
 int32_t nlx_quotient_eval(nlx_circuit* c, const nlx_commit* wires, const nlx_commit* zs, const uint64_t betas[2],
@@ -1040,10 +911,12 @@ int32_t nlx_quotient_eval(nlx_circuit* c, const nlx_commit* wires, const nlx_com
     for (int i = 0; i < 4; i++)
         if (public_inputs_hash[i] >= gl::P) return ctx->fail(NLX_E_RANGE, "public inputs hash is not canonical");
     (void)hipSetDevice(ctx->device);
-    int32_t rc = quotient_stage(c, wires, zs, betas, gammas, alphas, public_inputs_hash, nullptr, nullptr, quotient_out, [](const char*) {}, nullptr);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-    return rc;
+    StageClock untimed;
+    CommitPtr cq;
+    Scratch scratch(ctx);
+    NLX_RC(scratch.finish(quotient_stage(c, wires, zs, betas, gammas, alphas, public_inputs_hash, nullptr, nullptr, cq, untimed, scratch)));
+    *quotient_out = cq.release();
+    return NLX_OK;
 } NLX_CATCH(nullptr)
 
 }  // extern "C"
@@ -1082,19 +955,18 @@ int32_t fri_prove_api(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n
     const unsigned log_n = oracles[0]->log_n, rate_bits = oracles[0]->rate_bits;
     int32_t rc = ctx->ensure_tables(log_n + rate_bits);
     if (rc) return rc;
-    std::vector<void*> scratch;
+    Scratch scratch(ctx);
     // coset bases g * w_L^r and w_A^-i
     const uint32_t R = 1u << rate_bits, A = 1u << params->arity_bits;
     std::vector<uint64_t> small(4 * R + A);
     coset_tables_host(log_n, rate_bits, small.data());
     const uint64_t w_A_inv = gl::inv(gl::root_of_unity(params->arity_bits));
     for (uint32_t i = 0; i < A; i++) small[4 * R + i] = gl::pow(w_A_inv, i);
-    uint64_t* d_small = (uint64_t*)ctx->alloc(small.size() * 8);
+    uint64_t* d_small = scratch.alloc_as<uint64_t>(small.size() * 8);
     if (!d_small) return NLX_E_NOMEM;
-    scratch.push_back(d_small);
     hipError_t e = hipMemcpyAsync(d_small, small.data(), small.size() * 8, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ctx->release(d_small); return ctx->hip_fail(e, "hipMemcpyAsync(tables)"); }
+    if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync(tables)");
     FriProveArgs fa;
     for (uint32_t o = 0; o < n_oracles; o++) fa.oracles[o] = oracles[o];
     fa.n_oracles = n_oracles;
@@ -1116,11 +988,8 @@ int32_t fri_prove_api(nlx_ctx* ctx, const nlx_commit* const* oracles, uint32_t n
     ch.n_in = challenger->n_input;
     ch.n_out = challenger->n_output;
     Writer w{proof_out, 0, proof_cap};
-    rc = fri_prove(ctx, fa, ch, w, scratch, [](const char*) {});
-    e = hipStreamSynchronize(ctx->stream);
-    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-    for (void* q : scratch) ctx->release(q);
-    if (rc) return rc;
+    StageClock untimed;
+    NLX_RC(scratch.finish(fri_prove(ctx, fa, ch, w, scratch, untimed)));
     if (w.overflow) return ctx->fail(NLX_E_RANGE, "proof buffer too small");
     memcpy(challenger->state, ch.state, sizeof ch.state);
     memcpy(challenger->input, ch.in_buf, sizeof ch.in_buf);

@@ -217,12 +217,13 @@ extern "C" int32_t nlx_sha256_bind_round(nlx_ctx* ctx, const uint64_t* trace, ui
     if (tr.status) return tr.status;
     Staged so(ctx, acc_out, 2 * n * 8, false, true);
     if (so.status) return so.status;
-    gl::Ext* d_fp = (gl::Ext*)ctx->alloc((size_t)n_blocks * sizeof(gl::Ext));
+    std::vector<gl::Ext> fp_h(n_blocks), start(n_blocks);   // `start` becomes the source of a queued copy: it outlives the scratch
+    Scratch scratch(ctx);
+    gl::Ext* d_fp = scratch.alloc_as<gl::Ext>((size_t)n_blocks * sizeof(gl::Ext));
     if (!d_fp) return NLX_E_NOMEM;
     const gl::Ext g{gamma[0] % gl::P, gamma[1] % gl::P};
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(k_sha_bind_block, dim3((n_blocks + 63) / 64), dim3(64), 0, st, tr.as<uint64_t>(), n_blocks, g, d_fp);
-    std::vector<gl::Ext> fp_h(n_blocks), start(n_blocks);
     int32_t rc = fetch(ctx, fp_h.data(), d_fp, (size_t)n_blocks * sizeof(gl::Ext));
     if (!rc) {
         const gl::Ext g25 = gl::pow(g, 25);  // a block absorbs 17 + 8 elements
@@ -241,12 +242,7 @@ extern "C" int32_t nlx_sha256_bind_round(nlx_ctx* ctx, const uint64_t* trace, ui
                            so.as<uint64_t>());
         rc = so.finish();
     }
-    hipError_t e = hipStreamSynchronize(st);
-    ctx->release(d_fp);
-    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-    hipError_t le = hipGetLastError();
-    if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");
-    return rc;
+    return scratch.finish(rc);
 } NLX_CATCH(ctx)
 
 
@@ -264,7 +260,8 @@ extern "C" int32_t nlx_sha256_trace(nlx_ctx* ctx, const uint32_t* blocks, const 
     if (sf.status) return sf.status;
     Staged st(ctx, trace_out, (size_t)NLX_SHA256_COLS * n * 8, false, true);
     if (st.status) return st.status;
-    uint32_t* d_hin = (uint32_t*)ctx->alloc((size_t)(n_blocks + 1) * 32);
+    Scratch scratch(ctx);
+    uint32_t* d_hin = scratch.alloc_as<uint32_t>((size_t)(n_blocks + 1) * 32);
     if (!d_hin) return NLX_E_NOMEM;
     hipLaunchKernelGGL(k_sha_chain, dim3((n_blocks + 63) / 64), dim3(64), 0, ctx->stream, sb.as<uint32_t>(),
                        sf.as<uint8_t>(), n_blocks, d_hin);
@@ -276,10 +273,5 @@ extern "C" int32_t nlx_sha256_trace(nlx_ctx* ctx, const uint32_t* blocks, const 
         rc = fetch(ctx, dg, d_hin + (size_t)n_blocks * 8, 32);
         for (int k = 0; k < 8; k++) digest_out[k] = dg[k];
     }
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    ctx->release(d_hin);
-    if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-    hipError_t le = hipGetLastError();
-    if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");
-    return rc;
+    return scratch.finish(rc);
 } NLX_CATCH(ctx)

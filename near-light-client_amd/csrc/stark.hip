@@ -14,8 +14,6 @@
 //  * quotient chunks come from per-coset inverse transforms + a 2^qdb-point DFT across cosets, as in the
 //    plonky2 path; commitments, openings and FRI are the same device code as nlx_prove.
 #include <algorithm>
-#include <atomic>
-#include <thread>
 #include <vector>
 #include "commit.hpp"
 #include "fri.hpp"
@@ -254,10 +252,7 @@ struct nlx_stark {
     uint64_t* d_periodic = nullptr;            // [n_periodic][2^qdb][period]
     std::vector<uint64_t> periodic;            // canonicalised host copy
     const uint64_t* d_q_inv_scale_br = nullptr;  // ctx-owned
-    hipEvent_t ev[NLX_MAX_STAGES + 1]{};
-    const char* stage_names[NLX_MAX_STAGES]{};
-    uint32_t n_stages = 0;
-    bool timed = false;
+    StageClock clock;
 };
 
 static size_t stark_proof_max_bytes(const nlx_stark_desc& d, uint32_t n_rounds) {
@@ -542,8 +537,8 @@ int32_t nlx_stark_build(nlx_ctx* ctx, const nlx_stark_desc* desc, nlx_stark** ou
             s->d.degree_bits + s->d.rate_bits <= 28)
             s->gen = airgen_find(airgen_program_hash(s->program.data(), s->program.size()), (uint32_t)s->program.size());
     }
-    for (int i = 0; i <= NLX_MAX_STAGES; i++)
-        if (hipEventCreate(&s->ev[i]) != hipSuccess) return fail(ctx->fail(NLX_E_HIP, "hipEventCreate failed"));
+    rc = s->clock.create(ctx);
+    if (rc) return fail(rc);
     {
         hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return fail(ctx->hip_fail(e, "hipStreamSynchronize"));
@@ -562,9 +557,7 @@ void nlx_stark_destroy(nlx_stark* s) NLX_TRY {
     ctx->release(s->d_seg);
     ctx->release(s->d_l_inv);
     ctx->release(s->d_periodic);
-    for (int i = 0; i <= NLX_MAX_STAGES; i++)
-        if (s->ev[i]) (void)hipEventDestroy(s->ev[i]);
-    delete s;
+    delete s;   // and with it the stage clock's events
 } NLX_CATCH_VOID(nullptr)
 
 int32_t nlx_stark_quotient_kernel(const nlx_stark* s) NLX_TRY { return s && s->gen ? 1 : 0; } NLX_CATCH(nullptr)
@@ -574,19 +567,227 @@ size_t nlx_stark_proof_max_bytes(const nlx_stark* s) NLX_TRY {
 } NLX_CATCH_VALUE(nullptr, 0)
 
 int32_t nlx_stark_stage_times(const nlx_stark* s, uint32_t* n_stages, const char** names_out, float* ms_out) NLX_TRY {
-    if (!s || !n_stages) return NLX_E_INVAL;
-    if (!s->timed) { *n_stages = 0; return NLX_OK; }
-    *n_stages = s->n_stages;
-    for (uint32_t i = 0; i < s->n_stages; i++) {
-        if (names_out) names_out[i] = s->stage_names[i];
-        if (ms_out) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, s->ev[i], s->ev[i + 1]) != hipSuccess) ms = -1.f;
-            ms_out[i] = ms;
+    return s ? s->clock.times(n_stages, names_out, ms_out) : NLX_E_INVAL;
+} NLX_CATCH(nullptr)
+
+}  // extern "C"
+
+namespace {
+// What one STARK proof holds until its stream work has drained.  Members go in reverse order: the scratch first - which
+// synchronises -, then the host sources of the asynchronous copies (values, h_cols, the opening points), then the commitments.
+struct StarkCall {
+    CommitPtr cr[3], cq;
+    std::vector<uint64_t> values;           // readable by NLX_AIR_PUBLIC: the public inputs, then the verifier challenges in the order drawn
+    std::vector<const uint64_t*> h_cols;
+    OpeningPoints points;
+    Scratch scratch;
+    explicit StarkCall(nlx_ctx* ctx) : scratch(ctx) {}
+};
+
+int32_t stark_stages(nlx_stark* s, StarkCall& sc, nlx_round_fn round_fn, void* user, const uint64_t* public_inputs, Writer& w,
+                     size_t* proof_len) {
+    nlx_ctx* ctx = s->ctx;
+    const nlx_stark_desc& d = s->d;
+    hipStream_t st = ctx->stream;
+    const unsigned log_n = d.degree_bits, cap_h = d.cap_height, qdb = s->qdb;
+    const size_t n = (size_t)1 << log_n, L = n << d.rate_bits, capw = (size_t)4 << cap_h;
+    const uint32_t nc = d.num_challenges, ncols = d.n_cols, nq = s->nq, NRD = s->n_rounds;
+    Scratch& scratch = sc.scratch;
+    CommitPtr* const cr = sc.cr;
+    CommitPtr& cq = sc.cq;
+    uint32_t col0[4] = {0, 0, 0, 0};
+    Challenger ch;
+    // The transcript opens with the statement - the AIR digest, then the public inputs - before any commitment: the
+    // public inputs enter the AIR linearly, so a transcript without them would let a prover choose them after alpha and
+    // zeta are known (the starky of the pinned era had that gap; plonky2's own prover observes circuit_digest and the
+    // public-input hash first, and so does this one).
+    ch.observe(s->air_digest, 4);
+    ch.observe(public_inputs, d.num_public_inputs);
+    std::vector<uint64_t> cap(capw);
+    std::vector<uint64_t>& values = sc.values;
+    values.assign(public_inputs, public_inputs + d.num_public_inputs);
+    std::vector<uint64_t> round_vals;
+    std::vector<const uint64_t*>& h_cols = sc.h_cols;
+    h_cols.resize(ncols);
+
+    s->clock.begin(st);
+    s->clock.stage("commit_trace");
+    // ---- trace commitments, one per round (prover.rs: PolynomialBatch::from_values(trace_poly_values, ..);
+    //      starkyx: one TraceWriter round per commitment, challenges drawn in between) ----
+    for (uint32_t r = 0; r < NRD; r++) {
+        const uint32_t rcols = s->round_cols[r];
+        const uint32_t n_rv = s->round_values[r];
+        uint64_t rv[64];
+        const uint64_t* tr_ptr = round_fn(user, r, values.data() + d.num_public_inputs, (uint32_t)(values.size() - d.num_public_inputs),
+                                          n_rv ? rv : nullptr);
+        if (!tr_ptr) return ctx->fail(NLX_E_INVAL, "round %u: the round callback returned NULL", r);
+        for (uint32_t k = 0; k < n_rv; k++) rv[k] %= gl::P;
+        Staged tr(ctx, tr_ptr, (size_t)rcols * n * 8, true, false);
+        NLX_RC(tr.status);
+        // one PolynomialBatch, or (batch_cols) ceil(rcols / batch_cols) of them: transformed together, a tree and a cap each, the
+        // caps into the transcript and the proof in batch order
+        NLX_RC(commit_build(ctx, tr.as<uint64_t>(), n, CommitInput::ValuesNatural, rcols, log_n, d.rate_bits, cap_h, cr[r], d.leaf_group_cols,
+                           d.batch_cols));
+        for (uint32_t k = 0; k < cr[r]->n_trees; k++) {
+            NLX_RC(fetch(ctx, cap.data(), cr[r]->cap + (size_t)k * cr[r]->tree_words, capw * 8));
+            w.u64s(cap.data(), capw);
+            ch.observe(cap.data(), capw);
+        }
+        if (n_rv) {  // the round's values: into the transcript before its challenges, into the proof's tail later
+            ch.observe(rv, n_rv);
+            values.insert(values.end(), rv, rv + n_rv);
+            round_vals.insert(round_vals.end(), rv, rv + n_rv);
+        }
+        for (uint32_t k = 0; k < s->round_challenges[r]; k++) values.push_back(ch.challenge());
+        for (uint32_t c = 0; c < rcols; c++) h_cols[col0[r] + c] = cr[r]->lde + (size_t)c * L;
+        col0[r + 1] = col0[r] + rcols;
+    }
+    uint64_t alphas[2] = {0, 0};
+    for (uint32_t i = 0; i < nc; i++) alphas[i] = ch.challenge();
+
+    // ---- compute_quotient_polys ----
+    s->clock.stage("quotient_eval");
+    const size_t Q = n << qdb;
+    // public inputs ++ round challenges, then each segment's alpha^(constraints after it) per challenge
+    const uint32_t n_seg = (uint32_t)s->seg_after.size();
+    const size_t n_values = values.size();
+    for (uint32_t sg = 0; sg < n_seg; sg++)
+        for (uint32_t i = 0; i < 2; i++) values.push_back(gl::pow(alphas[i], s->seg_after[sg]));
+    uint64_t* d_pis = scratch.alloc_as<uint64_t>(values.size() * 8);
+    const uint64_t** d_cols = scratch.alloc_as<const uint64_t*>((size_t)ncols * 8);
+    uint64_t* d_qvals = scratch.alloc_as<uint64_t>((size_t)nc * Q * 8);
+    uint64_t* d_qchunks = scratch.alloc_as<uint64_t>((size_t)nc * Q * 8);
+    uint64_t* d_part = n_seg > 1 ? scratch.alloc_as<uint64_t>((size_t)n_seg * nc * Q * 8) : nullptr;
+    if (!d_pis || !d_cols || !d_qvals || !d_qchunks || (n_seg > 1 && !d_part)) return NLX_E_NOMEM;
+    NLX_HIP(ctx, hipMemcpyAsync(d_pis, values.data(), values.size() * 8, hipMemcpyHostToDevice, st));
+    NLX_HIP(ctx, hipMemcpyAsync(d_cols, h_cols.data(), (size_t)ncols * 8, hipMemcpyHostToDevice, st));
+    {
+        AirParams ap{};
+        ap.cols = d_cols; ap.program = s->d_program; ap.pis = d_pis;
+        ap.coset_base = s->d_q_coset_base; ap.zh_inv = s->d_q_zh_inv; ap.l_inv = s->d_l_inv;
+        ap.periodic = s->d_periodic; ap.period_bits = d.period_bits;
+        ap.w_n_table = ctx->tables.fwd[log_n];
+        ap.out = d_qvals;
+        ap.alphas[0] = alphas[0]; ap.alphas[1] = alphas[1];
+        ap.g_inv = gl::inv(gl::root_of_unity(log_n));
+        ap.log_n = log_n; ap.rate_bits = d.rate_bits; ap.qdb = qdb; ap.n_words = d.n_words; ap.nc = nc;
+        ap.n_regs = s->n_regs; ap.n_pis = d.num_public_inputs;
+        ap.seg = s->d_seg; ap.seg_mul = d_pis + n_values; ap.part = d_part; ap.n_seg = n_seg;
+        // one wave per block: the LDS register file (n_regs x 64 lanes x 8 B) is the occupancy limiter, and
+        // single-wave blocks pack the 160 KB of a CU at the finest granularity
+        unsigned bs = 64;
+        while (bs > n) bs >>= 1;
+        ctx->begin_kernel("air_quotient", 8.0 * Q * (2.0 * ncols + nc));
+        if (s->gen) s->gen->launch(st, (unsigned)(Q / AIRGEN_BLOCK), n_seg, ap);   // every segment of every point, straight-line code
+        for (size_t gi = 0; !s->gen && gi < s->seg_group.size(); gi++) {
+            const uint32_t first = s->seg_group[gi], last = gi + 1 < s->seg_group.size() ? s->seg_group[gi + 1] : n_seg;
+            AirParams gp = ap;
+            gp.seg = ap.seg + 2 * first;
+            gp.seg_mul = ap.seg_mul + 2 * first;
+            gp.part = n_seg > 1 ? ap.part + (size_t)first * nc * Q : nullptr;
+            const size_t lds = (size_t)bs * s->seg_regs[last - 1] * 8;  // the group's largest register file
+            hipLaunchKernelGGL(k_air_quotient, dim3((unsigned)(Q / bs), last - first), dim3(bs), lds, st, gp);
+        }
+        if (n_seg > 1)
+            hipLaunchKernelGGL(k_air_combine, dim3((unsigned)((nc * Q + 255) / 256)), dim3(256), 0, st, d_part, s->d_q_zh_inv,
+                               d_qvals, n_seg, nc, log_n, log_n + qdb);
+        ctx->end_kernel();
+    }
+    s->clock.stage("quotient_intt");
+    launch_intt_dif_cosets(st, ctx->tables, d_qvals, nc, log_n, qdb, s->d_q_inv_scale_br);
+    launch_quotient_chunks(st, d_qvals, d_qchunks, log_n, qdb, nc, s->d_q_wR_inv, s->d_q_chunk_scale);
+    s->clock.stage("commit_quotient");
+    NLX_RC(commit_build(ctx, d_qchunks, n, CommitInput::CoeffsBitrev, nq, log_n, d.rate_bits, cap_h, cq, d.leaf_group_cols));
+    NLX_RC(fetch(ctx, cap.data(), cq->cap, capw * 8));
+    w.u64s(cap.data(), capw);
+    ch.observe(cap.data(), capw);
+
+    // ---- StarkOpeningSet: local = columns(zeta), next = columns(g zeta), quotient(zeta) ----
+    s->clock.stage("openings");
+    uint64_t zeta[2], gzeta[2];
+    ch.ext_challenge(zeta);
+    {
+        const uint64_t g = gl::root_of_unity(log_n);
+        gzeta[0] = gl::mul(zeta[0], g);
+        gzeta[1] = gl::mul(zeta[1], g);
+    }
+    const uint32_t n_open = ncols + nq;
+    uint32_t widest = nq;
+    for (uint32_t r = 0; r < NRD; r++) widest = s->round_cols[r] > widest ? s->round_cols[r] : widest;
+    const OpeningPoints& pts = sc.points;
+    NLX_RC(sc.points.upload(scratch, zeta, gzeta, log_n));
+    // with an openings digest the vector is zero-padded to whole runs and the runs' digests follow it
+    const size_t open_words = (size_t)(n_open + ncols) * 2;
+    const size_t og = d.openings_group, og_runs = og ? (open_words + og - 1) / og : 0;
+    uint64_t* d_open = scratch.alloc_as<uint64_t>((og ? og_runs * og + 4 * og_runs : open_words) * 8);
+    uint64_t* d_eval_scratch = scratch.alloc_as<uint64_t>(eval_scratch_words(widest, log_n) * 8);
+    if (!d_open || !d_eval_scratch) return NLX_E_NOMEM;
+    {
+        for (uint32_t r = 0; r < NRD; r++) {
+            launch_eval_br(st, cr[r]->coeffs_br, n, s->round_cols[r], log_n, pts.zeta(), d_open + 2 * (size_t)col0[r],
+                           d_eval_scratch, pts.zeta_pows());
+            launch_eval_br(st, cr[r]->coeffs_br, n, s->round_cols[r], log_n, pts.gzeta(),
+                           d_open + 2 * (size_t)(n_open + col0[r]), d_eval_scratch, pts.gzeta_pows());
+        }
+        launch_eval_br(st, cq->coeffs_br, n, nq, log_n, pts.zeta(), d_open + 2 * (size_t)ncols, d_eval_scratch, pts.zeta_pows());
+        if (og) {
+            if (og_runs * og > open_words) NLX_HIP(ctx, hipMemsetAsync(d_open + open_words, 0, (og_runs * og - open_words) * 8, st));
+            launch_hash_leaves_rowmajor(st, d_open, (uint32_t)og, og_runs, d_open + og_runs * og);
         }
     }
+    std::vector<uint64_t> open(og ? og_runs * og + 4 * og_runs : open_words);
+    NLX_RC(fetch(ctx, open.data(), d_open, open.size() * 8));
+    const uint64_t* o_local = open.data();
+    const uint64_t* o_q = o_local + 2 * (size_t)ncols;
+    const uint64_t* o_next = open.data() + 2 * (size_t)n_open;
+    w.u64s(o_local, 2 * (size_t)ncols);
+    w.u64s(o_next, 2 * (size_t)ncols);
+    w.u64s(o_q, 2 * (size_t)nq);
+    // observe_openings(&openings.to_fri_openings()): zeta batch (local ++ quotient), then the g*zeta batch - every value, or
+    // (openings_group) the digest of the runs' digests the device has just made
+    if (og) {
+        uint64_t dig[4];
+        hash_no_pad_host(open.data() + og_runs * og, 4 * og_runs, dig);
+        ch.observe(dig, 4);
+    } else {
+        ch.observe(open.data(), 2 * (size_t)n_open);
+        ch.observe(o_next, 2 * (size_t)ncols);
+    }
+
+    // ---- FRI: Stark::fri_instance = [zeta: every round's columns ++ quotient], [g zeta: every round's columns] ----
+    {
+        FriProveArgs fa;
+        nlx_commit views[NLX_STARK_MAX_ORACLES];   // a batch as a commitment of its own: its columns, its tree
+        uint32_t no = 0;
+        for (uint32_t r = 0; r < NRD; r++)
+            for (uint32_t k = 0; k < cr[r]->n_trees; k++) {
+                views[no] = commit_view(cr[r].get(), k);
+                fa.oracles[no] = &views[no];
+                fa.nz[no] = views[no].n_cols;
+                no++;
+            }
+        fa.oracles[no] = cq.get();
+        fa.n_oracles = no + 1;
+        for (int i = 0; i < 2; i++) { fa.zeta[i] = zeta[i]; fa.gzeta[i] = gzeta[i]; }
+        fa.open0 = open.data();
+        fa.open1 = o_next;
+        fa.log_n = log_n; fa.rate_bits = d.rate_bits; fa.cap_height = cap_h; fa.arity_bits = d.fri_arity_bits;
+        fa.pow_bits = d.fri_pow_bits; fa.n_queries = d.fri_num_queries; fa.n_rounds = s->n_fri_rounds;
+        fa.d_coset_base = s->d_coset_base;
+        fa.d_wA_inv = s->d_wA_inv;
+        NLX_RC(fri_prove(ctx, fa, ch, w, scratch, s->clock));
+    }
+    w.usize(d.num_public_inputs);
+    w.u64s(public_inputs, d.num_public_inputs);
+    w.u64s(round_vals.data(), round_vals.size());
+    s->clock.end();
+    if (w.overflow) return ctx->fail(NLX_E_RANGE, "proof buffer too small (need %zu bytes)", nlx_stark_proof_max_bytes(s));
+    *proof_len = w.len;
     return NLX_OK;
-} NLX_CATCH(nullptr)
+}
+}  // namespace
+
+extern "C" {
 
 int32_t nlx_stark_prove_rounds(nlx_stark* s, nlx_round_fn round_fn, void* user, const uint64_t* public_inputs,
                                uint8_t* proof_out, size_t proof_cap, size_t* proof_len) NLX_TRY {
@@ -599,242 +800,9 @@ int32_t nlx_stark_prove_rounds(nlx_stark* s, nlx_round_fn round_fn, void* user, 
     for (uint32_t i = 0; i < d.num_public_inputs; i++)
         if (public_inputs[i] >= gl::P) return ctx->fail(NLX_E_RANGE, "public input %u is not canonical", i);
     (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const unsigned log_n = d.degree_bits, cap_h = d.cap_height, qdb = s->qdb;
-    const size_t n = (size_t)1 << log_n, L = n << d.rate_bits, capw = (size_t)4 << cap_h;
-    const uint32_t nc = d.num_challenges, ncols = d.n_cols, nq = s->nq, NRD = s->n_rounds;
-    int32_t rc = NLX_OK;
-    std::vector<void*> scratch;
-    auto dalloc = [&](size_t bytes) -> uint64_t* {
-        void* p = ctx->alloc(bytes);
-        if (p) scratch.push_back(p);
-        return (uint64_t*)p;
-    };
-    nlx_commit* cr[3] = {nullptr, nullptr, nullptr};
-    nlx_commit* cq = nullptr;
-    uint32_t col0[4] = {0, 0, 0, 0};
-    s->n_stages = 0;
-    s->timed = false;
-    auto stage = [&](const char* name) {
-        if (s->n_stages < NLX_MAX_STAGES) {
-            (void)hipEventRecord(s->ev[s->n_stages], st);
-            s->stage_names[s->n_stages++] = name;
-        }
-    };
     Writer w{proof_out, 0, proof_cap};
-    Challenger ch;
-    // The transcript opens with the statement - the AIR digest, then the public inputs - before any commitment: the
-    // public inputs enter the AIR linearly, so a transcript without them would let a prover choose them after alpha and
-    // zeta are known (the starky of the pinned era had that gap; plonky2's own prover observes circuit_digest and the
-    // public-input hash first, and so does this one).
-    ch.observe(s->air_digest, 4);
-    ch.observe(public_inputs, d.num_public_inputs);
-    std::vector<uint64_t> cap(capw);
-    // values readable by NLX_AIR_PUBLIC: the public inputs, then the verifier challenges in the order drawn
-    std::vector<uint64_t> values(public_inputs, public_inputs + d.num_public_inputs);
-    std::vector<uint64_t> round_vals;
-    std::vector<const uint64_t*> h_cols(ncols);
-#define CHECK(x) do { rc = (x); if (rc) goto done; } while (0)
-#define HIPCHK(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { rc = ctx->hip_fail(e__, #call); goto done; } } while (0)
-#define CHECK_ALLOC(p) do { if (!(p)) { rc = NLX_E_NOMEM; goto done; } } while (0)
-    {
-        // ---- trace commitments, one per round (prover.rs: PolynomialBatch::from_values(trace_poly_values, ..);
-        //      starkyx: one TraceWriter round per commitment, challenges drawn in between) ----
-        stage("commit_trace");
-        for (uint32_t r = 0; r < NRD; r++) {
-            const uint32_t rcols = s->round_cols[r];
-            const uint32_t n_rv = s->round_values[r];
-            uint64_t rv[64];
-            const uint64_t* tr_ptr = round_fn(user, r, values.data() + d.num_public_inputs, (uint32_t)(values.size() - d.num_public_inputs),
-                                              n_rv ? rv : nullptr);
-            if (!tr_ptr) { rc = ctx->fail(NLX_E_INVAL, "round %u: the round callback returned NULL", r); goto done; }
-            for (uint32_t k = 0; k < n_rv; k++) rv[k] %= gl::P;
-            Staged tr(ctx, tr_ptr, (size_t)rcols * n * 8, true, false);
-            CHECK(tr.status);
-            // one PolynomialBatch, or (batch_cols) ceil(rcols / batch_cols) of them: transformed together, a tree and a cap each, the
-            // caps into the transcript and the proof in batch order
-            CHECK(commit_build(ctx, tr.as<uint64_t>(), n, CommitInput::ValuesNatural, rcols, log_n, d.rate_bits, cap_h, &cr[r], d.leaf_group_cols,
-                               d.batch_cols));
-            for (uint32_t k = 0; k < cr[r]->n_trees; k++) {
-                CHECK(fetch(ctx, cap.data(), cr[r]->cap + (size_t)k * cr[r]->tree_words, capw * 8));
-                w.u64s(cap.data(), capw);
-                ch.observe(cap.data(), capw);
-            }
-            if (n_rv) {  // the round's values: into the transcript before its challenges, into the proof's tail later
-                ch.observe(rv, n_rv);
-                values.insert(values.end(), rv, rv + n_rv);
-                round_vals.insert(round_vals.end(), rv, rv + n_rv);
-            }
-            for (uint32_t k = 0; k < s->round_challenges[r]; k++) values.push_back(ch.challenge());
-            for (uint32_t c = 0; c < rcols; c++) h_cols[col0[r] + c] = cr[r]->lde + (size_t)c * L;
-            col0[r + 1] = col0[r] + rcols;
-        }
-        uint64_t alphas[2] = {0, 0};
-        for (uint32_t i = 0; i < nc; i++) alphas[i] = ch.challenge();
-
-        // ---- compute_quotient_polys ----
-        stage("quotient_eval");
-        const size_t Q = n << qdb;
-        // public inputs ++ round challenges, then each segment's alpha^(constraints after it) per challenge
-        const uint32_t n_seg = (uint32_t)s->seg_after.size();
-        const size_t n_values = values.size();
-        for (uint32_t sg = 0; sg < n_seg; sg++)
-            for (uint32_t i = 0; i < 2; i++) values.push_back(gl::pow(alphas[i], s->seg_after[sg]));
-        uint64_t* d_pis = dalloc(values.size() * 8);
-        const uint64_t** d_cols = (const uint64_t**)dalloc((size_t)ncols * 8);
-        uint64_t* d_qvals = dalloc((size_t)nc * Q * 8);
-        uint64_t* d_qchunks = dalloc((size_t)nc * Q * 8);
-        uint64_t* d_part = n_seg > 1 ? dalloc((size_t)n_seg * nc * Q * 8) : nullptr;
-        CHECK_ALLOC(d_pis && d_cols && d_qvals && d_qchunks && (n_seg == 1 || d_part));
-        HIPCHK(hipMemcpyAsync(d_pis, values.data(), values.size() * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_cols, h_cols.data(), (size_t)ncols * 8, hipMemcpyHostToDevice, st));
-        {
-            AirParams ap{};
-            ap.cols = d_cols; ap.program = s->d_program; ap.pis = d_pis;
-            ap.coset_base = s->d_q_coset_base; ap.zh_inv = s->d_q_zh_inv; ap.l_inv = s->d_l_inv;
-            ap.periodic = s->d_periodic; ap.period_bits = d.period_bits;
-            ap.w_n_table = ctx->tables.fwd[log_n];
-            ap.out = d_qvals;
-            ap.alphas[0] = alphas[0]; ap.alphas[1] = alphas[1];
-            ap.g_inv = gl::inv(gl::root_of_unity(log_n));
-            ap.log_n = log_n; ap.rate_bits = d.rate_bits; ap.qdb = qdb; ap.n_words = d.n_words; ap.nc = nc;
-            ap.n_regs = s->n_regs; ap.n_pis = d.num_public_inputs;
-            ap.seg = s->d_seg; ap.seg_mul = d_pis + n_values; ap.part = d_part; ap.n_seg = n_seg;
-            // one wave per block: the LDS register file (n_regs x 64 lanes x 8 B) is the occupancy limiter, and
-            // single-wave blocks pack the 160 KB of a CU at the finest granularity
-            unsigned bs = 64;
-            while (bs > n) bs >>= 1;
-            ctx->begin_kernel("air_quotient", 8.0 * Q * (2.0 * ncols + nc));
-            if (s->gen) s->gen->launch(st, (unsigned)(Q / AIRGEN_BLOCK), n_seg, ap);   // every segment of every point, straight-line code
-            for (size_t gi = 0; !s->gen && gi < s->seg_group.size(); gi++) {
-                const uint32_t first = s->seg_group[gi], last = gi + 1 < s->seg_group.size() ? s->seg_group[gi + 1] : n_seg;
-                AirParams gp = ap;
-                gp.seg = ap.seg + 2 * first;
-                gp.seg_mul = ap.seg_mul + 2 * first;
-                gp.part = n_seg > 1 ? ap.part + (size_t)first * nc * Q : nullptr;
-                const size_t lds = (size_t)bs * s->seg_regs[last - 1] * 8;  // the group's largest register file
-                hipLaunchKernelGGL(k_air_quotient, dim3((unsigned)(Q / bs), last - first), dim3(bs), lds, st, gp);
-            }
-            if (n_seg > 1)
-                hipLaunchKernelGGL(k_air_combine, dim3((unsigned)((nc * Q + 255) / 256)), dim3(256), 0, st, d_part, s->d_q_zh_inv,
-                                   d_qvals, n_seg, nc, log_n, log_n + qdb);
-            ctx->end_kernel();
-        }
-        stage("quotient_intt");
-        launch_intt_dif_cosets(st, ctx->tables, d_qvals, nc, log_n, qdb, s->d_q_inv_scale_br);
-        launch_quotient_chunks(st, d_qvals, d_qchunks, log_n, qdb, nc, s->d_q_wR_inv, s->d_q_chunk_scale);
-        stage("commit_quotient");
-        CHECK(commit_build(ctx, d_qchunks, n, CommitInput::CoeffsBitrev, nq, log_n, d.rate_bits, cap_h, &cq, d.leaf_group_cols));
-        CHECK(fetch(ctx, cap.data(), cq->cap, capw * 8));
-        w.u64s(cap.data(), capw);
-        ch.observe(cap.data(), capw);
-
-        // ---- StarkOpeningSet: local = columns(zeta), next = columns(g zeta), quotient(zeta) ----
-        stage("openings");
-        uint64_t zeta[2], gzeta[2];
-        ch.ext_challenge(zeta);
-        {
-            const uint64_t g = gl::root_of_unity(log_n);
-            gzeta[0] = gl::mul(zeta[0], g);
-            gzeta[1] = gl::mul(zeta[1], g);
-        }
-        const uint32_t n_open = ncols + nq;
-        uint32_t widest = nq;
-        for (uint32_t r = 0; r < NRD; r++) widest = s->round_cols[r] > widest ? s->round_cols[r] : widest;
-        uint64_t* d_points = dalloc(2048);
-        // with an openings digest the vector is zero-padded to whole runs and the runs' digests follow it
-        const size_t open_words = (size_t)(n_open + ncols) * 2;
-        const size_t og = d.openings_group, og_runs = og ? (open_words + og - 1) / og : 0;
-        uint64_t* d_open = dalloc((og ? og_runs * og + 4 * og_runs : open_words) * 8);
-        uint64_t* d_eval_scratch = dalloc(eval_scratch_words(widest, log_n) * 8);
-        CHECK_ALLOC(d_points && d_open && d_eval_scratch);
-        {
-            uint64_t pts[4 + 2 * 2 * 32] = {zeta[0], zeta[1], gzeta[0], gzeta[1]};
-            gl::Ext za{zeta[0], zeta[1]}, zb{gzeta[0], gzeta[1]};
-            for (unsigned k = 0; k < 32; k++) {
-                pts[4 + 2 * k] = za.a; pts[4 + 2 * k + 1] = za.b;
-                pts[4 + 64 + 2 * k] = zb.a; pts[4 + 64 + 2 * k + 1] = zb.b;
-                if (k + 1 < log_n) { za = gl::mul(za, za); zb = gl::mul(zb, zb); }
-            }
-            HIPCHK(hipMemcpyAsync(d_points, pts, sizeof pts, hipMemcpyHostToDevice, st));
-            for (uint32_t r = 0; r < NRD; r++) {
-                launch_eval_br(st, cr[r]->coeffs_br, n, s->round_cols[r], log_n, d_points, d_open + 2 * (size_t)col0[r],
-                               d_eval_scratch, d_points + 4);
-                launch_eval_br(st, cr[r]->coeffs_br, n, s->round_cols[r], log_n, d_points + 2,
-                               d_open + 2 * (size_t)(n_open + col0[r]), d_eval_scratch, d_points + 4 + 64);
-            }
-            launch_eval_br(st, cq->coeffs_br, n, nq, log_n, d_points, d_open + 2 * (size_t)ncols, d_eval_scratch, d_points + 4);
-            if (og) {
-                if (og_runs * og > open_words) HIPCHK(hipMemsetAsync(d_open + open_words, 0, (og_runs * og - open_words) * 8, st));
-                launch_hash_leaves_rowmajor(st, d_open, (uint32_t)og, og_runs, d_open + og_runs * og);
-            }
-        }
-        std::vector<uint64_t> open(og ? og_runs * og + 4 * og_runs : open_words);
-        CHECK(fetch(ctx, open.data(), d_open, open.size() * 8));
-        const uint64_t* o_local = open.data();
-        const uint64_t* o_q = o_local + 2 * (size_t)ncols;
-        const uint64_t* o_next = open.data() + 2 * (size_t)n_open;
-        w.u64s(o_local, 2 * (size_t)ncols);
-        w.u64s(o_next, 2 * (size_t)ncols);
-        w.u64s(o_q, 2 * (size_t)nq);
-        // observe_openings(&openings.to_fri_openings()): zeta batch (local ++ quotient), then the g*zeta batch - every value, or
-        // (openings_group) the digest of the runs' digests the device has just made
-        if (og) {
-            uint64_t dig[4];
-            hash_no_pad_host(open.data() + og_runs * og, 4 * og_runs, dig);
-            ch.observe(dig, 4);
-        } else {
-            ch.observe(open.data(), 2 * (size_t)n_open);
-            ch.observe(o_next, 2 * (size_t)ncols);
-        }
-
-        // ---- FRI: Stark::fri_instance = [zeta: every round's columns ++ quotient], [g zeta: every round's columns] ----
-        {
-            FriProveArgs fa;
-            nlx_commit views[NLX_STARK_MAX_ORACLES];   // a batch as a commitment of its own: its columns, its tree
-            uint32_t no = 0;
-            for (uint32_t r = 0; r < NRD; r++)
-                for (uint32_t k = 0; k < cr[r]->n_trees; k++) {
-                    views[no] = commit_view(cr[r], k);
-                    fa.oracles[no] = &views[no];
-                    fa.nz[no] = views[no].n_cols;
-                    no++;
-                }
-            fa.oracles[no] = cq;
-            fa.n_oracles = no + 1;
-            for (int i = 0; i < 2; i++) { fa.zeta[i] = zeta[i]; fa.gzeta[i] = gzeta[i]; }
-            fa.open0 = open.data();
-            fa.open1 = o_next;
-            fa.log_n = log_n; fa.rate_bits = d.rate_bits; fa.cap_height = cap_h; fa.arity_bits = d.fri_arity_bits;
-            fa.pow_bits = d.fri_pow_bits; fa.n_queries = d.fri_num_queries; fa.n_rounds = s->n_fri_rounds;
-            fa.d_coset_base = s->d_coset_base;
-            fa.d_wA_inv = s->d_wA_inv;
-            CHECK(fri_prove(ctx, fa, ch, w, scratch, stage));
-        }
-        w.usize(d.num_public_inputs);
-        w.u64s(public_inputs, d.num_public_inputs);
-        w.u64s(round_vals.data(), round_vals.size());
-        stage("end");
-        s->n_stages--;
-        s->timed = true;
-        if (w.overflow) { rc = ctx->fail(NLX_E_RANGE, "proof buffer too small (need %zu bytes)", nlx_stark_proof_max_bytes(s)); goto done; }
-        *proof_len = w.len;
-    }
-done:
-    {
-        hipError_t e = hipStreamSynchronize(st);
-        if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
-        hipError_t le = hipGetLastError();
-        if (!rc && le != hipSuccess) rc = ctx->hip_fail(le, "kernel launch");
-    }
-    for (void* p : scratch) ctx->release(p);
-    for (uint32_t r = 0; r < 3; r++)
-        if (cr[r]) nlx_commit_destroy(cr[r]);
-    if (cq) nlx_commit_destroy(cq);
-#undef CHECK
-#undef HIPCHK
-#undef CHECK_ALLOC
-    return rc;
+    StarkCall sc(ctx);
+    return sc.scratch.finish(stark_stages(s, sc, round_fn, user, public_inputs, w, proof_len));
 } NLX_CATCH(nullptr)
 
 static const uint64_t* single_round_fn(void* user, uint32_t round, const uint64_t*, uint32_t, uint64_t*) {
@@ -850,35 +818,9 @@ int32_t nlx_stark_prove(nlx_stark* s, const uint64_t* trace, const uint64_t* pub
 } NLX_CATCH(nullptr)
 
 int32_t nlx_stark_batch_prove(nlx_stark* const* workers, uint32_t n_workers, nlx_prove_job* jobs, size_t n_jobs) NLX_TRY {
-    if (!workers || n_workers == 0 || (!jobs && n_jobs)) return NLX_E_INVAL;
-    for (uint32_t w = 0; w < n_workers; w++) {
-        if (!workers[w]) return NLX_E_INVAL;
-        for (uint32_t v = 0; v < w; v++)
-            if (workers[v]->ctx == workers[w]->ctx)
-                return workers[w]->ctx->fail(NLX_E_INVAL, "nlx_stark_batch_prove: workers must use distinct contexts");
-    }
-    std::atomic<size_t> next{0};
-    auto run = [&](nlx_stark* s) {
-        (void)hipSetDevice(s->ctx->device);
-        for (;;) {
-            const size_t j = next.fetch_add(1);
-            if (j >= n_jobs) return;
-            nlx_prove_job& job = jobs[j];
-            job.proof_len = 0;
-            job.status = nlx_stark_prove(s, job.wires, job.public_inputs, job.proof_out, job.proof_cap, &job.proof_len);
-        }
-    };
-    if (n_workers == 1) {
-        run(workers[0]);
-    } else {
-        std::vector<std::thread> threads;
-        threads.reserve(n_workers);
-        for (uint32_t w = 0; w < n_workers; w++) threads.emplace_back(run, workers[w]);
-        for (auto& t : threads) t.join();
-    }
-    for (size_t j = 0; j < n_jobs; j++)
-        if (jobs[j].status != NLX_OK) return jobs[j].status;
-    return NLX_OK;
+    return batch_prove("nlx_stark_batch_prove", workers, n_workers, jobs, n_jobs, [](nlx_stark* s, nlx_prove_job& job) {
+        return nlx_stark_prove(s, job.wires, job.public_inputs, job.proof_out, job.proof_cap, &job.proof_len);
+    });
 } NLX_CATCH(nullptr)
 
 }  // extern "C"

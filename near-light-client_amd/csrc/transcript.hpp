@@ -137,12 +137,14 @@ inline int32_t ensure_pinned(nlx_ctx* ctx, size_t bytes) {
     return NLX_OK;
 }
 
-// device -> host through the pinned staging buffer, synchronous
-inline int32_t fetch(nlx_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes) {
+// device -> host through the pinned staging buffer, synchronous.  `last`: this read ends the call that owns that Scratch -
+// its synchronise is last->drain(), so the Scratch's destructor has nothing left to wait for.
+inline int32_t fetch(nlx_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes, Scratch* last = nullptr) {
     int32_t rc = ensure_pinned(ctx, bytes < (1u << 20) ? (1u << 20) : bytes);
     if (rc) return rc;
     NLX_HIP(ctx, hipMemcpyAsync(ctx->pinned, dev_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const hipError_t e = last ? last->drain() : hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return ctx->hip_fail(e, "hipStreamSynchronize(ctx->stream)");
     memcpy(host_dst, ctx->pinned, bytes);
     return NLX_OK;
 }
