@@ -288,7 +288,8 @@ int32_t nlx_bn254_kzg_open(nlx_ctx* ctx, const uint64_t* coeffs, uint64_t m, con
  *                       x_wire / x_coeff_id: one wire id and one index into `coeffs` per term - and the coefficient table
  *                       (n_coeffs x 4 words, fr.Element Montgomery).  Without it nlx_bn254_r1cs_eval and a prove call that
  *                       does not bring a, b, c return NLX_E_INVAL.
- *   n_commitments       Bsb22 / Pedersen commitments (Proof.Commitments, CommitmentPok): must be 0, else NLX_E_UNSUPPORTED.
+ *   n_commitments       Bsb22 / Pedersen commitments (Proof.Commitments, CommitmentPok): must be 0 here, else NLX_E_UNSUPPORTED -
+ *                       a key with commitments brings its Pedersen bases through nlx_bn254_groth16_key_create_committed.
  * Creation uploads once, converts every query to the bucket kernels' form once (the three wire queries and G1.K expanded to the
  * wires' index space, the point at infinity at masked and public positions, so that one set of sorted digits serves all four),
  * and classifies the R1CS: coefficients equal to 1 or -1 are marked (added or subtracted, no product), rows of more than 64
@@ -316,8 +317,33 @@ typedef struct {
 } nlx_bn254_groth16_key_desc;
 int32_t nlx_bn254_groth16_key_create(nlx_ctx* ctx, const nlx_bn254_groth16_key_desc* desc, nlx_bn254_groth16_key** out);
 void nlx_bn254_groth16_key_destroy(nlx_bn254_groth16_key* key);
-/* out[0] = bytes the key keeps resident in HBM, out[1] = R1CS rows run one per lane, out[2] = rows run one per wave, out[3] =
- * terms of the three matrices, out[4] = terms whose coefficient is 1 or -1, out[5] = the row-length threshold; the rest 0. */
+/* A key with k = 1 .. NLX_BN254_GROTH16_MAX_COMMITMENTS Bsb22 / Pedersen commitments (gnark's ProvingKey.CommitmentKeys and the
+ * R1CS's CommitmentInfo; rules recalled and unpinned like the rest: tools/groth16_commit_model.py).  Every
+ * pointer may be host or device.
+ *   n_commitments       k; desc->n_commitments must equal it
+ *   n_private           k counts: |PrivateCommitted_j|; M = their sum
+ *   private_wires       the k sets concatenated, M wire ids: private wires, ascending inside a set, the sets pairwise disjoint
+ *   basis, basis_exp_sigma   the k Pedersen keys' Basis and BasisExpSigma concatenated, M G1Affine points each (8 words,
+ *                       Montgomery; (0, 0) = the point at infinity is allowed)
+ *   commitment_wires    k wire ids (CommitmentIndex_j): private, not committed, distinct
+ * desc->g1_k then holds n_wires - n_public - M - k points: the private wires that are neither committed nor a commitment's, in
+ * ascending order.  NLX_E_RANGE: k outside 1 .. 8, desc->n_commitments != k, an id below n_public or >= n_wires, ids that do not
+ * ascend inside a set, sets that overlap, a commitment wire that is committed or listed twice, a G1.K count that disagrees -
+ * and everything nlx_bn254_groth16_key_create refuses.  The two bases are converted once and stay compact (M points each) next
+ * to the wire ids; the committed and the commitment wires hold the point at infinity in the expanded G1.K. */
+#define NLX_BN254_GROTH16_MAX_COMMITMENTS 8
+typedef struct {
+    uint32_t n_commitments;
+    const uint64_t* n_private;
+    const uint32_t* private_wires;
+    const uint64_t *basis, *basis_exp_sigma;
+    const uint32_t* commitment_wires;
+} nlx_bn254_groth16_commit_desc;
+int32_t nlx_bn254_groth16_key_create_committed(nlx_ctx* ctx, const nlx_bn254_groth16_key_desc* desc,
+                                               const nlx_bn254_groth16_commit_desc* commit_desc, nlx_bn254_groth16_key** out);
+/* out[0] = bytes the key keeps resident in HBM (the Pedersen bases and the committed wire ids included), out[1] = R1CS rows run
+ * one per lane, out[2] = rows run one per wave, out[3] = terms of the three matrices, out[4] = terms whose coefficient is 1 or
+ * -1, out[5] = the row-length threshold, out[6] = M, the committed wires, out[7] = k, the commitments (both 0 on a key without). */
 #define NLX_BN254_GROTH16_KEY_INFO_WORDS 8
 int32_t nlx_bn254_groth16_key_info(const nlx_bn254_groth16_key* key, uint64_t out[NLX_BN254_GROTH16_KEY_INFO_WORDS]);
 /* a = A w, b = B w, c = C w: three sparse matrix-vector products over Fr.  witness: n_wires x 4 words (Montgomery), host or
@@ -332,10 +358,31 @@ int32_t nlx_bn254_r1cs_eval(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, cons
  * domain generator), the four MSMs over the wire vector on one digit decomposition and one set of sorted indices, G1.Z over h,
  * and on the host Ar = sum w_i A_i + alpha + r delta, Bs = sum w_i B_i + beta + s delta (G2; Bs1 the same in G1),
  * Krs = sum_private w_i K_i + sum_(i < n-1) h_i Z_i + s Ar + r Bs1 - r s delta.
- * ar_out, krs_out: G1Affine words; bs_out: G2Affine words.  Kernel-timing name "bn254_groth16_msms". */
+ * ar_out, krs_out: G1Affine words; bs_out: G2Affine words.  Kernel-timing name "bn254_groth16_msms".  A key with commitments:
+ * NLX_E_INVAL (its proofs come from nlx_bn254_groth16_prove_committed). */
 int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, const uint64_t* witness, const uint64_t* a,
                                 const uint64_t* b, const uint64_t* c, const uint64_t r[4], const uint64_t s[4], uint64_t ar_out[8],
                                 uint64_t bs_out[16], uint64_t krs_out[8]);
+/* C_j = sum_i w[PrivateCommitted_j[i]] Basis_j[i] of commitment j < k: the call a solver's hint makes while the witness is still
+ * being solved - of `witness` (n_wires x 4 words, Montgomery, host or device) only the wires of PrivateCommitted_j are read.
+ * out: G1Affine words, (0, 0) for the point at infinity (an empty set, or values that are all zero).  The hash that turns C_j
+ * into the commitment wire's value is the caller's (no SHA-256 in this library).  NLX_E_INVAL on a key without commitments,
+ * NLX_E_RANGE for j >= k.  Kernel-timing name "bn254_groth16_commit", units committed wires. */
+int32_t nlx_bn254_groth16_commit(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, uint32_t j, const uint64_t* witness, uint64_t out[8]);
+/* One proof on a key with commitments: everything nlx_bn254_groth16_prove does (the same guards first, the same a, b, c, r, s;
+ * Krs sums G1.K over the private wires that are left: the prover does not add C_j to it), and all k commitments recomputed from
+ * the finished witness with their proof of knowledge (pedersen.BatchProve):
+ *   commitments_out     k x 8 words: C_j, G1Affine
+ *   pok_out             Pok = sum_j rho^j sum_i w[PrivateCommitted_j[i]] BasisExpSigma_j[i]: one gather of the M committed values
+ *                       into a plain and a rho^j-scaled compact vector, k MSMs over slices of the first, ONE over the second
+ *   rho                 the folding challenge, host, four Montgomery words, below r (else NLX_E_RANGE); the caller's hash of
+ *                       the k commitment-wire values; not used when k = 1
+ * The library does not check that the witness's commitment wires hold the challenges of the C_j it returns: the caller does (the
+ * Python binding's prove_committed).  A key without commitments: NLX_E_INVAL.  No output is written before the end. */
+int32_t nlx_bn254_groth16_prove_committed(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, const uint64_t* witness, const uint64_t* a,
+                                          const uint64_t* b, const uint64_t* c, const uint64_t r[4], const uint64_t s[4],
+                                          const uint64_t rho[4], uint64_t ar_out[8], uint64_t bs_out[16], uint64_t krs_out[8],
+                                          uint64_t* commitments_out, uint64_t pok_out[8]);
 
 /* ---- a3: plonky2::fri::oracle::PolynomialBatch::{from_values, from_coeffs} ----
  * values / coeffs: n_cols x 2^log_n column-major, natural order.  The coset shift is the

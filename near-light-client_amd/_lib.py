@@ -99,6 +99,9 @@ SIGNATURES = {
     "nlx_bn254_groth16_key_info": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_bn254_r1cs_eval": (ctypes.c_int32, [ctypes.c_void_p] * 6),
     "nlx_bn254_groth16_prove": (ctypes.c_int32, [ctypes.c_void_p] * 11),
+    "nlx_bn254_groth16_key_create_committed": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
+    "nlx_bn254_groth16_commit": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_bn254_groth16_prove_committed": (ctypes.c_int32, [ctypes.c_void_p] * 14),
     "nlx_commit_from_values": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, c_void_pp]),
     "nlx_commit_from_coeffs": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,

@@ -5,7 +5,12 @@ gnark-produced bytes unpinned: DESIGN.md section 19).
   ProvingKey(ctx, ...)   nlx_bn254_groth16_key_create: gnark's key as it lies in memory, uploaded and converted once
   r1cs_eval(pk, w)       nlx_bn254_r1cs_eval: A w, B w, C w
   prove(pk, w, r, s)     nlx_bn254_groth16_prove: the proof's three points (G1Affine / G2Affine / G1Affine words)
-  proof_bytes(...)       gnark's Proof.WriteTo without commitments, 164 bytes; g1_compress / g2_compress: gnark-crypto's Bytes()
+  proof_bytes(...)       gnark's Proof.WriteTo, 164 + 32 k bytes; g1_compress / g2_compress: gnark-crypto's Bytes()
+Keys with k Bsb22 / Pedersen commitments (rules: tools/groth16_commit_model.py):
+  ProvingKey(ctx, ..., commitments=[...])   nlx_bn254_groth16_key_create_committed: the Pedersen bases resident next to the key
+  commit(pk, j, w)                          nlx_bn254_groth16_commit: C_j, the call a solver's hint makes
+  commitment_challenge(pk, j, point, w)     the value of commitment j's wire: fr.Hash(C_j.Marshal() || hashed values)
+  prove_committed(pk, w, r, s)              nlx_bn254_groth16_prove_committed: (ar, bs, krs, [C_j], pok)
 
 Every element is an fr.Element / fp.Element as it lies in memory (four little-endian words, Montgomery); arrays are numpy uint64
 or device tensors.  Parity: device bytes equal the big-integer model's (tools/groth16_model.py) and its trapdoor verifier accepts
@@ -16,12 +21,17 @@ import secrets
 import numpy as np
 
 from . import batch as B
-from ._lib import dll, ptr
+from ._lib import NlxError, dll, ptr
+from .bn254_plonk import fr_bytes, g1_marshal, hash_to_field
 
 R, Q = B.BN254_R, B.BN254_Q
 _MONT = (1 << 256) % R
 NLX_BN254_MONTGOMERY = 1
 KEY_INFO_WORDS = 8
+MAX_COMMITMENTS = 8
+COMMITMENT_DST = b"bsb22-commitment"     # the hint's hash (gnark constraint/commitment.go)
+FOLD_DST = b"G16-BSB22"                  # pedersen.BatchProve's folding challenge (gnark backend/groth16/bn254/prove.go)
+NLX_E_INVAL = -1
 
 
 class _KeyDesc(ctypes.Structure):
@@ -33,6 +43,12 @@ class _KeyDesc(ctypes.Structure):
                                                   "a_row_ptr", "b_row_ptr", "c_row_ptr", "a_wire", "b_wire", "c_wire",
                                                   "a_coeff_id", "b_coeff_id", "c_coeff_id", "coeffs")]
                 + [("n_coeffs", ctypes.c_uint64), ("n_commitments", ctypes.c_uint32)])
+
+
+class _CommitDesc(ctypes.Structure):
+    """nlx_bn254_groth16_commit_desc (include/nlx.h)"""
+    _fields_ = [("n_commitments", ctypes.c_uint32), ("n_private", ctypes.c_void_p), ("private_wires", ctypes.c_void_p),
+                ("basis", ctypes.c_void_p), ("basis_exp_sigma", ctypes.c_void_p), ("commitment_wires", ctypes.c_void_p)]
 
 
 def fr_words(x):
@@ -90,11 +106,20 @@ class ProvingKey:
     infinity, as gnark keeps them; infinity_a, infinity_b: one byte (or bool) per wire, non-zero = filtered out; g1_alpha,
     g1_beta, g1_delta (8 words), g2_beta, g2_delta (16 words).  r1cs (optional): {"A": (row_ptr, wire, coeff_id), "B": ...,
     "C": ..., "coeffs": (n_coeffs, 4) fr.Element words} with row_ptr uint64, wire and coeff_id uint32.  Arrays are numpy or device
-    tensors.  n_commitments: gnark's Bsb22 / Pedersen commitments, unsupported (anything but 0 raises)."""
+    tensors.  commitments (optional): gnark's Bsb22 / Pedersen commitments, one dict each - "private": PrivateCommitted (wire
+    ids, ascending), "public": PublicAndCommitmentCommitted (wire ids; kept on the host, for the hash), "wire": CommitmentIndex,
+    "basis" / "basis_exp_sigma": the Pedersen key's points, (len(private), 8) words, numpy - and g1_k then holds the private wires
+    that are neither committed nor a commitment's.  n_commitments without `commitments`: anything but 0 raises (the bases have
+    nowhere to go)."""
 
     def __init__(self, ctx, log_n, n_wires, n_public, n_constraints, g1_a, g1_b, g2_b, g1_k, g1_z, infinity_a, infinity_b,
-                 g1_alpha, g1_beta, g1_delta, g2_beta, g2_delta, r1cs=None, n_commitments=0, flags=NLX_BN254_MONTGOMERY):
+                 g1_alpha, g1_beta, g1_delta, g2_beta, g2_delta, r1cs=None, n_commitments=None, flags=NLX_BN254_MONTGOMERY,
+                 commitments=None):
         self.ctx, self.handle = ctx, None
+        self.commitments = [] if commitments is None else [
+            {"private": [int(i) for i in c["private"]], "public": [int(i) for i in c["public"]], "wire": int(c["wire"])} for c in commitments]
+        if n_commitments is None:
+            n_commitments = len(self.commitments)
         self.log_n, self.n_wires, self.n_public, self.n_constraints = int(log_n), int(n_wires), int(n_public), int(n_constraints)
         d = _KeyDesc()
         d.log_n, d.flags, d.n_wires, d.n_public, d.n_constraints = self.log_n, int(flags), self.n_wires, self.n_public, self.n_constraints
@@ -131,7 +156,24 @@ class ProvingKey:
             keep.append(k)
             d.coeffs, d.n_coeffs = p, rows
         h = ctypes.c_void_p()
-        ctx.check(dll.nlx_bn254_groth16_key_create(ctx.handle, ctypes.byref(d), ctypes.byref(h)))
+        if commitments is None:
+            ctx.check(dll.nlx_bn254_groth16_key_create(ctx.handle, ctypes.byref(d), ctypes.byref(h)))
+        else:
+            cd = _CommitDesc()
+            cd.n_commitments = len(commitments)
+            counts = np.array([len(c["private"]) for c in self.commitments], dtype=np.uint64)
+            ids = np.array([i for c in self.commitments for i in c["private"]], dtype=np.uint32)
+            wires = np.array([c["wire"] for c in self.commitments], dtype=np.uint32)
+            bases = []
+            for name in ("basis", "basis_exp_sigma"):
+                parts = [np.ascontiguousarray(c[name], dtype=np.uint64).reshape(-1, 8) for c in commitments]
+                if [len(p) for p in parts] != [len(c["private"]) for c in self.commitments]:
+                    raise ValueError("%s holds one point per committed wire" % name)
+                bases.append(np.concatenate(parts) if parts else np.zeros((0, 8), dtype=np.uint64))
+            keep += [counts, ids, wires] + bases
+            cd.n_private, cd.private_wires, cd.commitment_wires = counts.ctypes.data, ids.ctypes.data, wires.ctypes.data
+            cd.basis, cd.basis_exp_sigma = bases[0].ctypes.data, bases[1].ctypes.data
+            ctx.check(dll.nlx_bn254_groth16_key_create_committed(ctx.handle, ctypes.byref(d), ctypes.byref(cd), ctypes.byref(h)))
         self.handle = h
         self.has_r1cs = r1cs is not None
         ctx._adopt(self)
@@ -140,7 +182,7 @@ class ProvingKey:
         """what the key reports: resident bytes, and the SpMV's row split"""
         out = np.zeros(KEY_INFO_WORDS, dtype=np.uint64)
         self.ctx.check(dll.nlx_bn254_groth16_key_info(self.handle, out.ctypes.data))
-        names = ("resident_bytes", "lane_rows", "wave_rows", "terms", "unit_terms", "long_row_threshold")
+        names = ("resident_bytes", "lane_rows", "wave_rows", "terms", "unit_terms", "long_row_threshold", "committed_wires", "commitments")
         return {k: int(out[i]) for i, k in enumerate(names)}
 
     def close(self):
@@ -225,7 +267,73 @@ def g2_compress(words):
     return bytes(b)
 
 
-def proof_bytes(ar, bs, krs):
-    """gnark's Proof.WriteTo without commitments: Ar, Bs, Krs compressed, the empty Commitments slice (uint32 0, big-endian) and
-    CommitmentPok (a compressed point at infinity) - 164 bytes"""
-    return g1_compress(ar) + g2_compress(bs) + g1_compress(krs) + (0).to_bytes(4, "big") + bytes([0x40]) + bytes(31)
+def proof_bytes(ar, bs, krs, commitments=(), pok=None):
+    """gnark's Proof.WriteTo: Ar, Bs, Krs compressed, the Commitments slice (uint32 k, big-endian, then k compressed points) and
+    CommitmentPok (compressed; the point at infinity without commitments) - 164 + 32 k bytes"""
+    return (g1_compress(ar) + g2_compress(bs) + g1_compress(krs) + len(commitments).to_bytes(4, "big")
+            + b"".join(g1_compress(c) for c in commitments) + (bytes([0x40]) + bytes(31) if pok is None else g1_compress(pok)))
+
+
+# ---- keys with Bsb22 / Pedersen commitments ----
+def _witness_values(witness, ids):
+    """the integers of a few wires of a witness (numpy or a device tensor)"""
+    if not ids:
+        return []
+    if hasattr(witness, "data_ptr"):
+        import torch
+        rows = witness[torch.as_tensor(ids, device=witness.device)].cpu().numpy().view(np.uint64)
+    else:
+        rows = np.asarray(witness, dtype=np.uint64)[ids]
+    return fr_unpack(rows)
+
+
+def commit(pk, j, witness):
+    """C_j = sum_i w[PrivateCommitted_j[i]] Basis_j[i] as 8 G1Affine words - what a solver's hint computes while it solves: only
+    the wires of PrivateCommitted_j need to be filled."""
+    _, w_ptr, rows = _buf(witness, np.uint64, 4)
+    if rows != pk.n_wires:
+        raise ValueError("the witness has %d rows, the key %d wires" % (rows, pk.n_wires))
+    out = np.zeros(8, dtype=np.uint64)
+    pk.ctx.check(dll.nlx_bn254_groth16_commit(pk.ctx.handle, pk.handle, int(j), w_ptr, ptr(out)))
+    return out
+
+
+def commitment_challenge(pk, j, point, witness):
+    """the value commitment j's wire must hold: fr.Hash(C_j.Marshal() || the PublicAndCommitmentCommitted_j values, 32 bytes
+    big-endian each, "bsb22-commitment", 1)[0].  point: C_j's words; of the witness only those wires are read."""
+    hashed = _witness_values(witness, pk.commitments[j]["public"])
+    return hash_to_field(g1_marshal(point) + b"".join(fr_bytes(v) for v in hashed), COMMITMENT_DST)
+
+
+def prove_committed(pk, witness, r=None, s=None, abc=None):
+    """One proof on a key with commitments: (ar, bs, krs, [C_j], pok).  r, s, abc as for prove().  The folding challenge rho is
+    fr.Hash(the k commitment-wire values, "G16-BSB22"); every C_j is recomputed from the finished witness, and the value of its
+    wire is checked against the challenge the returned C_j gives: NlxError (NLX_E_INVAL, naming the commitment) if not."""
+    r = secrets.randbelow(R) if r is None else int(r)
+    s = secrets.randbelow(R) if s is None else int(s)
+    if not (0 <= r < R and 0 <= s < R):
+        raise ValueError("r and s must be below the group order")
+    wk, w_ptr, rows = _buf(witness, np.uint64, 4)
+    if rows != pk.n_wires:
+        raise ValueError("the witness has %d rows, the key %d wires" % (rows, pk.n_wires))
+    keep, ptrs = [], [None, None, None]
+    if abc is not None:
+        for i, v in enumerate(abc):
+            k_, p, rows = _buf(v, np.uint64, 4)
+            if rows != 1 << pk.log_n:
+                raise ValueError("a, b, c hold 2^log_n rows")
+            keep.append(k_)
+            ptrs[i] = p
+    k = len(pk.commitments)
+    wire_values = _witness_values(wk, [c["wire"] for c in pk.commitments])
+    rho = hash_to_field(b"".join(fr_bytes(v) for v in wire_values), FOLD_DST)
+    rw, sw, rhow = fr_words(r), fr_words(s), fr_words(rho)
+    ar, bs, krs = np.zeros(8, dtype=np.uint64), np.zeros(16, dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+    cs, pok = np.zeros((max(k, 1), 8), dtype=np.uint64), np.zeros(8, dtype=np.uint64)
+    pk.ctx.check(dll.nlx_bn254_groth16_prove_committed(pk.ctx.handle, pk.handle, w_ptr, ptrs[0], ptrs[1], ptrs[2], ptr(rw), ptr(sw), ptr(rhow),
+                                                       ptr(ar), ptr(bs), ptr(krs), ptr(cs), ptr(pok)))
+    for j in range(k):
+        if commitment_challenge(pk, j, cs[j], wk) != wire_values[j]:
+            raise NlxError(NLX_E_INVAL, "commitment %d: wire %d does not hold the challenge of the witness's own commitment"
+                           % (j, pk.commitments[j]["wire"]))
+    return ar, bs, krs, [cs[j] for j in range(k)], pok

@@ -15,6 +15,12 @@
 // The SpMV: one lane per row for rows of at most R1CS_LONG_ROW terms, one wave per row above that (partial sums joined by
 // shuffles); coefficients equal to 1 or -1 are marked when the key is built and cost an addition or a subtraction.  Fr in
 // Montgomery form on bn254_fp.hpp's eight 32-bit limbs; the witness gather (32 bytes per term) is the random-access stream.
+//
+// Keys with Bsb22 / Pedersen commitments (rules: tools/groth16_commit_model.py): the committed wires and
+// the commitment wires hold the point at infinity in the expanded G1.K, so Krs needs nothing new; the two Pedersen bases stay
+// compact (M points each, concatenated over the k commitments) next to the committed wire ids.  k_g16_gather_scale gathers the
+// M committed values once per proof into a plain and a rho^j-scaled compact vector: C_j is an MSM over a slice of the first
+// and Basis, Pok ONE MSM over the second and BasisExpSigma.
 #include <cstring>
 #include <vector>
 #include "bn254_fp.hpp"
@@ -102,6 +108,33 @@ __global__ __launch_bounds__(256) void k_g16_check(const uint64_t* __restrict__ 
     if (bad) atomicMin(first_bad, (uint32_t)i);
 }
 
+// The committed values, compact: lane t < m loads its wire id, then w[id] (the random 32-byte stream: two 16-byte loads), and
+// stores it to plain[t] and, times rho^j, to scaled[t] (NULL: not wanted).  j = the number of segment ends at or below t - an
+// empty set repeats an end; ends past the last commitment equal m.  rho^0 = 1: a plain copy.
+struct CommitSegments {
+    uint32_t end[NLX_BN254_GROTH16_MAX_COMMITMENTS];
+    Fr rho_pow[NLX_BN254_GROTH16_MAX_COMMITMENTS];   // Montgomery; [0] is not read
+};
+__global__ __launch_bounds__(256) void k_g16_gather_scale(const uint32_t* __restrict__ ids, uint32_t m, const uint64_t* __restrict__ witness,
+                                                          CommitSegments seg, uint64_t* __restrict__ plain, uint64_t* __restrict__ scaled) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= m) return;
+    Fr w = load<RP>(witness, ids[t]);
+    store(plain, t, w);
+    if (!scaled) return;
+    int j = 0;
+#pragma unroll
+    for (int i = 0; i < NLX_BN254_GROTH16_MAX_COMMITMENTS - 1; i++) j += t >= seg.end[i];
+    if (j) {
+        Fr p = seg.rho_pow[1];
+#pragma unroll
+        for (int i = 2; i < NLX_BN254_GROTH16_MAX_COMMITMENTS; i++)   // static indices: the table stays in scalar registers
+            if (j == i) p = seg.rho_pow[i];
+        w = mul(w, p);
+    }
+    store(scaled, t, w);
+}
+
 }  // namespace g16
 }  // namespace nlx
 
@@ -118,6 +151,12 @@ struct nlx_bn254_groth16_key {
     bool has_r1cs = false;
     g16::R1csDev r1cs{};
     uint32_t* long_rows = nullptr;
+    // Bsb22 / Pedersen commitments (n_commit = 0: none): set j's entries are [seg[j], seg[j + 1]) of the compact arrays
+    uint32_t n_commit = 0;
+    uint64_t n_committed = 0;                                    // M
+    uint32_t seg[NLX_BN254_GROTH16_MAX_COMMITMENTS + 1] = {};
+    const uint32_t* committed_ids = nullptr;                     // [M] wire ids, device
+    void *basis = nullptr, *basis_sigma = nullptr;               // [M] each, the bucket kernels' form
     std::vector<void*> blocks;     // every device block the key owns
     uint64_t info[NLX_BN254_GROTH16_KEY_INFO_WORDS] = {};
 };
@@ -270,12 +309,50 @@ void launch_r1cs(const nlx_bn254_groth16_key* key, const uint64_t* d_witness, ui
 
 }  // namespace
 
-extern "C" int32_t nlx_bn254_groth16_key_create(nlx_ctx* ctx, const nlx_bn254_groth16_key_desc* d, nlx_bn254_groth16_key** out) NLX_TRY {
-    if (!ctx) return NLX_E_INVAL;
-    if (!d || !out) return ctx->fail(NLX_E_INVAL, "NULL argument");
-    *out = nullptr;
-    if (d->flags != NLX_BN254_MONTGOMERY) return ctx->fail(NLX_E_RANGE, "flags must be NLX_BN254_MONTGOMERY");
-    if (d->n_commitments) return ctx->fail(NLX_E_UNSUPPORTED, "Groth16 with Bsb22 / Pedersen commitments is not supported");
+// The committed sets of a key on the host, validated: ids within the private wires, ascending inside a set, the sets disjoint,
+// the commitment wires private, not committed and distinct.  committed[i] != 0: wire i has left G1.K.
+struct CommitHost {
+    std::vector<uint64_t> counts;
+    std::vector<uint32_t> ids, wires;
+    std::vector<uint8_t> committed;
+    uint64_t m = 0;
+};
+static int32_t commit_host(nlx_ctx* ctx, const nlx_bn254_groth16_key_desc* d, const nlx_bn254_groth16_commit_desc* cd, CommitHost& h) {
+    const uint32_t k = cd->n_commitments;
+    if (!cd->n_private || !cd->commitment_wires) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    (void)hipSetDevice(ctx->device);
+    int32_t rc = to_host(ctx, cd->n_private, (size_t)k, h.counts);
+    if (!rc) rc = to_host(ctx, cd->commitment_wires, (size_t)k, h.wires);
+    if (rc) return rc;
+    for (uint32_t j = 0; j < k; j++) {
+        if (h.counts[j] > d->n_wires) return ctx->fail(NLX_E_RANGE, "commitment %u commits more wires than the key has", j);
+        h.m += h.counts[j];
+    }
+    if (h.m + k > d->n_wires - d->n_public) return ctx->fail(NLX_E_RANGE, "more committed and commitment wires than private wires");
+    if (h.m && (!cd->private_wires || !cd->basis || !cd->basis_exp_sigma)) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    rc = to_host(ctx, cd->private_wires, (size_t)h.m, h.ids);
+    if (rc) return rc;
+    h.committed.assign((size_t)d->n_wires, 0);
+    size_t t = 0;
+    for (uint32_t j = 0; j < k; j++)
+        for (uint64_t i = 0; i < h.counts[j]; i++, t++) {
+            const uint32_t id = h.ids[t];
+            if (id < d->n_public || id >= d->n_wires) return ctx->fail(NLX_E_RANGE, "commitment %u: wire %u is not a private wire", j, id);
+            if (i && id <= h.ids[t - 1]) return ctx->fail(NLX_E_RANGE, "commitment %u: the committed wire ids do not ascend at %u", j, id);
+            if (h.committed[id]) return ctx->fail(NLX_E_RANGE, "commitment %u: wire %u is committed twice", j, id);
+            h.committed[id] = 1;
+        }
+    for (uint32_t j = 0; j < k; j++) {
+        const uint32_t id = h.wires[j];
+        if (id < d->n_public || id >= d->n_wires) return ctx->fail(NLX_E_RANGE, "commitment %u: its wire %u is not a private wire", j, id);
+        if (h.committed[id]) return ctx->fail(NLX_E_RANGE, "commitment %u: its wire %u is committed or listed twice", j, id);
+        h.committed[id] = 2;
+    }
+    return NLX_OK;
+}
+
+// both creation entries, past their own first checks; cd = NULL: a key without commitments
+static int32_t key_build(nlx_ctx* ctx, const nlx_bn254_groth16_key_desc* d, const nlx_bn254_groth16_commit_desc* cd, nlx_bn254_groth16_key** out) {
     if (d->log_n < 1 || d->log_n > 26) return ctx->fail(NLX_E_RANGE, "log_n must be in [1, 26]");
     const uint64_t n = (uint64_t)1 << d->log_n;
     if (d->n_constraints > n) return ctx->fail(NLX_E_RANGE, "n_constraints exceeds 2^log_n");
@@ -284,7 +361,10 @@ extern "C" int32_t nlx_bn254_groth16_key_create(nlx_ctx* ctx, const nlx_bn254_gr
     if (!d->infinity_a || !d->infinity_b || !d->g1_alpha || !d->g1_beta || !d->g1_delta || !d->g2_beta || !d->g2_delta ||
         (d->n_g1_a && !d->g1_a) || (d->n_g1_b && !d->g1_b) || (d->n_g2_b && !d->g2_b) || (d->n_g1_k && !d->g1_k) || !d->g1_z)
         return ctx->fail(NLX_E_INVAL, "NULL argument");
-    if (d->n_g1_k != d->n_wires - d->n_public) return ctx->fail(NLX_E_RANGE, "G1.K holds one point per private wire");
+    CommitHost ch;
+    if (cd) NLX_RC(commit_host(ctx, d, cd, ch));
+    if (d->n_g1_k != d->n_wires - d->n_public - ch.m - (cd ? cd->n_commitments : 0))
+        return ctx->fail(NLX_E_RANGE, cd ? "G1.K holds one point per private wire that is neither committed nor a commitment's" : "G1.K holds one point per private wire");
     if (d->n_g1_z != n - 1) return ctx->fail(NLX_E_RANGE, "G1.Z holds 2^log_n - 1 points");
     if (d->n_g2_b != d->n_g1_b) return ctx->fail(NLX_E_RANGE, "G1.B and G2.B are filtered by the same mask");
     (void)hipSetDevice(ctx->device);
@@ -293,11 +373,11 @@ extern "C" int32_t nlx_bn254_groth16_key_create(nlx_ctx* ctx, const nlx_bn254_gr
     if (!rc) rc = to_host(ctx, d->infinity_b, (size_t)d->n_wires, mask_b);
     if (rc) return rc;
     std::vector<uint32_t> idx_a((size_t)d->n_wires), idx_b((size_t)d->n_wires), idx_k((size_t)d->n_wires);
-    uint64_t clear_a = 0, clear_b = 0;
+    uint64_t clear_a = 0, clear_b = 0, clear_k = 0;
     for (uint64_t i = 0; i < d->n_wires; i++) {
         idx_a[i] = mask_a[i] ? 0xFFFFFFFFu : (uint32_t)clear_a++;
         idx_b[i] = mask_b[i] ? 0xFFFFFFFFu : (uint32_t)clear_b++;
-        idx_k[i] = i < d->n_public ? 0xFFFFFFFFu : (uint32_t)(i - d->n_public);
+        idx_k[i] = (i < d->n_public || (cd && ch.committed[i])) ? 0xFFFFFFFFu : (uint32_t)clear_k++;
     }
     if (clear_a != d->n_g1_a) return ctx->fail(NLX_E_RANGE, "InfinityA leaves %llu wires, G1.A holds %llu points", (unsigned long long)clear_a, (unsigned long long)d->n_g1_a);
     if (clear_b != d->n_g1_b) return ctx->fail(NLX_E_RANGE, "InfinityB leaves %llu wires, G1.B holds %llu points", (unsigned long long)clear_b, (unsigned long long)d->n_g1_b);
@@ -317,6 +397,16 @@ extern "C" int32_t nlx_bn254_groth16_key_create(nlx_ctx* ctx, const nlx_bn254_gr
     if (!rc) rc = key_query(key, d->g2_b, d->n_g2_b, &idx_b, (size_t)d->n_wires, 1, &key->b2);
     if (!rc) rc = key_query(key, d->g1_k, d->n_g1_k, &idx_k, (size_t)d->n_wires, 0, &key->k);
     if (!rc) rc = key_query(key, d->g1_z, d->n_g1_z, nullptr, (size_t)d->n_g1_z, 0, &key->z);
+    if (!rc && cd) {   // the Pedersen bases, compact, and the committed wire ids next to them
+        key->n_commit = cd->n_commitments;
+        key->n_committed = ch.m;
+        for (uint32_t j = 0; j < cd->n_commitments; j++) key->seg[j + 1] = key->seg[j] + (uint32_t)ch.counts[j];
+        rc = key_query(key, cd->basis, ch.m, nullptr, (size_t)ch.m, 0, &key->basis);
+        if (!rc) rc = key_query(key, cd->basis_exp_sigma, ch.m, nullptr, (size_t)ch.m, 0, &key->basis_sigma);
+        if (!rc) rc = key_upload(key, ch.ids, &key->committed_ids);
+        key->info[0] += ch.m * 4;
+        key->info[6] = ch.m, key->info[7] = cd->n_commitments;
+    }
     if (!rc && any_matrix) {
         if (!d->coeffs) rc = ctx->fail(NLX_E_INVAL, "NULL argument (the matrices come with their coefficient table)");
         else rc = key_r1cs(key, d);
@@ -332,6 +422,29 @@ extern "C" int32_t nlx_bn254_groth16_key_create(nlx_ctx* ctx, const nlx_bn254_gr
     key->info[5] = g16::R1CS_LONG_ROW;
     *out = key;
     return NLX_OK;
+}
+
+extern "C" int32_t nlx_bn254_groth16_key_create(nlx_ctx* ctx, const nlx_bn254_groth16_key_desc* d, nlx_bn254_groth16_key** out) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (!d || !out) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    *out = nullptr;
+    if (d->flags != NLX_BN254_MONTGOMERY) return ctx->fail(NLX_E_RANGE, "flags must be NLX_BN254_MONTGOMERY");
+    if (d->n_commitments)
+        return ctx->fail(NLX_E_UNSUPPORTED, "a key with Bsb22 / Pedersen commitments brings its bases: nlx_bn254_groth16_key_create_committed");
+    return key_build(ctx, d, nullptr, out);
+} NLX_CATCH(ctx)
+
+extern "C" int32_t nlx_bn254_groth16_key_create_committed(nlx_ctx* ctx, const nlx_bn254_groth16_key_desc* d, const nlx_bn254_groth16_commit_desc* cd,
+                                                          nlx_bn254_groth16_key** out) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (!d || !cd || !out) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    *out = nullptr;
+    if (d->flags != NLX_BN254_MONTGOMERY) return ctx->fail(NLX_E_RANGE, "flags must be NLX_BN254_MONTGOMERY");
+    if (cd->n_commitments < 1 || cd->n_commitments > NLX_BN254_GROTH16_MAX_COMMITMENTS)
+        return ctx->fail(NLX_E_RANGE, "1 .. %d commitments", NLX_BN254_GROTH16_MAX_COMMITMENTS);
+    if (d->n_commitments != cd->n_commitments)
+        return ctx->fail(NLX_E_RANGE, "the key descriptor counts %u commitments, the commitment descriptor %u", d->n_commitments, cd->n_commitments);
+    return key_build(ctx, d, cd, out);
 } NLX_CATCH(ctx)
 
 extern "C" void nlx_bn254_groth16_key_destroy(nlx_bn254_groth16_key* key) NLX_TRY {
@@ -372,13 +485,19 @@ extern "C" int32_t nlx_bn254_r1cs_eval(nlx_ctx* ctx, const nlx_bn254_groth16_key
     return NLX_OK;
 } NLX_CATCH(ctx)
 
-extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, const uint64_t* witness, const uint64_t* a,
-                                           const uint64_t* b, const uint64_t* c, const uint64_t r[4], const uint64_t s[4], uint64_t ar_out[8],
-                                           uint64_t bs_out[16], uint64_t krs_out[8]) NLX_TRY {
+// The committed values gathered (and scaled by rho^j when `scaled` is wanted): entries [first, first + m) of the key's sets
+static void launch_gather(const nlx_bn254_groth16_key* key, uint32_t first, uint32_t m, const uint64_t* d_witness, const g16::CommitSegments& seg,
+                          uint64_t* d_plain, uint64_t* d_scaled) {
+    hipLaunchKernelGGL(g16::k_g16_gather_scale, dim3((m + 255) / 256), dim3(256), 0, key->ctx->stream, key->committed_ids + first, m, d_witness, seg,
+                       d_plain, d_scaled);
+}
+
+// One proof on either kind of key (the entries below have checked their own arguments).  rho = NULL: a key without
+// commitments; otherwise the k commitments and Pok are computed as well (commitments_out: k x 8 words).
+static int32_t prove_body(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, const uint64_t* witness, const uint64_t* a, const uint64_t* b,
+                          const uint64_t* c, const uint64_t r[4], const uint64_t s[4], const uint64_t* rho, uint64_t ar_out[8], uint64_t bs_out[16],
+                          uint64_t krs_out[8], uint64_t* commitments_out, uint64_t* pok_out) {
     using namespace nlx::msm;
-    if (!ctx) return NLX_E_INVAL;
-    if (!key || !witness || !r || !s || !ar_out || !bs_out || !krs_out) return ctx->fail(NLX_E_INVAL, "NULL argument");
-    if (key->ctx != ctx) return ctx->fail(NLX_E_INVAL, "the key belongs to another context");
     const bool given = a && b && c;
     if (!given && (a || b || c)) return ctx->fail(NLX_E_INVAL, "a, b, c come together or not at all");
     if (!given && !key->has_r1cs) return ctx->fail(NLX_E_INVAL, "a, b, c are NULL and the key was built without its R1CS matrices");
@@ -390,23 +509,27 @@ extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16
     Staged sw(ctx, witness, nw * 32, true, false);
     if (sw.status) return sw.status;
     const uint64_t* d_w = sw.as<uint64_t>();
-    SortedDigits wires_sorted[g16::G16_WIRE_SORTS], h_sorted;
+    const uint32_t k = rho ? key->n_commit : 0, m = (uint32_t)key->n_committed;
+    SortedDigits wires_sorted[g16::G16_WIRE_SORTS], h_sorted, commit_sorted[NLX_BN254_GROTH16_MAX_COMMITMENTS + 1];   // the last one: Pok
     struct ReleaseSorted {   // runs after `scratch` below (declared later, destroyed first) has synchronised the stream
         nlx_ctx* ctx;
-        SortedDigits *wires, *h;
+        SortedDigits *wires, *h, *commit;
         ~ReleaseSorted() {
             for (int i = 0; i < g16::G16_WIRE_SORTS; i++) release_digits(ctx, wires + i);
             release_digits(ctx, h);
+            for (int i = 0; i <= NLX_BN254_GROTH16_MAX_COMMITMENTS; i++) release_digits(ctx, commit + i);
         }
-    } release_sorted{ctx, wires_sorted, &h_sorted};
+    } release_sorted{ctx, wires_sorted, &h_sorted, commit_sorted};
     Scratch scratch(ctx);
     auto dev = [&](size_t bytes) { return scratch.alloc(bytes); };
     uint64_t* d_abc = (uint64_t*)dev(3 * n * 32);
     uint64_t* d_h = (uint64_t*)dev(n * 32);
     uint32_t* d_bad = (uint32_t*)dev(64);
     void* d_buckets = dev(bucket_bytes(1));   // one block serves all five bucket passes (the stream runs them in order)
-    unsigned char* d_wsum = (unsigned char*)dev(4 * window_sum_bytes(0) + window_sum_bytes(1));
-    if (!d_abc || !d_h || !d_bad || !d_buckets || !d_wsum) return ctx->fail(NLX_E_NOMEM, "Groth16 proof: device memory");
+    const size_t wsum_bytes = (4 + (k ? k + 1 : 0)) * window_sum_bytes(0) + window_sum_bytes(1);   // then the k commitments' and Pok's
+    unsigned char* d_wsum = (unsigned char*)dev(wsum_bytes);
+    uint64_t* d_committed = k && m ? (uint64_t*)dev(2 * (size_t)m * 32) : nullptr;   // plain | scaled by rho^j
+    if (!d_abc || !d_h || !d_bad || !d_buckets || !d_wsum || (k && m && !d_committed)) return ctx->fail(NLX_E_NOMEM, "Groth16 proof: device memory");
     // the solver's a, b, c, or the key's matrices times the witness
     hipError_t e = hipSuccess;
     if (given) {
@@ -442,14 +565,14 @@ extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16
     // the MSMs: four queries over the wire vector on one set of sorted indices, G1.Z over h on its own
     const void* query[4] = {key->a, key->b1, key->b2, key->k};
     const int query_g2[4] = {0, 0, 1, 0};
-    unsigned char* wsum_at[5];
+    unsigned char* wsum_at[5 + NLX_BN254_GROTH16_MAX_COMMITMENTS + 1];
     {
         unsigned char* p = d_wsum;
         for (int q = 0; q < 4; q++) {
             wsum_at[q] = p;
             p += window_sum_bytes(query_g2[q]);
         }
-        wsum_at[4] = p;
+        for (uint32_t q = 4; q < 5 + (k ? k + 1 : 0); q++, p += window_sum_bytes(0)) wsum_at[q] = p;
     }
     ctx->begin_kernel("bn254_groth16_msms", 32.0 * (double)(nw + n) + 320.0 * (double)nw + 64.0 * (double)n, (double)(4 * nw + n));
     for (int q = 0; q < 4 && !rc; q++) {
@@ -460,9 +583,30 @@ extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16
         rc = sort_digits(ctx, d_h, n - 1, 1, &h_sorted);
         if (!rc) bucket_reduce(ctx, h_sorted, key->z, 0, d_buckets, wsum_at[4]);
     }
+    if (!rc && k && m) {
+        // the committed values once, plain and scaled; then C_j over the slices of the plain vector and Basis, Pok over the
+        // scaled vector and BasisExpSigma.  An empty set reaches no kernel: its C_j is the point at infinity.
+        g16::CommitSegments seg;
+        Fr power = bnf::one<RP>();
+        const Fr rho_m = load_words<RP>(rho);
+        for (uint32_t j = 0; j < NLX_BN254_GROTH16_MAX_COMMITMENTS; j++) {
+            seg.end[j] = j < k ? key->seg[j + 1] : m;
+            seg.rho_pow[j] = power;
+            power = bnf::mul(power, rho_m);
+        }
+        launch_gather(key, 0, m, d_w, seg, d_committed, d_committed + (size_t)m * 4);
+        for (uint32_t j = 0; j < k && !rc; j++) {
+            const uint32_t lo = key->seg[j], count = key->seg[j + 1] - lo;
+            if (!count) continue;
+            rc = sort_digits(ctx, d_committed + (size_t)lo * 4, count, 1, &commit_sorted[j]);
+            if (!rc) bucket_reduce(ctx, commit_sorted[j], (const unsigned char*)key->basis + (size_t)lo * converted_point_bytes(0), 0, d_buckets, wsum_at[5 + j]);
+        }
+        if (!rc) rc = sort_digits(ctx, d_committed + (size_t)m * 4, m, 1, &commit_sorted[k]);
+        if (!rc) bucket_reduce(ctx, commit_sorted[k], key->basis_sigma, 0, d_buckets, wsum_at[5 + k]);
+    }
     ctx->end_kernel();
     if (rc) return rc;
-    std::vector<unsigned char> words(4 * window_sum_bytes(0) + window_sum_bytes(1));
+    std::vector<unsigned char> words(wsum_bytes);
     rc = fetch(ctx, words.data(), d_wsum, words.size());
     if (!rc) {
         e = hipGetLastError();
@@ -483,8 +627,81 @@ extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16
     krs = hjadd<H1>(krs, hjmul<H1>(ar, sk));
     krs = hjadd<H1>(krs, hjmul<H1>(bs1, rk));
     krs = hjadd<H1>(krs, hjneg<H1>(hjmul<H1>(s_delta1, rk)));
+    JacH<H1> commitment[NLX_BN254_GROTH16_MAX_COMMITMENTS], pok = hinf<H1>();
+    for (uint32_t j = 0; j < k; j++)
+        commitment[j] = key->seg[j + 1] > key->seg[j] ? window_tail_g1(words.data() + off4 + (1 + j) * off1) : hinf<H1>();
+    if (k && m) pok = window_tail_g1(words.data() + off4 + (1 + k) * off1);
     hstore_affine<H1>(ar, ar_out);
     hstore_affine<H2>(bs, bs_out);
     hstore_affine<H1>(krs, krs_out);
+    for (uint32_t j = 0; j < k; j++) hstore_affine<H1>(commitment[j], commitments_out + 8 * j);
+    if (k) hstore_affine<H1>(pok, pok_out);
+    return NLX_OK;
+}
+
+extern "C" int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, const uint64_t* witness, const uint64_t* a,
+                                           const uint64_t* b, const uint64_t* c, const uint64_t r[4], const uint64_t s[4], uint64_t ar_out[8],
+                                           uint64_t bs_out[16], uint64_t krs_out[8]) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (!key || !witness || !r || !s || !ar_out || !bs_out || !krs_out) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    if (key->ctx != ctx) return ctx->fail(NLX_E_INVAL, "the key belongs to another context");
+    if (key->n_commit) return ctx->fail(NLX_E_INVAL, "the key carries commitments: its proofs come from nlx_bn254_groth16_prove_committed");
+    return prove_body(ctx, key, witness, a, b, c, r, s, nullptr, ar_out, bs_out, krs_out, nullptr, nullptr);
+} NLX_CATCH(ctx)
+
+extern "C" int32_t nlx_bn254_groth16_prove_committed(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, const uint64_t* witness, const uint64_t* a,
+                                                     const uint64_t* b, const uint64_t* c, const uint64_t r[4], const uint64_t s[4],
+                                                     const uint64_t rho[4], uint64_t ar_out[8], uint64_t bs_out[16], uint64_t krs_out[8],
+                                                     uint64_t* commitments_out, uint64_t pok_out[8]) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (!key || !witness || !r || !s || !rho || !ar_out || !bs_out || !krs_out || !commitments_out || !pok_out) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    if (key->ctx != ctx) return ctx->fail(NLX_E_INVAL, "the key belongs to another context");
+    if (!key->n_commit) return ctx->fail(NLX_E_INVAL, "the key carries no commitment: its proofs come from nlx_bn254_groth16_prove");
+    if (is_device_ptr(rho)) return ctx->fail(NLX_E_INVAL, "rho is a host value");
+    if (!bnf::below_mod<bnf::RP>(rho)) return ctx->fail(NLX_E_RANGE, "rho is not below the group order");
+    return prove_body(ctx, key, witness, a, b, c, r, s, rho, ar_out, bs_out, krs_out, commitments_out, pok_out);
+} NLX_CATCH(ctx)
+
+extern "C" int32_t nlx_bn254_groth16_commit(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, uint32_t j, const uint64_t* witness, uint64_t out[8]) NLX_TRY {
+    using namespace nlx::msm;
+    if (!ctx) return NLX_E_INVAL;
+    if (!key || !witness || !out) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    if (key->ctx != ctx) return ctx->fail(NLX_E_INVAL, "the key belongs to another context");
+    if (!key->n_commit) return ctx->fail(NLX_E_INVAL, "the key carries no commitment");
+    if (j >= key->n_commit) return ctx->fail(NLX_E_RANGE, "commitment %u of %u", j, key->n_commit);
+    const uint32_t lo = key->seg[j], count = key->seg[j + 1] - lo;
+    if (!count) {   // the empty sum
+        memset(out, 0, 64);
+        return NLX_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    Staged sw(ctx, witness, (size_t)key->n_wires * 32, true, false);
+    if (sw.status) return sw.status;
+    SortedDigits sorted;
+    struct ReleaseSorted {   // after `scratch` (declared later, destroyed first) has synchronised the stream
+        nlx_ctx* ctx;
+        SortedDigits* s;
+        ~ReleaseSorted() { release_digits(ctx, s); }
+    } release_sorted{ctx, &sorted};
+    Scratch scratch(ctx);
+    uint64_t* d_plain = (uint64_t*)scratch.alloc((size_t)count * 32);
+    void* d_buckets = scratch.alloc(bucket_bytes(0));
+    void* d_wsum = scratch.alloc(window_sum_bytes(0));
+    if (!d_plain || !d_buckets || !d_wsum) return ctx->fail(NLX_E_NOMEM, "Groth16 commitment: device memory");
+    g16::CommitSegments seg{};
+    ctx->begin_kernel("bn254_groth16_commit", 100.0 * (double)count, (double)count);
+    launch_gather(key, lo, count, sw.as<uint64_t>(), seg, d_plain, nullptr);
+    int32_t rc = sort_digits(ctx, d_plain, count, 1, &sorted);
+    if (!rc) bucket_reduce(ctx, sorted, (const unsigned char*)key->basis + (size_t)lo * converted_point_bytes(0), 0, d_buckets, d_wsum);
+    ctx->end_kernel();
+    if (rc) return rc;
+    std::vector<unsigned char> words(window_sum_bytes(0));
+    rc = fetch(ctx, words.data(), d_wsum, words.size());
+    if (!rc) {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = ctx->hip_fail(e, "kernel launch");
+    }
+    if (rc) return rc;
+    hstore_affine<H1>(window_tail_g1(words.data()), out);
     return NLX_OK;
 } NLX_CATCH(ctx)

@@ -12,6 +12,10 @@ of the commit before it.
 --runs N --warmup W: median and min .. max of N runs after W unrecorded ones; --json PATH appends one record per size and mode.
 --one-proof: build the key, run ONE proof (a, b, c computed) and stop - the process to put under a kernel trace:
   rocprofv3 --kernel-trace --stats -d DIR -- python3 tools/groth16_prove_timing.py 18 --one-proof
+--commitments K --committed M: the same instance on a key with K Bsb22 / Pedersen commitments over M committed wires in all (split
+evenly; the bases tiled from the same 64 points), proved by nlx_bn254_groth16_prove_committed - what a commitment costs is the
+difference to the run without.  The commitment wires hold the instance's own values: the library does not
+hash, and the binding's challenge check is not part of the proof's time, so the library entry is timed directly.
 The A/B of the shared sort: a tuning build of the library that sorts the wire vector's digits once per query,
   NLX_BUILD_VARIANT=g16sort NLX_EXTRA_FLAGS=-DNLX_GROTH16_INDEPENDENT_SORT python near-light-client_amd/build.py
 and this tool run with NLX_BUILD_VARIANT=g16sort in the environment (its records are labelled independent-sort)."""
@@ -36,6 +40,8 @@ ap.add_argument("--runs", type=int, default=7)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--json", default=None)
 ap.add_argument("--one-proof", action="store_true")
+ap.add_argument("--commitments", type=int, default=0)
+ap.add_argument("--committed", type=int, default=0)
 opt = ap.parse_args()
 
 nlx = nlxpkg.load()
@@ -149,13 +155,44 @@ for log_n in opt.log_n or [18]:
         continue
     G = nlx.bn254_groth16
     t0 = time.perf_counter()
+    commitments = None
+    if opt.commitments:
+        # the commitment wires are the last K wires, the committed ones M wires spread over the private wires before them
+        K, M = opt.commitments, opt.committed
+        cwires = list(range(n_wires - K, n_wires))
+        ids = np.unique(np.linspace(1, n_wires - K - 1, M).astype(np.int64))
+        assert len(ids) == M, "too many committed wires for this size"
+        sets = np.array_split(ids, K)
+        commitments = [dict(private=[int(i) for i in sets[j]], public=[0] + cwires[:j], wire=cwires[j], basis=p1[(7 * sets[j] + j) % 64],
+                            basis_exp_sigma=p1[(11 * sets[j] + 5 + j) % 64]) for j in range(K)]
+        left = np.ones(n_wires, dtype=bool)
+        left[0], left[ids], left[cwires] = False, False, False
+        q["g1_k"] = p1[(3 * wires[left] + 1) % 64]
     key = G.ProvingKey(ctx, log_n, n_wires, 1, n, q["g1_a"], q["g1_b"], q["g2_b"], q["g1_k"], q["g1_z"], mask_a.astype(np.uint8),
-                       mask_b.astype(np.uint8), p1[1], p1[2], p1[3], p2[1], p2[2], r1cs=r1cs)
+                       mask_b.astype(np.uint8), p1[1], p1[2], p1[3], p2[1], p2[2], r1cs=r1cs, commitments=commitments)
     info = key.info()
     print("key resident: %.1f MB, created in %.2f s; rows per lane %d, per wave %d; %d of %d terms have a unit coefficient" % (
         info["resident_bytes"] / 1e6, time.perf_counter() - t0, info["lane_rows"], info["wave_rows"], info["unit_terms"], info["terms"]), flush=True)
     r, s = 0x1234567 + log_n, 0x7654321 + log_n
     sort = "independent-sort" if os.environ.get("NLX_BUILD_VARIANT") == "g16sort" else "shared-sort"
+    if opt.commitments:
+        rw, sw, rhow = G.fr_words(r), G.fr_words(s), G.fr_words(0x2468ACE + log_n)
+        outs = [np.zeros(8, dtype=np.uint64), np.zeros(16, dtype=np.uint64), np.zeros(8, dtype=np.uint64), np.zeros((opt.commitments, 8), dtype=np.uint64),
+                np.zeros(8, dtype=np.uint64)]
+
+        def committed(abc=(None, None, None)):
+            ctx.check(nlx.lib.dll.nlx_bn254_groth16_prove_committed(ctx.handle, key.handle, d_w.data_ptr(), *[None if t is None else t.data_ptr() for t in abc],
+                                                                    rw.ctypes.data, sw.ctypes.data, rhow.ctypes.data, *[o.ctypes.data for o in outs]))
+        if opt.one_proof:
+            committed()
+            torch.cuda.synchronize()
+            key.close()
+            continue
+        label = "%d commitments over %d wires, " % (opt.commitments, opt.committed)
+        record(log_n, "resident-key, abc supplied, " + label + sort, timed(lambda: committed((d_a, d_b, d_c))), resident_mb=round(info["resident_bytes"] / 1e6, 1))
+        record(log_n, "resident-key, abc computed, " + label + sort, timed(committed))
+        key.close()
+        continue
     if opt.one_proof:
         G.prove(key, d_w, r, s)
         torch.cuda.synchronize()
@@ -178,7 +215,7 @@ for log_n in opt.log_n or [18]:
                                     alg_gb_per_s=round(gbs, 1))) + "\n")
     key.close()
 
-if not opt.separate_calls and not opt.one_proof:
+if not opt.separate_calls and not opt.one_proof and not opt.commitments:
     # what the baseline leaves out: the blinding tail (five host scalar multiplications, one of them in G2).  A proof of ONE
     # constraint on two wires costs that tail plus the fixed launches of an empty pipeline: an upper bound of the tail's cost
     G = nlx.bn254_groth16
