@@ -366,7 +366,7 @@ int32_t nlx_bn254_groth16_prove(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, 
 /* C_j = sum_i w[PrivateCommitted_j[i]] Basis_j[i] of commitment j < k: the call a solver's hint makes while the witness is still
  * being solved - of `witness` (n_wires x 4 words, Montgomery, host or device) only the wires of PrivateCommitted_j are read.
  * out: G1Affine words, (0, 0) for the point at infinity (an empty set, or values that are all zero).  The hash that turns C_j
- * into the commitment wire's value is the caller's (no SHA-256 in this library).  NLX_E_INVAL on a key without commitments,
+ * into the commitment wire's value is the caller's here (nlx_bn254_hash_to_field is the library's, for the PLONK prover).  NLX_E_INVAL on a key without commitments,
  * NLX_E_RANGE for j >= k.  Kernel-timing name "bn254_groth16_commit", units committed wires. */
 int32_t nlx_bn254_groth16_commit(nlx_ctx* ctx, const nlx_bn254_groth16_key* key, uint32_t j, const uint64_t* witness, uint64_t out[8]);
 /* One proof on a key with commitments: everything nlx_bn254_groth16_prove does (the same guards first, the same a, b, c, r, s;
@@ -383,6 +383,77 @@ int32_t nlx_bn254_groth16_prove_committed(nlx_ctx* ctx, const nlx_bn254_groth16_
                                           const uint64_t* b, const uint64_t* c, const uint64_t r[4], const uint64_t s[4],
                                           const uint64_t rho[4], uint64_t ar_out[8], uint64_t bs_out[16], uint64_t krs_out[8],
                                           uint64_t* commitments_out, uint64_t pok_out[8]);
+
+/* ---- f.4, the PLONK half: whole gnark-shaped proofs from a proving key resident in HBM (gnark backend/plonk/bn254 ProvingKey and
+ * Prove; Go, not in the reference: the protocol is restated from its published structure, parity with gnark-produced bytes
+ * unpinned - DESIGN.md section 23).  Every element is an fr.Element / G1Affine as it lies in memory (Montgomery words).
+ *   log_n               3 .. 26; flags: NLX_BN254_MONTGOMERY, optionally | NLX_BN254_PLONK_KEY_COSET
+ *   ql qr qm qo qk s1 s2 s3   the fixed polynomials by values on H (n x 4 words each, host or device), as gnark's trace holds them
+ *   k1, k2, coset_shift host, four words each, below r
+ *   srs, n_srs          G1Affine points (8 words each, host or device); n_srs >= n + 3, the first n + 3 are used
+ *   n_commit            k = 0 .. NLX_BN254_PLONK_MAX_COMMIT Bsb22 commitments; with k > 0:
+ *   qcp                 HOST array of k pointers, qcp[j] = the selector of commitment j by values on H (host or device)
+ *   n_committed         k counts (host or device): the rows whose L wire commitment j covers
+ *   committed_rows      the k sets concatenated (host or device), ascending inside a set, each row < n
+ *   commit_rows         k rows (host or device): commitment j's own row i_j, whose L wire must hold c_j
+ *   last_row            the key-wide second blinding row (gnark: the last constraint)
+ * Creation computes the 8 + k coefficient forms once (kept padded to n + 3), converts the first n + 3 SRS points to the bucket
+ * kernels' form once, computes the 8 + k KZG commitments, and checks on the device that each qcp[j] is 1 exactly on its rows.
+ * With NLX_BN254_PLONK_KEY_COSET the key also keeps the fixed polynomials' values on the coset coset_shift * <w_4n>
+ * ((8 + k) * 4 n * 32 bytes): a proof then transforms only l r o z (pi, pi2_j); without it they are recomputed per proof from
+ * the resident coefficients.  The two settings give the same bytes.
+ * NLX_E_RANGE: log_n, unknown flags, n_commit, n_srs < n + 3, a scalar not below r, a row outside H, rows that do not ascend;
+ * NLX_E_INVAL: a NULL pointer, a selector that disagrees with its rows.  The key belongs to its context and must be destroyed
+ * before it. */
+typedef struct nlx_bn254_plonk_key nlx_bn254_plonk_key;
+typedef struct {
+    uint32_t log_n;
+    uint32_t flags;
+    const uint64_t *ql, *qr, *qm, *qo, *qk, *s1, *s2, *s3;
+    const uint64_t *k1, *k2, *coset_shift;
+    const uint64_t* srs; uint64_t n_srs;
+    uint32_t n_commit;
+    const uint64_t *const *qcp;
+    const uint64_t* n_committed;
+    const uint32_t* committed_rows;
+    const uint32_t* commit_rows;
+    uint32_t last_row;
+} nlx_bn254_plonk_key_desc;
+#define NLX_BN254_PLONK_KEY_COSET 0x400u
+int32_t nlx_bn254_plonk_key_create(nlx_ctx* ctx, const nlx_bn254_plonk_key_desc* desc, nlx_bn254_plonk_key** out);
+void nlx_bn254_plonk_key_destroy(nlx_bn254_plonk_key* key);
+/* out[0] = bytes the key keeps resident in HBM, out[1] = n, out[2] = k, out[3] = the committed rows of all sets, out[4] = 1 if
+ * the coset values are resident. */
+#define NLX_BN254_PLONK_KEY_INFO_WORDS 5
+int32_t nlx_bn254_plonk_key_info(const nlx_bn254_plonk_key* key, uint64_t out[NLX_BN254_PLONK_KEY_INFO_WORDS]);
+/* The verifying key's points: (8 + k) x 8 words in the order the transcript binds them: s1 s2 s3 ql qr qm qo qk qcp_0 .. */
+int32_t nlx_bn254_plonk_key_commitments(const nlx_bn254_plonk_key* key, uint64_t* out);
+size_t nlx_bn254_plonk_proof_bytes(const nlx_bn254_plonk_key* key);   /* 552 + 64 k */
+/* The solver's hint of commitment j < k, while the witness is still being solved: of l (n x 4 words, host or device) only the
+ * committed rows of set j are read.  pi2_j on H = those L values, then blinding[0] on the commitment row, THEN blinding[1] on
+ * last_row (the second write stands where the two coincide); point_out = [PI2_j] (G1Affine words), c_out =
+ * hash_to_field([PI2_j].Marshal(), "BSB22-Plonk") (Montgomery words): the value the circuit expects on the L wire of row i_j.
+ * blinding: host, two elements.  NLX_E_INVAL on a key without commitments, NLX_E_RANGE for j >= k. */
+int32_t nlx_bn254_plonk_commit(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, uint32_t j, const uint64_t* l, const uint64_t* blinding,
+                               uint64_t point_out[8], uint64_t c_out[4]);
+/* One proof in gnark's Proof.WriteTo bytes (552 + 64 k of them).  l, r, o: the wires on H, n x 4 words each, host or device.
+ * public_inputs: host, n_public x 4 words.  blinding: host, nine elements (l 2, r 2, o 2, z 3); commit_blinding: host, 2 k
+ * elements (commitment j: [2 j] on its row, [2 j + 1] on last_row), NULL exactly when k = 0.  The library draws no randomness.
+ * Every pi2_j is recomputed from the finished wires.  NLX_E_INVAL with a message, nothing written: l[commit_rows[j]] != c_j (also
+ * what a committed value changed after the hint gives), a grand product that does not close, a quotient whose coefficients
+ * from 3 n + 6 up do not vanish.  NLX_E_RANGE: proof_cap too small, a scalar not below r.  Kernel-timing names, one per round:
+ * bn254_plonk_prove_commit, _wires, _z, _quotient, _evals, _open. */
+int32_t nlx_bn254_plonk_prove(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, const uint64_t* l, const uint64_t* r, const uint64_t* o,
+                              const uint64_t* public_inputs, uint64_t n_public, const uint64_t* blinding, const uint64_t* commit_blinding,
+                              uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
+/* n_polys <= 16 polynomials at ONE point in one pass: polys = host array of pointers to lens[i] x 4 words (coefficients, natural
+ * order, host or device; 1 <= lens[i] <= 2^28, the lengths may differ), point: host; out: host, n_polys x 4 words.  Kernel-timing
+ * name "bn254_fr_eval_many". */
+int32_t nlx_bn254_fr_eval_many(nlx_ctx* ctx, uint32_t n_polys, const uint64_t* const* polys, const uint64_t* lens, const uint64_t point[4],
+                               uint64_t* out);
+/* gnark-crypto fr.Hash(msg, dst, 1)[0] as Montgomery words: RFC 9380 expand_message_xmd over SHA-256 to 48 bytes, read
+ * big-endian, mod r.  Host only, needs no context; dst_len <= 255. */
+int32_t nlx_bn254_hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len, uint64_t out[4]);
 
 /* ---- a3: plonky2::fri::oracle::PolynomialBatch::{from_values, from_coeffs} ----
  * values / coeffs: n_cols x 2^log_n column-major, natural order.  The coset shift is the

@@ -102,6 +102,18 @@ SIGNATURES = {
     "nlx_bn254_groth16_key_create_committed": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
     "nlx_bn254_groth16_commit": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_bn254_groth16_prove_committed": (ctypes.c_int32, [ctypes.c_void_p] * 14),
+    "nlx_bn254_plonk_key_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
+    "nlx_bn254_plonk_key_destroy": (None, [ctypes.c_void_p]),
+    "nlx_bn254_plonk_key_info": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_bn254_plonk_key_commitments": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_bn254_plonk_proof_bytes": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "nlx_bn254_plonk_commit": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_bn254_plonk_prove": (ctypes.c_int32, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                                       ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "nlx_bn254_fr_eval_many": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
+    "nlx_bn254_hash_to_field": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "nlx_commit_from_values": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, c_void_pp]),
     "nlx_commit_from_coeffs": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,

@@ -14,6 +14,7 @@ What this is not: gnark's byte format, blinding, its fiat-shamir labels (the tra
 chain) or the wrapper circuit - a maintainer wires the same calls into gnark's rounds.  Parity: the
 proof's nine points and six scalars equal the big-integer model's (oracle/bn254_py.py plonk_prove_model) and the model's
 verifier accepts them (tests/test_gpu_bn254_plonk.py)."""
+import ctypes
 import hashlib
 
 import numpy as np
@@ -448,3 +449,197 @@ def prove_gnark(pk, l=None, r=None, o=None, public_inputs=(), blinding=None, com
     out += k.to_bytes(4, "big") + b"".join(g1_compress(c) for c in pi2c)      # Bsb22Commitments
     out += g1_compress(bh) + len(claimed).to_bytes(4, "big") + b"".join(fr_bytes(v) for v in claimed)
     return out + g1_compress(zshift) + fr_bytes(zw)
+
+
+# ---- the same proof from a key resident in HBM, behind the C ABI (nlx_bn254_plonk_key_create / _commit / _prove) ------------
+# What prove_gnark orchestrates above - transcript, blinding patches, the Bsb22 round, the linearisation scalars, the batched
+# opening, Proof.WriteTo - runs inside the library (csrc/bn254_plonk_prove.hip); this is the binding.
+class _PlonkKeyDesc(ctypes.Structure):
+    """nlx_bn254_plonk_key_desc (include/nlx.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("flags", ctypes.c_uint32)] + [(k, ctypes.c_void_p) for k in (
+        "ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3", "k1", "k2", "coset_shift", "srs")] + [
+        ("n_srs", ctypes.c_uint64), ("n_commit", ctypes.c_uint32), ("qcp", ctypes.POINTER(ctypes.c_void_p)), ("n_committed", ctypes.c_void_p),
+        ("committed_rows", ctypes.c_void_p), ("commit_rows", ctypes.c_void_p), ("last_row", ctypes.c_uint32)]
+
+
+NLX_BN254_PLONK_KEY_COSET = 0x400
+
+
+def _wire_words(col):
+    """a wire column for the C ABI: an (n, 4) device tensor / uint64 array as it is, integers packed as fr.Element words"""
+    if hasattr(col, "data_ptr"):
+        return col.contiguous()
+    if isinstance(col, np.ndarray) and col.dtype == np.uint64:
+        return np.ascontiguousarray(col)
+    return B.bn254_pack([[_to_mont(x) for x in col]])[0]
+
+
+def _ptr(a):
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
+class ResidentKey:
+    """ProvingKey's arguments, kept by the library: coefficients, commitments, the converted SRS (and, with coset=True, the fixed
+    polynomials' values on the quotient's coset) stay in HBM across proofs.  values may hold integer lists, (n, 4) uint64 arrays
+    or device tensors of fr.Element words."""
+
+    NAMES = ProvingKey.NAMES
+
+    def __init__(self, ctx, values, srs, k1, k2, commitments=(), coset=False, coset_shift=None):
+        import ctypes
+        from ._lib import dll
+        self.ctx, self.handle = ctx, None
+        first = values["ql"]
+        self.n = first.shape[0] if hasattr(first, "shape") else len(first)
+        self.log_n = self.n.bit_length() - 1
+        self.k1, self.k2 = int(k1), int(k2)
+        self.bsb22 = [{"committed": [int(i) for i in c["committed"]], "row": int(c["row"]), "last_row": int(c["last_row"])} for c in commitments]
+        k = self.k = len(self.bsb22)
+        if k > 4:
+            raise ValueError("at most four Bsb22 commitments")
+        if any(c["last_row"] != self.bsb22[0]["last_row"] for c in self.bsb22):
+            raise ValueError("a last_row that differs from the key's")
+        keep = {name: _wire_words(values[name]) for name in self.NAMES}
+        qcp = [_wire_words(values["qcp%d" % j]) for j in range(k)]
+        srs = srs if hasattr(srs, "data_ptr") else np.ascontiguousarray(srs, dtype=np.uint64)
+        sc = [B._fr_words(_to_mont(x)) for x in (self.k1, self.k2, self.k1 if coset_shift is None else coset_shift)]
+        d = _PlonkKeyDesc()
+        d.log_n, d.flags = self.log_n, 1 | (NLX_BN254_PLONK_KEY_COSET if coset else 0)
+        for name in self.NAMES:
+            setattr(d, name, _ptr(keep[name]))
+        d.k1, d.k2, d.coset_shift = (x.ctypes.data for x in sc)
+        d.srs, d.n_srs, d.n_commit = _ptr(srs), srs.shape[0], k
+        arr = (ctypes.c_void_p * max(k, 1))(*[_ptr(q) for q in qcp])
+        counts = np.array([len(c["committed"]) for c in self.bsb22], dtype=np.uint64)
+        rows = np.array([i for c in self.bsb22 for i in c["committed"]], dtype=np.int64)
+        crows = np.array([c["row"] for c in self.bsb22], dtype=np.int64)
+        if k and (rows.min(initial=0) < 0 or rows.max(initial=0) >= 1 << 32 or crows.min() < 0 or crows.max() >= 1 << 32 or not 0 <= self.bsb22[0]["last_row"] < 1 << 32):
+            raise ValueError("rows outside H")
+        rows, crows = rows.astype(np.uint32), crows.astype(np.uint32)
+        if k:
+            d.qcp = ctypes.cast(arr, ctypes.POINTER(ctypes.c_void_p))
+            d.n_committed, d.committed_rows, d.commit_rows = counts.ctypes.data, rows.ctypes.data, crows.ctypes.data
+            d.last_row = self.bsb22[0]["last_row"]
+        h = ctypes.c_void_p()
+        rc = dll.nlx_bn254_plonk_key_create(ctx.handle, ctypes.byref(d), ctypes.byref(h))
+        if rc:
+            _raise(ctx, rc)
+        self.handle = h
+        ctx._adopt(self)
+        self.proof_bytes = dll.nlx_bn254_plonk_proof_bytes(h)
+
+    def info(self):
+        """dict: resident bytes, n, k, the committed rows of all sets, whether the coset values are resident"""
+        from ._lib import dll
+        out = np.zeros(5, dtype=np.uint64)
+        self.ctx.check(dll.nlx_bn254_plonk_key_info(self.handle, out.ctypes.data))
+        return {"resident_bytes": int(out[0]), "n": int(out[1]), "k": int(out[2]), "committed_rows": int(out[3]), "coset": bool(out[4])}
+
+    def key_commitments(self):
+        """(8 + k, 8) G1Affine words in the transcript's order: s1 s2 s3 ql qr qm qo qk qcp_0 .."""
+        from ._lib import dll
+        out = np.zeros((8 + self.k, 8), dtype=np.uint64)
+        self.ctx.check(dll.nlx_bn254_plonk_key_commitments(self.handle, out.ctypes.data))
+        return out
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            from ._lib import dll
+            dll.nlx_bn254_plonk_key_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _raise(ctx, rc):
+    """NLX_E_INVAL from the prover is a statement about the caller's witness or key: ValueError, as prove_gnark raises"""
+    from ._lib import NlxError, dll
+    err = NlxError(rc, dll.nlx_last_error(ctx.handle).decode())
+    if rc == -1:
+        raise ValueError(str(err)) from err
+    raise err
+
+
+def commit_resident(key, j, l, blinding):
+    """The solver's hint of commitment j (nlx_bn254_plonk_commit): l = the L wire as far as it is solved, blinding = two
+    scalars.  Returns ([PI2_j] as G1Affine words, c_j as an integer)."""
+    from ._lib import dll
+    lw = _wire_words(l)
+    b = np.stack([B._fr_words(_to_mont(int(x) % R)) for x in blinding])
+    if b.shape[0] != 2:
+        raise ValueError("two blinding scalars per Bsb22 commitment")
+    point, c = np.zeros(8, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    rc = dll.nlx_bn254_plonk_commit(key.ctx.handle, key.handle, j, _ptr(lw), b.ctypes.data, point.ctypes.data, c.ctypes.data)
+    if rc:
+        _raise(key.ctx, rc)
+    return point, _from_words_mont(c)
+
+
+def prove_resident(key, l=None, r=None, o=None, public_inputs=(), blinding=None, commit_blinding=None, witness=None):
+    """prove_gnark's contract on a ResidentKey: the same arguments (wires also as (n, 4) device tensors of fr.Element words), the
+    same bytes, ValueError where prove_gnark raises it.  One library call per proof, and one per commitment when the witness is
+    a callable (the hint)."""
+    import ctypes
+    import secrets
+    from ._lib import dll
+    k = key.k
+    if (witness is None) == (l is None) or (witness is None and (r is None or o is None)):
+        raise ValueError("pass the wires l, r, o or a callable witness(cs) -> (l, r, o)")
+    b = [secrets.randbelow(R) for _ in range(9)] if blinding is None else [int(x) % R for x in blinding]
+    if len(b) != 9:
+        raise ValueError("nine blinding scalars")
+    cb = [secrets.randbelow(R) for _ in range(2 * k)] if commit_blinding is None else [int(x) % R for x in commit_blinding]
+    if len(cb) != 2 * k:
+        raise ValueError("two blinding scalars per Bsb22 commitment")
+    committed = []
+    if witness is not None:
+        cs = []
+        for j, info in enumerate(key.bsb22):
+            lj = witness(list(cs))[0]
+            committed.append([int(lj[i]) % R for i in info["committed"]])
+            cs.append(commit_resident(key, j, lj, cb[2 * j:2 * j + 2])[1])
+        l, r, o = witness(list(cs))
+        for j, info in enumerate(key.bsb22):
+            if [int(l[i]) % R for i in info["committed"]] != committed[j]:
+                raise ValueError("Bsb22 commitment %d: a committed value was changed after the commitment" % j)
+    wires = [_wire_words(c) for c in (l, r, o)]
+    pubs = np.stack([B._fr_words(_to_mont(int(x) % R)) for x in public_inputs]) if len(public_inputs) else None
+    bw = np.stack([B._fr_words(_to_mont(x)) for x in b])
+    cbw = np.stack([B._fr_words(_to_mont(x)) for x in cb]) if k else None
+    out = np.zeros(key.proof_bytes, dtype=np.uint8)
+    got = ctypes.c_size_t()
+    rc = dll.nlx_bn254_plonk_prove(key.ctx.handle, key.handle, _ptr(wires[0]), _ptr(wires[1]), _ptr(wires[2]),
+                                   pubs.ctypes.data if pubs is not None else None, len(public_inputs), bw.ctypes.data,
+                                   cbw.ctypes.data if k else None, out.ctypes.data, out.nbytes, ctypes.byref(got))
+    if rc:
+        _raise(key.ctx, rc)
+    return out[:got.value].tobytes()
+
+
+def eval_many(ctx, polys, point):
+    """nlx_bn254_fr_eval_many: up to 16 polynomials ((m_i, 4) uint64 arrays / device tensors of fr.Element words, coefficients in
+    natural order, lengths may differ) at one point (a canonical integer) -> their values as canonical integers"""
+    import ctypes
+    from ._lib import dll
+    keep = [p.contiguous() if hasattr(p, "data_ptr") else np.ascontiguousarray(p, dtype=np.uint64) for p in polys]
+    arr = (ctypes.c_void_p * max(len(keep), 1))(*[_ptr(p) for p in keep])
+    lens = np.array([p.shape[0] for p in keep], dtype=np.uint64)
+    z = B._fr_words(_to_mont(int(point) % R))
+    out = np.zeros((max(len(keep), 1), 4), dtype=np.uint64)
+    ctx.check(dll.nlx_bn254_fr_eval_many(ctx.handle, len(keep), arr, lens.ctypes.data, z.ctypes.data, out.ctypes.data))
+    return [_from_words_mont(w) for w in out[:len(keep)]]
+
+
+def hash_to_field_native(msg, dst=BSB22_DST):
+    """nlx_bn254_hash_to_field (host code of the library, no context): what hash_to_field above computes with hashlib"""
+    from ._lib import dll
+    msg, dst = bytes(msg), bytes(dst)
+    out = np.zeros(4, dtype=np.uint64)
+    rc = dll.nlx_bn254_hash_to_field(msg, len(msg), dst, len(dst), out.ctypes.data)
+    if rc:
+        raise ValueError("nlx_bn254_hash_to_field: error %d" % rc)
+    return _from_words_mont(out)

@@ -30,6 +30,7 @@
 #include <vector>
 #include "ctx.hpp"
 #include "bn254_f29.hpp"
+#include "bn254_plonk.hpp"
 
 namespace nlx {
 namespace bnp {
@@ -103,8 +104,9 @@ struct Consts {
     Fe zh_inv[4];    // 1 / (x^n - 1) on the coset: x^n = shift^n i^(k mod 4)
 };
 struct QuotientParams {
-    const uint64_t* ev;   // [12 + has_pi + 2 n_commit][4n] evaluations on the coset, natural order: ql qr qm qo qk s1 s2 s3 l r o z
-                          // (pi) (qcp_0 .. pi2_0 ..)
+    // evaluations on the coset, natural order, [4n] each, in two groups (a resident key keeps the first one across proofs):
+    const uint64_t* ev_fixed;   // [8 + n_commit]: ql qr qm qo qk s1 s2 s3 (qcp_0 ..)
+    const uint64_t* ev_proof;   // [4 + has_pi + n_commit]: l r o z (pi) (pi2_0 ..)
     const uint64_t* x;    // [4n] the points, I-form
     const uint64_t* linv; // [4n] 1 / (n (x - 1)), I-form
     const Consts* k;
@@ -171,14 +173,26 @@ __global__ __launch_bounds__(64) void k_plonk_domain(const Consts* __restrict__ 
     }
 }
 
+// Coefficients in natural order (len of them, len <= 4n) -> their places in the zero-filled 4n-array the coset FFT (DIT) reads
+__global__ __launch_bounds__(256) void k_plonk_place_coeffs(const uint64_t* __restrict__ coeffs, size_t len, uint32_t log_n, uint64_t* __restrict__ col) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const uint32_t pos = __brev((uint32_t)i) >> (32 - (log_n + 2));
+    const uint4* q = reinterpret_cast<const uint4*>(coeffs + 4 * i);
+    uint4* d = reinterpret_cast<uint4*>(col + 4 * (size_t)pos);
+    d[0] = q[0];
+    d[1] = q[1];
+}
+
 // Blinding in coefficient form: p(X) += (b_0 + b_1 X + ...)(X^n - 1), i.e. coefficient i loses b_i and coefficient n + i gains it.
 // The coefficients lie in the 4n-array in bit-reversed order (what the coset FFT (DIT) reads): one lane per touched coefficient.
-// ev: [poly][4n] elements; job t = (poly, i, sign) for the nine blinding scalars b (D-form words, in order l l r r o o z z z).
+// ev: the per-proof group [l r o z ..][4n] elements; job t = (poly, i, sign) for the nine blinding scalars b (D-form words, in
+// order l l r r o o z z z).
 __global__ void k_plonk_blind(uint64_t* __restrict__ ev, const uint64_t* __restrict__ b, uint32_t log_n) {
     const uint32_t t = threadIdx.x;
     if (t >= 18) return;
     const uint32_t j = t >> 1, add_side = t & 1;                   // scalar j, the - b_i (0) or the + b_i (1) side
-    const uint32_t poly = j < 6 ? 8 + (j >> 1) : 11, i = j < 6 ? (j & 1) : j - 6;
+    const uint32_t poly = j < 6 ? (j >> 1) : 3, i = j < 6 ? (j & 1) : j - 6;
     const size_t N4 = (size_t)4 << log_n;
     const uint32_t idx = (add_side ? ((uint32_t)1 << log_n) : 0u) + i;
     const uint32_t pos = __brev(idx) >> (32 - (log_n + 2));
@@ -195,24 +209,25 @@ __global__ __launch_bounds__(256) void k_plonk_quotient(QuotientParams p) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N4) return;
     const Consts& k = *p.k;
-    auto E = [&](int poly, size_t at) { return ld(p.ev + (size_t)poly * 4 * N4, at); };   // canonical words: already tight
-    const Fe l = E(8, i), r = E(9, i), o = E(10, i);
+    auto E = [&](int poly, size_t at) { return ld(p.ev_fixed + (size_t)poly * 4 * N4, at); };   // canonical words: already tight
+    auto W = [&](int poly, size_t at) { return ld(p.ev_proof + (size_t)poly * 4 * N4, at); };
+    const Fe l = W(0, i), r = W(1, i), o = W(2, i);
     // gate: ql l + qr r + qm l r + qo o + qk (+ pi); every product of two data values is put back into D-form
     Fe gate = mul_dd(E(0, i), l);
     gate = add(gate, mul_dd(E(1, i), r));
     gate = add(gate, mul_dd(E(2, i), mul_dd(l, r)));
     gate = add(gate, mul_dd(E(3, i), o));
     gate = add(gate, E(4, i));
-    if (p.has_pi) gate = add(gate, E(12, i));
+    if (p.has_pi) gate = add(gate, W(4, i));
     if constexpr (COMMIT) {
-        const int base = 12 + (int)p.has_pi, nc = (int)p.n_commit;
+        const int base = 4 + (int)p.has_pi, nc = (int)p.n_commit;
 #pragma unroll 1
-        for (int j = 0; j < nc; j++) gate = add(gate, mul_dd(E(base + j, i), E(base + nc + j, i)));
+        for (int j = 0; j < nc; j++) gate = add(gate, mul_dd(E(8 + j, i), W(base + j, i)));
     }
     // permutation: the identity side on x, k1 x, k2 x and the sigma side on s1, s2, s3; z at the next point of the size-n
     // subgroup = four positions further on the size-4n coset
     const Fe x = ld(p.x, i), g = k.gamma_d;
-    const Fe z = E(11, i), zn = E(11, (i + 4) & (N4 - 1));
+    const Fe z = W(3, i), zn = W(3, (i + 4) & (N4 - 1));
     Fe f = mul_dd(add(add(l, mul(k.beta_d, x)), g), add(add(r, mul(k.beta_k1_d, x)), g));
     f = mul_dd(f, add(add(o, mul(k.beta_k2_d, x)), g));
     f = mul_dd(f, z);
@@ -432,6 +447,122 @@ int32_t mul_scan(nlx_ctx* ctx, uint64_t* seq, size_t len, int to_d, Scratch& scr
 }
 }  // namespace
 
+// ---- the quotient chain behind nlx_bn254_plonk_quotient and the resident prover (bn254_plonk_prove.hip) ----
+namespace nlx {
+namespace bnp {
+
+// polys (values on H or coefficients, never coset values) -> their values on the coset shift * <w_4n>, [count][4n] in d_ev:
+// FFTInverse(DIF) for the ones given by values, every coefficient to its bit-reversed place of 4n, FFT(DIT, OnCoset).
+// blind: the per-proof group's first column in d_ev and the nine scalars on the device (values-on-H callers), or NULL.
+static int32_t to_coset_blinded(nlx_ctx* ctx, uint32_t log_n, const PolyIn* polys, uint32_t count, const uint64_t shift[4], uint64_t* d_ev,
+                                Scratch& scratch, uint32_t blind_first, const uint64_t* d_blind) {
+    hipStream_t st = ctx->stream;
+    const size_t n = (size_t)1 << log_n, N4 = 4 * n;
+    uint32_t n_values = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (!polys[i].p) return ctx->fail(NLX_E_INVAL, "NULL polynomial");
+        if (polys[i].kind == POLY_VALUES) n_values++;
+        else if (polys[i].kind != POLY_COEFFS || polys[i].len > N4 || !is_device_ptr(polys[i].p)) return ctx->fail(NLX_E_INVAL, "coefficients are at most 4 n device elements");
+    }
+    uint64_t* d_in = n_values ? scratch.alloc_as<uint64_t>((size_t)n_values * n * 32) : nullptr;
+    if (n_values && !d_in) return NLX_E_NOMEM;
+    uint32_t v = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (polys[i].kind != POLY_VALUES) continue;
+        hipError_t e = hipMemcpyAsync(d_in + (size_t)v++ * n * 4, polys[i].p, n * 32,
+                                      is_device_ptr(polys[i].p) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
+    }
+    // 1. FFTInverse(DIF): values on H -> coefficients in bit-reversed order
+    if (n_values) NLX_RC(nlx_bn254_ntt_batch_coset(ctx, d_in, n_values, log_n, 1, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_OUT, nullptr));
+    // 2. zero-padded to 4n in bit-reversed order (coefficient at position p of n sits at 4 p of 4n), then FFT(DIT, OnCoset)
+    hipError_t e = hipMemsetAsync(d_ev, 0, (size_t)count * N4 * 32, st);
+    v = 0;
+    for (uint32_t i = 0; i < count && e == hipSuccess; i++) {
+        uint64_t* col = d_ev + (size_t)i * N4 * 4;
+        if (polys[i].kind == POLY_VALUES) e = hipMemcpy2DAsync(col, 128, d_in + (size_t)v++ * n * 4, 32, 32, n, hipMemcpyDeviceToDevice, st);
+        else if (polys[i].len) hipLaunchKernelGGL(k_plonk_place_coeffs, dim3((unsigned)((polys[i].len + 255) / 256)), dim3(256), 0, st, polys[i].p, polys[i].len, log_n, col);
+    }
+    if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpy2DAsync");
+    if (d_blind) hipLaunchKernelGGL(k_plonk_blind, dim3(1), dim3(64), 0, st, d_ev + (size_t)blind_first * N4 * 4, d_blind, log_n);
+    return nlx_bn254_ntt_batch_coset(ctx, d_ev, count, log_n + 2, 0, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_IN, shift);
+}
+
+int32_t to_coset(nlx_ctx* ctx, uint32_t log_n, const PolyIn* polys, uint32_t count, const uint64_t shift[4], uint64_t* d_ev) {
+    Scratch scratch(ctx);
+    return scratch.finish(to_coset_blinded(ctx, log_n, polys, count, shift, d_ev, scratch, 0, nullptr));
+}
+
+int32_t quotient_chain(nlx_ctx* ctx, const QuotientIn& q, uint64_t* t_out, size_t t_count, size_t t_keep, int32_t* high_chunk_is_zero) {
+    for (const uint64_t* sc : q.scalars)
+        if (!sc || is_device_ptr(sc)) return ctx->fail(NLX_E_INVAL, "the challenges and shifts are host values (four words each)");
+    for (const uint64_t* sc : q.scalars)
+        if (!bnf::below_mod<bnf::RP>(sc)) return ctx->fail(NLX_E_RANGE, "a challenge or shift is not below r (fr.Element words are residues)");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const uint32_t log_n = q.log_n, K = q.n_commit, nF = 8 + K, nP = 4 + q.has_pi + K;
+    const bool fixed_resident = q.fixed[0].kind == POLY_COSET;   // then all of the group: one block, used where it lies
+    const uint32_t T = (fixed_resident ? 0 : nF) + nP;
+    const bool blinded = q.blinding != nullptr, commit = K != 0;
+    const size_t n = (size_t)1 << log_n, N4 = 4 * n;
+    Scratch scratch(ctx);
+    int32_t rc = NLX_OK;
+    uint64_t* d_ev = scratch.alloc_as<uint64_t>((size_t)T * N4 * 32);
+    uint64_t* d_x = scratch.alloc_as<uint64_t>(N4 * 32);
+    uint64_t* d_linv = scratch.alloc_as<uint64_t>(N4 * 32);
+    uint64_t* d_t = scratch.alloc_as<uint64_t>(N4 * 32);
+    uint64_t* d_small = scratch.alloc_as<uint64_t>(6 * 32 + sizeof(Consts) + 64 + 9 * 32);
+    if (!d_ev || !d_x || !d_linv || !d_t || !d_small) return NLX_E_NOMEM;
+    Consts* d_k = (Consts*)(d_small + 6 * 4);
+    uint32_t* d_flag = (uint32_t*)((char*)d_k + sizeof(Consts));
+    uint64_t* d_blind = (uint64_t*)((char*)d_flag + 64);
+    {
+        uint64_t h[6 * 4];
+        for (int i = 0; i < 6; i++) memcpy(h + 4 * i, q.scalars[i], 32);
+        hipError_t e = hipMemcpyAsync(d_small, h, sizeof h, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && blinded) e = hipMemcpyAsync(d_blind, q.blinding, 9 * 32, hipMemcpyHostToDevice, st);   // caller-owned: outlives the sync below
+        if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 8, st);   // [0] high chunk non-zero, [1] Z_H vanishes on the coset
+        if (e == hipSuccess) e = hipStreamSynchronize(st);   // h leaves scope
+        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
+    }
+    hipLaunchKernelGGL(k_plonk_consts, dim3(1), dim3(1), 0, st, d_k, log_n, d_small, d_flag + 1);
+    hipLaunchKernelGGL(k_plonk_domain, dim3((unsigned)(((N4 + DOMAIN_RUN - 1) / DOMAIN_RUN + 63) / 64)), dim3(64), 0, st, d_k, log_n, d_x, d_linv);
+    PolyIn polys[13 + 2 * NLX_BN254_PLONK_MAX_COMMIT];
+    uint32_t t = 0;
+    if (!fixed_resident)
+        for (uint32_t i = 0; i < nF; i++) polys[t++] = q.fixed[i];
+    const uint32_t proof_first = t;
+    for (uint32_t i = 0; i < nP; i++) polys[t++] = q.proof[i];
+    rc = to_coset_blinded(ctx, log_n, polys, T, q.scalars[0], d_ev, scratch, proof_first, blinded ? d_blind : nullptr);
+    if (rc) return rc;
+    // 3. the quotient's values on the coset
+    QuotientParams qp{fixed_resident ? q.fixed[0].p : d_ev, d_ev + (size_t)proof_first * N4 * 4, d_x, d_linv, d_k, d_t, log_n, q.has_pi, K};
+    ctx->begin_kernel("plonk_quotient", 32.0 * N4 * (nF + nP + 4));
+    if (commit) hipLaunchKernelGGL(k_plonk_quotient<true>, dim3((unsigned)((N4 + 255) / 256)), dim3(256), 0, st, qp);
+    else hipLaunchKernelGGL(k_plonk_quotient<false>, dim3((unsigned)((N4 + 255) / 256)), dim3(256), 0, st, qp);
+    ctx->end_kernel();
+    // 4. back to coefficients
+    rc = nlx_bn254_ntt_batch_coset(ctx, d_t, 1, log_n + 2, 1, NLX_BN254_MONTGOMERY, q.scalars[0]);
+    if (rc) return rc;
+    // coefficients that must vanish: t_keep .. 4 n - 1 (3 n without blinding; the blinded wires raise the quotient's degree by six)
+    hipLaunchKernelGGL(k_any_nonzero, dim3((unsigned)(((N4 - t_keep) * 4 + 255) / 256)), dim3(256), 0, st, d_t + t_keep * 4, (N4 - t_keep) * 4, d_flag);
+    uint32_t flags[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(flags, d_flag, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
+    if (flags[1]) return ctx->fail(NLX_E_INVAL, "coset shift lies in the evaluation subgroup (x^n - 1 vanishes on the coset)");
+    e = hipMemcpyAsync(t_out, d_t, t_count * 32, is_device_ptr(t_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
+    hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return ctx->hip_fail(le, "kernel launch");
+    if (high_chunk_is_zero) *high_chunk_is_zero = flags[0] ? 0 : 1;
+    return NLX_OK;
+}
+
+}  // namespace bnp
+}  // namespace nlx
+
 extern "C" {
 
 int32_t nlx_bn254_plonk_grand_product(nlx_ctx* ctx, uint32_t log_n, const uint64_t* l, const uint64_t* r, const uint64_t* o,
@@ -581,85 +712,16 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
         for (uint32_t j = 0; j < K; j++)
             if (!a->qcp[j] || !a->pi2[j]) return ctx->fail(NLX_E_INVAL, "NULL polynomial (qcp / pi2)");
     }
-    {
-        const uint64_t* sc[6] = {a->coset_shift, a->k1, a->k2, a->alpha, a->beta, a->gamma};
-        for (const uint64_t* q : sc)
-            if (!q || is_device_ptr(q)) return ctx->fail(NLX_E_INVAL, "the challenges and shifts are host values (four words each)");
-        for (const uint64_t* q : sc)
-            if (!bnf::below_mod<bnf::RP>(q)) return ctx->fail(NLX_E_RANGE, "a challenge or shift is not below r (fr.Element words are residues)");
-    }
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const uint32_t log_n = a->log_n, P0 = a->pi ? 13 : 12, P = P0 + 2 * K;   // in ev after (pi): qcp_0 .. pi2_0 ..
-    const size_t n = (size_t)1 << log_n, N4 = 4 * n;
-    Scratch scratch(ctx);
-    int32_t rc = NLX_OK;
-    uint64_t* d_in = scratch.alloc_as<uint64_t>((size_t)P * n * 32);
-    uint64_t* d_ev = scratch.alloc_as<uint64_t>((size_t)P * N4 * 32);
-    uint64_t* d_x = scratch.alloc_as<uint64_t>(N4 * 32);
-    uint64_t* d_linv = scratch.alloc_as<uint64_t>(N4 * 32);
-    uint64_t* d_t = scratch.alloc_as<uint64_t>(N4 * 32);
-    uint64_t* d_small = scratch.alloc_as<uint64_t>(6 * 32 + sizeof(bnp::Consts) + 64 + 9 * 32);
-    if (!d_in || !d_ev || !d_x || !d_linv || !d_t || !d_small) return NLX_E_NOMEM;
-    bnp::Consts* d_k = (bnp::Consts*)(d_small + 6 * 4);
-    uint32_t* d_flag = (uint32_t*)((char*)d_k + sizeof(bnp::Consts));
-    uint64_t* d_blind = (uint64_t*)((char*)d_flag + 64);
-    {
-        uint64_t h[6 * 4];
-        const uint64_t* src[6] = {a->coset_shift, a->k1, a->k2, a->alpha, a->beta, a->gamma};
-        for (int i = 0; i < 6; i++) memcpy(h + 4 * i, src[i], 32);
-        hipError_t e = hipMemcpyAsync(d_small, h, sizeof h, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess && blinded) e = hipMemcpyAsync(d_blind, a->blinding, 9 * 32, hipMemcpyHostToDevice, st);   // caller-owned: outlives the sync below
-        if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, 8, st);   // [0] high chunk non-zero, [1] Z_H vanishes on the coset
-        if (e == hipSuccess) e = hipStreamSynchronize(st);   // h leaves scope
-        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
-    }
-    for (uint32_t i = 0; i < P; i++) {
-        const uint64_t* src = i < P0 ? polys[i] : i < P0 + K ? a->qcp[i - P0] : a->pi2[i - P0 - K];
-        hipError_t e = hipMemcpyAsync(d_in + (size_t)i * n * 4, src, n * 32,
-                                      is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpyAsync");
-    }
-    hipLaunchKernelGGL(bnp::k_plonk_consts, dim3(1), dim3(1), 0, st, d_k, log_n, d_small, d_flag + 1);
-    hipLaunchKernelGGL(bnp::k_plonk_domain, dim3((unsigned)(((N4 + bnp::DOMAIN_RUN - 1) / bnp::DOMAIN_RUN + 63) / 64)), dim3(64), 0, st, d_k, log_n, d_x, d_linv);
-    // 1. FFTInverse(DIF): values on H -> coefficients in bit-reversed order
-    rc = nlx_bn254_ntt_batch_coset(ctx, d_in, P, log_n, 1, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_OUT, nullptr);
-    if (rc) return rc;
-    // 2. zero-padded to 4n in bit-reversed order (coefficient at position p of n sits at 4 p of 4n), then FFT(DIT, OnCoset)
-    {
-        hipError_t e = hipMemsetAsync(d_ev, 0, (size_t)P * N4 * 32, st);
-        for (uint32_t i = 0; i < P && e == hipSuccess; i++)
-            e = hipMemcpy2DAsync(d_ev + (size_t)i * N4 * 4, 128, d_in + (size_t)i * n * 4, 32, 32, n, hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return ctx->hip_fail(e, "hipMemcpy2DAsync");
-    }
-    if (blinded) hipLaunchKernelGGL(bnp::k_plonk_blind, dim3(1), dim3(64), 0, st, d_ev, d_blind, log_n);
-    rc = nlx_bn254_ntt_batch_coset(ctx, d_ev, P, log_n + 2, 0, NLX_BN254_MONTGOMERY | NLX_BN254_BITREV_IN, a->coset_shift);
-    if (rc) return rc;
-    // 3. the quotient's values on the coset
-    bnp::QuotientParams qp{d_ev, d_x, d_linv, d_k, d_t, log_n, a->pi ? 1u : 0u, K};
-    ctx->begin_kernel("plonk_quotient", 32.0 * N4 * (P + 4));
-    if (commit) hipLaunchKernelGGL(bnp::k_plonk_quotient<true>, dim3((unsigned)((N4 + 255) / 256)), dim3(256), 0, st, qp);
-    else hipLaunchKernelGGL(bnp::k_plonk_quotient<false>, dim3((unsigned)((N4 + 255) / 256)), dim3(256), 0, st, qp);
-    ctx->end_kernel();
-    // 4. back to coefficients
-    rc = nlx_bn254_ntt_batch_coset(ctx, d_t, 1, log_n + 2, 1, NLX_BN254_MONTGOMERY, a->coset_shift);
-    if (rc) return rc;
-    // coefficients that must vanish: 3 n .. 4 n - 1 (3 n + 6 .. with blinding: the blinded wires raise the quotient's degree by six)
-    const size_t t_keep = blinded ? 3 * n + 6 : 3 * n;
-    hipLaunchKernelGGL(bnp::k_any_nonzero, dim3((unsigned)(((N4 - t_keep) * 4 + 255) / 256)), dim3(256), 0, st, d_t + t_keep * 4, (N4 - t_keep) * 4, d_flag);
-    uint32_t flags[2] = {0, 0};
-    hipError_t e = hipMemcpyAsync(flags, d_flag, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
-    if (flags[1]) return ctx->fail(NLX_E_INVAL, "coset shift lies in the evaluation subgroup (x^n - 1 vanishes on the coset)");
-    e = hipMemcpyAsync(t_out, d_t, (blinded ? N4 : 3 * n) * 32, is_device_ptr(t_out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return ctx->hip_fail(e, "copy out");
-    hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return ctx->hip_fail(le, "kernel launch");
-    const uint32_t flag = flags[0];
-    if (high_chunk_is_zero) *high_chunk_is_zero = flag ? 0 : 1;
-    return NLX_OK;
+    const size_t n = (size_t)1 << a->log_n;
+    bnp::PolyIn fixed[8 + NLX_BN254_PLONK_MAX_COMMIT], proof[5 + NLX_BN254_PLONK_MAX_COMMIT];
+    uint32_t np = 0;
+    for (int i = 0; i < 8; i++) fixed[i] = bnp::PolyIn{polys[i], bnp::POLY_VALUES, n};
+    for (uint32_t j = 0; j < K; j++) fixed[8 + j] = bnp::PolyIn{a->qcp[j], bnp::POLY_VALUES, n};
+    for (int i = 8; i < 12; i++) proof[np++] = bnp::PolyIn{polys[i], bnp::POLY_VALUES, n};
+    if (a->pi) proof[np++] = bnp::PolyIn{a->pi, bnp::POLY_VALUES, n};
+    for (uint32_t j = 0; j < K; j++) proof[np++] = bnp::PolyIn{a->pi2[j], bnp::POLY_VALUES, n};
+    bnp::QuotientIn in{a->log_n, a->pi ? 1u : 0u, K, fixed, proof, {a->coset_shift, a->k1, a->k2, a->alpha, a->beta, a->gamma}, blinded ? a->blinding : nullptr};
+    return bnp::quotient_chain(ctx, in, t_out, blinded ? 4 * n : 3 * n, blinded ? 3 * n + 6 : 3 * n, high_chunk_is_zero);
 } NLX_CATCH(ctx)
 
 int32_t nlx_bn254_kzg_open(nlx_ctx* ctx, const uint64_t* coeffs, uint64_t m, const uint64_t zeta[4], const uint64_t* srs,
