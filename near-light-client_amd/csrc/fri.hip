@@ -110,7 +110,9 @@ int32_t fri_prove(nlx_ctx* ctx, const FriProveArgs& a, Challenger& ch, Writer& w
             d_cap = launch_pbn_merkle_levels(st, dg, n_leaves, cap_h, ctx->pbn_quad_max_parents);
             ctx->end_kernel();
         } else {
-            if (n_leaves <= ((size_t)1 << 13)) launch_fri_leaves_wide(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg);
+            // a quad per leaf up to 2^14 leaves (profiles/poseidon_quad_sweep.txt, idle GPU, arity 16: 68 against 128 us; at 2^15
+            // leaves - two waves per SIMD - 103 against 130 us for 2.5 x the instructions, at 2^16 183 against 133 us)
+            if (n_leaves <= ((size_t)1 << 14)) launch_fri_leaves_wide(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg);
             else launch_fri_leaves(st, layer_values[r], ln, a.rate_bits, a.arity_bits, dg);
             d_cap = launch_merkle_levels(st, dg, n_leaves, cap_h);
         }

@@ -90,8 +90,11 @@ __global__ __launch_bounds__(256, 4) void k_merkle_level(const uint64_t* __restr
     if (live) store_digest(parents, i, s);
 }
 
-constexpr size_t MERKLE_WIDE_MAX_PARENTS = (size_t)1 << 14;
-constexpr unsigned MERKLE_FUSED_MAX_LEVELS = 6;  // 2^6 children per block: 32 sixteen-lane groups on the first fused level
+// measured crossover (profiles/poseidon_quad_sweep.txt, idle GPU, a level and everything above it): 8 192 parents 189 us fused
+// against 203 us with the level on one lane per parent first, 16 384 parents 237 against 223; ten trees of 1 024 parents each
+// 160 against 141 - the count is parents x trees
+constexpr size_t MERKLE_WIDE_MAX_PARENTS = (size_t)1 << 13;
+constexpr unsigned MERKLE_FUSED_MAX_LEVELS = 6;  // 2^6 children per block: 32 quads (two waves) on the first fused level
 void launch_merkle_fused(hipStream_t st, const uint64_t* children, size_t n_children, unsigned levels, uint32_t n_trees, size_t tree_words);
 
 // ---- host launchers (stream-ordered, no synchronisation) ----
@@ -118,11 +121,12 @@ const uint64_t* launch_merkle_levels(hipStream_t st, uint64_t* d_digests, size_t
     while (lvl > cap) {
         uint64_t* nxt = cur + lvl * 4;
         size_t half = lvl >> 1;
-        // below ~2^14 parents a level no longer fills the chip with one lane per permutation: switch to sixteen lanes per
-        // permutation (latency ~1/5), and - every such level being latency-bound - run up to six consecutive levels in
-        // ONE launch: a block owns a subtree of 2^K children and walks it up in LDS (round 1 launched every level
-        // separately: 11 launches of ~29 us for the top of a 2^19-leaf tree, now 2)
-        if (half <= MERKLE_WIDE_MAX_PARENTS) {
+        // up to 2^13 parents (over all the trees of the launch, as launch_hash_lde_leaves counts rows x batches) a level no
+        // longer fills the chip with one lane per permutation: switch to a quad of lanes per permutation, and - every such
+        // level being latency-bound - run up to six consecutive levels in ONE launch: a block owns a subtree of 2^K children
+        // and walks it up in LDS (round 1 launched every level separately: 11 launches of ~29 us for the top of a 2^19-leaf
+        // tree, now 2)
+        if (half * n_trees <= MERKLE_WIDE_MAX_PARENTS) {
             unsigned K = 0;
             while (K < MERKLE_FUSED_MAX_LEVELS && (lvl >> K) > cap) K++;
             launch_merkle_fused(st, cur, lvl, K, n_trees, tree_words);
@@ -147,7 +151,11 @@ namespace nlx {
 // g*w_L^(8k+r)).  plonky2 orders Merkle leaves by the bit-reversed LDE index, so the digest of
 // (r,k) lands at tree position bitrev_b(r)*n + bitrev_logn(k): a 32-byte scatter per row
 // instead of a transposed copy of the whole table.
-constexpr size_t HASH_LEAVES_WIDE_MAX_ROWS = (size_t)1 << 13;  // measured crossover (4 745 columns): 2^13 rows 16 vs 24 ms, 2^14 rows 31 vs 26 ms
+// profiles/poseidon_quad_sweep.txt (idle GPU, 135 / 512 / 1 955 columns): a quad per leaf takes 0.52 of one lane per leaf up to
+// 2^14 rows (one wave per SIMD: 3.9 against 7.5 ms at 1 955 columns) and 0.75 at 2^15 (two waves).  The constant stays at 2^13
+// all the same: a quad spends 2.5 x the instructions of a lane per permutation, which the overlapped streams of a proving step
+// pay in full once every SIMD has a wave, and tests/test_gpu_poseidon_aims.py pins 2^14 rows to the one-lane kernel.
+constexpr size_t HASH_LEAVES_WIDE_MAX_ROWS = (size_t)1 << 13;
 
 // batch_cols > 0: the table is committed as ceil(n_cols / batch_cols) PolynomialBatches of at most batch_cols columns each
 // (blockIdx.y = batch): a batch's leaf is hash_or_noop of ITS columns of the row, its digests go to tree blockIdx.y
@@ -238,7 +246,7 @@ void launch_hash_lde_leaves(hipStream_t st, const uint64_t* d_lde, size_t col_st
     const uint32_t n_batches = batch_cols ? (n_cols + batch_cols - 1) / batch_cols : 1;
     const uint32_t widest = batch_cols && batch_cols < n_cols ? batch_cols : n_cols;
     // Few rows of many columns (a short wide STARK trace): one lane per leaf leaves most SIMDs idle while every lane
-    // walks its ceil(c/8) permutations one after the other; sixteen lanes per leaf cut that chain's latency ~5x.
+    // walks its ceil(c/8) permutations one after the other; a quad per leaf puts four times as many waves to work.
     // (leaves in flight = rows x batches: with batches a short trace fills the chip with one lane per leaf much sooner)
     if (rows * n_batches <= HASH_LEAVES_WIDE_MAX_ROWS && widest > 16) {
         launch_hash_lde_leaves_wide(st, d_lde, col_stride, n_cols, log_n, rate_bits, d_digests, batch_cols, tree_words);
@@ -251,70 +259,123 @@ void launch_hash_lde_leaves(hipStream_t st, const uint64_t* d_lde, size_t col_st
 }  // namespace nlx
 
 // =====================================================================================
-// Latency-optimised ("wide") Poseidon for small tree levels
+// Sub-wave Poseidon for small tree levels, FRI leaves and short traces: one state per quad of lanes
 // =====================================================================================
-// One permutation per 16-lane group, one state element per lane (lanes 12..15 idle).  A level
-// with m parents occupies 16*m lanes, so levels too small to fill the chip finish in ~1/5 of
-// the one-lane-per-permutation latency (the dependent chain per round is one S-box plus one
-// 12-term dot product instead of twelve of each).  The linear layer exchanges elements through
-// a per-group LDS slot (1 ds_write_b64 + 12 broadcast ds_read_b64 per round).
+// Lane q of an aligned quad holds state elements q, q + 4 and q + 8 (slot m = element q + 4 m), so a wave holds sixteen
+// states and every lane works in the full rounds.  The linear layer out[r] = sum_e C[(e - r) mod 12] s[e] (+ 8 s[0] for r = 0)
+// needs all twelve elements in every lane: the three other lanes' slots arrive by DPP quad rotations (18 v_mov_dpp, no LDS, no
+// fence, no barrier).  With this split the coefficient of the element that rotation d delivered in slot m, for output slot
+// m', depends on (m - m') mod 3 only: C[((q + d) % 4 - q + 4 (m - m')) mod 12] - twelve constants per lane, C rotated by the
+// lane's position, kept in registers for the whole kernel (a thirteenth carries the + 8 of the matrix's corner).
+// (e = 3 q + m would need twenty: the coefficient depends on m - m' itself there.)
+//
+// CONTRACT (as for k_ed_scan4): DPP reads its neighbours' registers, so whole quads reach the permutation together - spare
+// quads of a wave redo the last item and store nothing, no lane returns before the last permutation; a branch around the
+// permutation must be quad-uniform.
 namespace nlx {
+namespace pquad {
 
-constexpr unsigned WIDE_GROUPS_PER_BLOCK = 16;  // 256 threads
+struct Mds {
+    uint32_t k[4][3];   // [rotation d][(m - m') mod 3]
+    uint32_t k00;       // k[0][0] + 8 in the lane that owns element 0: the coefficient of its own slot 0 for its output slot 0
+};
 
-__device__ __forceinline__ gl32::F permute_wide(gl32::F x, uint32_t j, volatile uint64_t* slot) {
+__device__ __forceinline__ Mds mds_table(uint32_t q) {
     constexpr uint32_t C[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
-    const uint64_t* rc = poseidon::RC_DEV;
-    const uint32_t jj = j < 12 ? j : 0;
-    const uint32_t diag = j == 0 ? 8u : 0u;
-    // A 16-lane group lives inside ONE wave and LDS operations of a wave execute in order, so no
-    // workgroup barrier is needed: a wave-level fence keeps the compiler from reordering the slot
-    // write and the reads around it.  Two slots alternate so a round's reads never race the next
-    // round's write.
-#pragma unroll 1
-    for (int r = 0; r < 30; r++) {
-        x = gl32::add_const_v(x, rc[r * 12 + jj]);
-        const gl32::F x7 = gl32::sbox7(x);
-        const bool full = (r < 4) || (r >= 26);
-        if (full || j == 0) x = x7;
-        volatile uint64_t* sl = slot + (r & 1) * 12;
-        if (j < 12) sl[j] = gl32::to_u64(x);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // two accumulator pairs shorten the dependent multiply-add chain
-        uint64_t al = (uint64_t)x.lo * diag, ah = (uint64_t)x.hi * diag, bl = 0, bh = 0;
+    Mds t;
 #pragma unroll
-        for (int i = 0; i < 12; i += 2) {
-            uint32_t s0 = jj + i, s1 = jj + i + 1;
-            s0 = s0 >= 12 ? s0 - 12 : s0;
-            s1 = s1 >= 12 ? s1 - 12 : s1;
-            const uint64_t v0 = sl[s0], v1 = sl[s1];
-            al += (uint64_t)(uint32_t)v0 * C[i];
-            ah += (uint64_t)(uint32_t)(v0 >> 32) * C[i];
-            bl += (uint64_t)(uint32_t)v1 * C[i + 1];
-            bh += (uint64_t)(uint32_t)(v1 >> 32) * C[i + 1];
+    for (int d = 0; d < 4; d++)
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int qq = 0; qq < 4; qq++)
+                if (q == (uint32_t)qq) v = C[(((qq + d) & 3) + 12 - qq + 4 * m) % 12];
+            t.k[d][m] = v;
         }
-        x = gl32::fold_acc(al + bl, ah + bh);
-    }
-    return x;
+    t.k00 = t.k[0][0] + (q == 0 ? 8u : 0u);
+    return t;
 }
+
+constexpr int ROT1 = 0x39, ROT2 = 0x4E, ROT3 = 0x93;   // quad_perm [1,2,3,0], [2,3,0,1], [3,0,1,2]: lane q reads lane (q + d) % 4
+
+template <int CTRL>
+__device__ __forceinline__ gl32::F rot(gl32::F v) {
+    gl32::F r;
+    r.lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)v.lo, CTRL, 0xF, 0xF, true);
+    r.hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)v.hi, CTRL, 0xF, 0xF, true);
+    return r;
+}
+
+// One round without its constants: S-boxes (all three slots in a full round, element 0's lane alone in a partial one), then the
+// linear layer.  `cn` (SEED): this lane's three constants of the NEXT round, which seed the accumulators as in gl32::mds_layer,
+// so that adding them costs no instruction of its own.  The accumulators of an output are exact integer sums below 2^42 (the
+// coefficients of a row add up to 264, a constant's limb is one more term), whatever the order of the terms.
+template <bool SEED>
+__device__ __forceinline__ void round(gl32::F (&x)[3], uint32_t q, const Mds& mds, bool full, const uint64_t (&cn)[3]) {
+    if (full || q == 0) x[0] = gl32::sbox7(x[0]);
+    if (full) {
+        x[1] = gl32::sbox7(x[1]);
+        x[2] = gl32::sbox7(x[2]);
+    }
+    gl32::F v[4][3];
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+        v[0][m] = x[m];
+        v[1][m] = rot<ROT1>(x[m]);
+        v[2][m] = rot<ROT2>(x[m]);
+        v[3][m] = rot<ROT3>(x[m]);
+    }
+#pragma unroll
+    for (int mo = 0; mo < 3; mo++) {
+        uint64_t al = SEED ? (uint32_t)cn[mo] : 0, ah = SEED ? cn[mo] >> 32 : 0;
+#pragma unroll
+        for (int d = 0; d < 4; d++)
+#pragma unroll
+            for (int m = 0; m < 3; m++) {
+                const uint32_t k = (d == 0 && m == 0 && mo == 0) ? mds.k00 : mds.k[d][(m - mo + 3) % 3];
+                al += (uint64_t)v[d][m].lo * k;
+                ah += (uint64_t)v[d][m].hi * k;
+            }
+        x[mo] = gl32::fold_acc(al, ah);
+    }
+}
+
+// The plain thirty-round schedule on gl32's primitives; x[m] = element q + 4 m, loose in, loose out (the same field elements
+// as poseidon::permute_loose's: callers canonicalise what they store).
+__device__ __forceinline__ void permute(gl32::F (&x)[3], uint32_t q, const Mds& mds) {
+    const uint64_t* rc = poseidon::RC_DEV + q;
+#pragma unroll
+    for (int m = 0; m < 3; m++) x[m] = gl32::add_const_v(x[m], rc[4 * m]);
+#pragma unroll 1
+    for (int r = 0; r < 29; r++) {
+        const uint64_t* rn = rc + (r + 1) * 12;   // loaded first: they travel while the S-boxes compute
+        const uint64_t cn[3] = {rn[0], rn[4], rn[8]};
+        round<true>(x, q, mds, (r < 4) || (r >= 26), cn);
+    }
+    const uint64_t none[3] = {0, 0, 0};
+    round<false>(x, q, mds, true, none);
+}
+
+}  // namespace pquad
+
+constexpr unsigned QUADS_PER_BLOCK = 16;   // one wave per block: a short launch spreads over as many CUs as it has waves
 
 // K consecutive tree levels in one launch: block b owns the subtree over children [b 2^K, (b + 1) 2^K) of the level at
 // `children` (n_children digests, level-major array: the parent levels follow it back to back) and walks it up in LDS,
-// one parent per sixteen-lane group and level; every level is also written to its place in the digest array (Merkle
-// paths are read from it later).  2^K <= 2 * FUSED_GROUPS.
-constexpr unsigned FUSED_GROUPS = 32;  // 512 threads: two waves per SIMD on the first level, one from the second on
+// one parent per quad and level; every level is also written to its place in the digest array (Merkle paths are read
+// from it later).  2^K <= 2 * FUSED_QUADS.
+constexpr unsigned FUSED_QUADS = 32;  // 128 threads: two waves on the first level, one from the second on
 
-__global__ __launch_bounds__(FUSED_GROUPS * 16) void k_merkle_fused(const uint64_t* __restrict__ children, uint64_t* __restrict__ parents0,
-                                                                   size_t n_children, unsigned K, size_t tree_words) {
+__global__ __launch_bounds__(FUSED_QUADS * 4) void k_merkle_fused(const uint64_t* __restrict__ children, uint64_t* __restrict__ parents0,
+                                                                  size_t n_children, unsigned K, size_t tree_words) {
     children += (size_t)blockIdx.y * tree_words;
     parents0 += (size_t)blockIdx.y * tree_words;
-    __shared__ uint64_t slots[FUSED_GROUPS * 24];
-    __shared__ uint64_t lv[2][FUSED_GROUPS * 2 * 4];
-    const uint32_t j = threadIdx.x & 15, g = threadIdx.x >> 4;
+    __shared__ uint64_t lv[2][FUSED_QUADS * 2 * 4];
+    const uint32_t q = threadIdx.x & 3, g = threadIdx.x >> 2;
+    const pquad::Mds mds = pquad::mds_table(q);
     const uint32_t n_own = 1u << K;
-    for (uint32_t i = threadIdx.x; i < n_own * 4; i += FUSED_GROUPS * 16) lv[0][i] = children[((size_t)blockIdx.x << K) * 4 + i];
+    for (uint32_t i = threadIdx.x; i < n_own * 4; i += FUSED_QUADS * 4) lv[0][i] = children[((size_t)blockIdx.x << K) * 4 + i];
     __syncthreads();
     uint64_t* outp = parents0;
     size_t level_total = n_children;
@@ -323,81 +384,83 @@ __global__ __launch_bounds__(FUSED_GROUPS * 16) void k_merkle_fused(const uint64
         level_total >>= 1;
         const uint64_t* src = lv[(s - 1) & 1];
         uint64_t* dst = lv[s & 1];
-        if (g < own) {
-            const uint64_t v = j < 8 ? src[g * 8 + j] : 0;
-            const gl32::F x = permute_wide(gl32::from_u64(v), j, slots + g * 24);
-            if (j < 4) {
-                const uint64_t w = gl::canon(gl32::to_u64(x));
-                dst[g * 4 + j] = w;
-                outp[((size_t)blockIdx.x * own + g) * 4 + j] = w;
-            }
+        if (g < own) {   // quad-uniform: a quad is in or out as a whole
+            gl32::F x[3] = {gl32::from_u64(src[g * 8 + q]), gl32::from_u64(src[g * 8 + 4 + q]), gl32::from_u64(0)};
+            pquad::permute(x, q, mds);
+            const uint64_t w = gl::canon(gl32::to_u64(x[0]));   // the digest is elements 0 .. 3: slot 0 of the four lanes
+            dst[g * 4 + q] = w;
+            outp[((size_t)blockIdx.x * own + g) * 4 + q] = w;
         }
         __syncthreads();
         outp += level_total * 4;
     }
 }
 
-// FRI layer leaves, one leaf per 16 lanes (see k_fri_leaves for the index maps)
+// FRI layer leaves, one leaf per quad (see k_fri_leaves for the index maps)
 template <int ARITY_BITS>
-__global__ __launch_bounds__(256) void k_fri_leaves_wide(const uint64_t* __restrict__ values, unsigned log_n,
-                                                         unsigned rate_bits, uint64_t* __restrict__ digests) {
-    __shared__ uint64_t lds[WIDE_GROUPS_PER_BLOCK * 24];
+__global__ __launch_bounds__(QUADS_PER_BLOCK * 4) void k_fri_leaves_wide(const uint64_t* __restrict__ values, unsigned log_n,
+                                                                         unsigned rate_bits, uint64_t* __restrict__ digests) {
     constexpr int ARITY = 1 << ARITY_BITS;
     const unsigned log_np = log_n - ARITY_BITS;
-    const uint32_t j = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const size_t jp = (size_t)blockIdx.x * WIDE_GROUPS_PER_BLOCK + g;
-    const bool live = (jp >> (log_np + rate_bits)) == 0;
+    const uint32_t q = threadIdx.x & 3;
+    const size_t n_leaves = (size_t)1 << (log_np + rate_bits);
+    const size_t jp_raw = (size_t)blockIdx.x * QUADS_PER_BLOCK + (threadIdx.x >> 2);
+    const bool live = jp_raw < n_leaves;                // spare quads redo the last leaf and store nothing
+    const size_t jp = live ? jp_raw : n_leaves - 1;
     const size_t np = (size_t)1 << log_np, n = (size_t)1 << log_n;
     const uint32_t r = (uint32_t)(jp >> log_np), kp = (uint32_t)(jp & (np - 1));
-    gl32::F x = gl32::from_u64(0);
-    // absorb 8 words (4 extension elements, slots m0..m0+3) per permutation; lane j < 8 owns word j
+    const pquad::Mds mds = pquad::mds_table(q);
+    gl32::F x[3] = {gl32::from_u64(0), gl32::from_u64(0), gl32::from_u64(0)};
+    // absorb 8 words (4 extension elements, slots m0..m0+3) per permutation; lane q owns words q and q + 4
 #pragma unroll 1
     for (int m0 = 0; m0 < ARITY; m0 += 4) {
-        if (j < 8) {
-            const int m = m0 + (int)(j >> 1);
-            const uint32_t mm = gl::bitrev32((uint32_t)m, ARITY_BITS);
-            uint64_t v = 0;
-            if (live) v = values[2 * ((size_t)r * n + kp + (size_t)mm * np) + (j & 1)];
-            x = gl32::from_u64(v);  // overwrite-mode absorb
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const uint32_t j = q + 4 * h;
+            const uint32_t mm = gl::bitrev32((uint32_t)m0 + (j >> 1), ARITY_BITS);
+            x[h] = gl32::from_u64(values[2 * ((size_t)r * n + kp + (size_t)mm * np) + (j & 1)]);  // overwrite-mode absorb
         }
-        x = permute_wide(x, j, lds + g * 24);
+        pquad::permute(x, q, mds);
     }
-    if (live && j < 4) {
+    if (live) {
         const size_t leaf = ((size_t)gl::bitrev32(r, rate_bits) << log_np) + gl::bitrev32(kp, log_np);
-        digests[leaf * 4 + j] = gl::canon(gl32::to_u64(x));
+        digests[leaf * 4 + q] = gl::canon(gl32::to_u64(x[0]));
     }
 }
 
-// LDE leaf digests, one leaf per 16 lanes (index maps as in k_hash_lde_leaves): lane j < 8 of a group owns the j-th
-// word of each 8-column chunk.
-__global__ __launch_bounds__(256) void k_hash_lde_leaves_wide(const uint64_t* __restrict__ lde, size_t col_stride, uint32_t n_cols,
-                                                              unsigned log_n, unsigned rate_bits, uint64_t* __restrict__ digests,
-                                                              uint32_t batch_cols, size_t tree_words) {
+// LDE leaf digests, one leaf per quad (index maps as in k_hash_lde_leaves): lane q of a quad owns words q and q + 4 of
+// each 8-column chunk.
+__global__ __launch_bounds__(QUADS_PER_BLOCK * 4) void k_hash_lde_leaves_wide(const uint64_t* __restrict__ lde, size_t col_stride, uint32_t n_cols,
+                                                                              unsigned log_n, unsigned rate_bits, uint64_t* __restrict__ digests,
+                                                                              uint32_t batch_cols, size_t tree_words) {
     if (batch_cols) {   // see k_hash_lde_leaves
         const uint32_t c0 = blockIdx.y * batch_cols;
         lde += (size_t)c0 * col_stride;
         n_cols = n_cols - c0 < batch_cols ? n_cols - c0 : batch_cols;
         digests += (size_t)blockIdx.y * tree_words;
     }
-    __shared__ uint64_t lds[WIDE_GROUPS_PER_BLOCK * 24];
-    const uint32_t j = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const size_t pos = (size_t)blockIdx.x * WIDE_GROUPS_PER_BLOCK + g;
-    const bool live = (pos >> (log_n + rate_bits)) == 0;
+    const uint32_t q = threadIdx.x & 3;
+    const size_t rows = (size_t)1 << (log_n + rate_bits);
+    const size_t pos_raw = (size_t)blockIdx.x * QUADS_PER_BLOCK + (threadIdx.x >> 2);
+    const bool live = pos_raw < rows;                   // spare quads redo the last row and store nothing
+    const size_t pos = live ? pos_raw : rows - 1;
     const uint64_t* p = lde + pos;
-    gl32::F x = gl32::from_u64(0);
+    gl32::F x[3] = {gl32::from_u64(0), gl32::from_u64(0), gl32::from_u64(0)};
     if (n_cols <= 4) {   // hash_or_noop: a row of at most four elements IS its digest, zero-padded (a short last batch)
-        if (j < n_cols) x = gl32::from_u64(live ? p[(size_t)j * col_stride] : 0);
+        if (q < n_cols) x[0] = gl32::from_u64(p[(size_t)q * col_stride]);
     } else {
+        const pquad::Mds mds = pquad::mds_table(q);
 #pragma unroll 1
-        for (uint32_t c = 0; c < n_cols; c += 8) {
-            if (j < 8 && c + j < n_cols) x = gl32::from_u64(live ? p[(size_t)(c + j) * col_stride] : 0);  // overwrite-mode absorb
-            x = permute_wide(x, j, lds + g * 24);
+        for (uint32_t c = 0; c < n_cols; c += 8) {   // overwrite-mode absorb; n_cols is wave-uniform, so the whole quad walks the same chunks
+            if (c + q < n_cols) x[0] = gl32::from_u64(p[(size_t)(c + q) * col_stride]);
+            if (c + 4 + q < n_cols) x[1] = gl32::from_u64(p[(size_t)(c + 4 + q) * col_stride]);
+            pquad::permute(x, q, mds);
         }
     }
-    if (live && j < 4) {
+    if (live) {
         const uint32_t r = (uint32_t)(pos >> log_n), k = (uint32_t)(pos & (((size_t)1 << log_n) - 1));
         const size_t leaf = ((size_t)gl::bitrev32(r, rate_bits) << log_n) + gl::bitrev32(k, log_n);
-        digests[leaf * 4 + j] = gl::canon(gl32::to_u64(x));
+        digests[leaf * 4 + q] = gl::canon(gl32::to_u64(x[0]));
     }
 }
 
@@ -405,22 +468,23 @@ void launch_hash_lde_leaves_wide(hipStream_t st, const uint64_t* d_lde, size_t c
                                  unsigned rate_bits, uint64_t* d_digests, uint32_t batch_cols, size_t tree_words) {
     const size_t rows = (size_t)1 << (log_n + rate_bits);
     const uint32_t n_batches = batch_cols ? (n_cols + batch_cols - 1) / batch_cols : 1;
-    hipLaunchKernelGGL(k_hash_lde_leaves_wide, dim3((unsigned)((rows + WIDE_GROUPS_PER_BLOCK - 1) / WIDE_GROUPS_PER_BLOCK), n_batches), dim3(256), 0,
+    hipLaunchKernelGGL(k_hash_lde_leaves_wide, dim3((unsigned)((rows + QUADS_PER_BLOCK - 1) / QUADS_PER_BLOCK), n_batches), dim3(QUADS_PER_BLOCK * 4), 0,
                        st, d_lde, col_stride, n_cols, log_n, rate_bits, d_digests, batch_cols, tree_words);
 }
 
 void launch_fri_leaves_wide(hipStream_t st, const uint64_t* d_values, unsigned log_n, unsigned rate_bits,
                             unsigned arity_bits, uint64_t* d_digests) {
     const size_t leaves = (size_t)1 << (log_n - arity_bits + rate_bits);
-    const unsigned blocks = (unsigned)((leaves + WIDE_GROUPS_PER_BLOCK - 1) / WIDE_GROUPS_PER_BLOCK);
-    if (arity_bits == 4) hipLaunchKernelGGL(k_fri_leaves_wide<4>, dim3(blocks), dim3(256), 0, st, d_values, log_n, rate_bits, d_digests);
-    else if (arity_bits == 3) hipLaunchKernelGGL(k_fri_leaves_wide<3>, dim3(blocks), dim3(256), 0, st, d_values, log_n, rate_bits, d_digests);
-    else if (arity_bits == 2) hipLaunchKernelGGL(k_fri_leaves_wide<2>, dim3(blocks), dim3(256), 0, st, d_values, log_n, rate_bits, d_digests);
+    const unsigned blocks = (unsigned)((leaves + QUADS_PER_BLOCK - 1) / QUADS_PER_BLOCK);
+    const dim3 threads(QUADS_PER_BLOCK * 4);
+    if (arity_bits == 4) hipLaunchKernelGGL(k_fri_leaves_wide<4>, dim3(blocks), threads, 0, st, d_values, log_n, rate_bits, d_digests);
+    else if (arity_bits == 3) hipLaunchKernelGGL(k_fri_leaves_wide<3>, dim3(blocks), threads, 0, st, d_values, log_n, rate_bits, d_digests);
+    else if (arity_bits == 2) hipLaunchKernelGGL(k_fri_leaves_wide<2>, dim3(blocks), threads, 0, st, d_values, log_n, rate_bits, d_digests);
 }
 
 void launch_merkle_fused(hipStream_t st, const uint64_t* children, size_t n_children, unsigned levels, uint32_t n_trees, size_t tree_words) {
     // children level at `children`, its parents right behind it (level-major digest array)
-    hipLaunchKernelGGL(k_merkle_fused, dim3((unsigned)(n_children >> levels), n_trees), dim3(FUSED_GROUPS * 16), 0, st, children,
+    hipLaunchKernelGGL(k_merkle_fused, dim3((unsigned)(n_children >> levels), n_trees), dim3(FUSED_QUADS * 4), 0, st, children,
                        const_cast<uint64_t*>(children) + n_children * 4, n_children, levels, tree_words);
 }
 
