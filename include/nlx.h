@@ -624,6 +624,46 @@ size_t nlx_proof_max_bytes(const nlx_circuit* c);
 int32_t nlx_prove(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_inputs, uint8_t* proof_out,
                   size_t proof_cap, size_t* proof_len);
 
+/* ---- witness checker: which row, gate and constraint a witness breaks ----
+ * Evaluates the circuit on the TRACE ROWS of a witness (no LDE, no random combination: a row is bad iff one of its own gate's
+ * constraints is non-zero) and names the first thing that does not hold.  Call it when a proof does not verify. */
+#define NLX_CHECK_GATES   1u   /* every row's gate constraints (Gate::eval_unfiltered_base of the row's own gate) */
+#define NLX_CHECK_COPIES  2u   /* w[x] == w[sigma(x)] for every routed cell */
+#define NLX_CHECK_LOOKUPS 4u   /* circuits with tables: real LookupGate slots and LookupTableGate entries */
+#define NLX_CHECK_ALL     7u
+
+typedef struct {
+    uint32_t checked;      /* the NLX_CHECK_* bits that ran (LOOKUPS is dropped for a circuit without tables) */
+    uint32_t satisfied;    /* 1: nothing found by any check that ran */
+    /* gates: "first" = lowest row, then lowest constraint index (plonky2's order of the gate's constraints) */
+    uint64_t gate_rows_bad;            /* rows with at least one non-zero constraint */
+    uint32_t gate_row, gate_index /* into desc.gates */, gate_kind /* NLX_GATE_* */, gate_constraint;
+    uint64_t gate_value;               /* that constraint's canonical value */
+    /* copies: "first" = lowest row, then lowest column */
+    uint64_t copy_cells_bad;           /* routed cells x with w[x] != w[sigma(x)] */
+    uint32_t copy_row, copy_col, copy_to_row, copy_to_col;
+    uint64_t copy_value, copy_to_value;
+    /* lookups: "first" = lowest row, then lowest slot */
+    uint64_t lookup_slots_bad;
+    uint32_t lookup_row, lookup_slot, lookup_table, lookup_pad_;
+    uint64_t lookup_input, lookup_output;
+} nlx_witness_report;
+
+/* wires: num_wires x n column-major, host or device, as nlx_prove takes them; never written (unlike nlx_prove on a circuit with
+ * tables: the padding slots and multiplicity wires that nlx_prove fills are left alone and are not checked).  public_inputs feed
+ * PublicInputGate through hash_no_pad, as in nlx_prove.  what: a non-empty set of NLX_CHECK_* bits.
+ * Returns NLX_OK whenever the check ran - the verdict is in *report, which is zero-filled before anything else happens; when
+ * report->satisfied == 0, nlx_last_error holds one line naming the row, the gate's plonky2 name, the constraint index and its
+ * value, or the two cells of the copy, or the lookup slot.  NLX_E_INVAL: a NULL argument, `what` outside 1 .. 7, or a sigma
+ * value that lies in no coset k_i H (its position is in the message).  Works the same under both hashers: nothing here hashes
+ * except the host hash_no_pad of the public inputs.
+ * The first check of a circuit builds what later checks reuse and the circuit keeps until nlx_circuit_destroy: for
+ * NLX_CHECK_GATES the constants' values on H (one forward transform of the constants commitment's coefficients), for
+ * NLX_CHECK_COPIES the sigma values decoded to (row, column).  A circuit that is never checked pays neither time nor memory for
+ * them at nlx_circuit_build. */
+int32_t nlx_circuit_check_witness(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_inputs, uint32_t what,
+                                  nlx_witness_report* report);
+
 /* ---- stage-level entry points: the fine seam for callers that keep plonky2's own
  * prove_with_partition_witness loop and replace it stage by stage (SURVEY.md §8b call list) ---- */
 

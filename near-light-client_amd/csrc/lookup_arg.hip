@@ -307,6 +307,45 @@ void launch_lookup_polys(hipStream_t st, const LookupShape& s, const LookupTable
     hipLaunchKernelGGL(k_lk_scan, dim3(nc * s.num_luts), dim3(LK_SCAN_THREADS), 0, st, s, d_tabs, n, d_deltas, d_cols);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// the witness checker's lookup pass (nlx_circuit_check_witness, NLX_CHECK_LOOKUPS)
+// ---------------------------------------------------------------------------------------------------------------------
+// One lane per item of table blockIdx.y: the `lookups` real LookupGate slots (input in the table AND the output that pair's -
+// k_lk_count looks at the input alone), then the `len` LookupTableGate entries (entry e holds pair e).  Padding slots and
+// multiplicity wires are nlx_prove's to write and are not looked at.  Slot numbers are the row's: 2 slot / 3 slot is the input wire.
+namespace {
+__global__ __launch_bounds__(256) void k_check_lookups(LookupShape s, const LookupTableDev* __restrict__ tabs,
+                                                       const uint64_t* __restrict__ wires, size_t n, CheckBlock* __restrict__ block) {
+    const LookupTableDev t = tabs[blockIdx.y];
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    uint32_t row = 0, slot = 0;
+    if (x < t.lookups) {
+        row = t.last_lu + x / s.n_lu_slots;
+        slot = x % s.n_lu_slots;
+        const uint64_t in = wires[(size_t)(2 * slot) * n + row], out = wires[(size_t)(2 * slot + 1) * n + row];
+        const int32_t idx = in <= 0xFFFF ? t.idx_of[in] : -1;
+        bad = idx < 0 || out != (uint64_t)(t.pairs[idx] >> 16);
+    } else if (x - t.lookups < t.len) {
+        const uint32_t e = x - t.lookups;
+        row = t.first_lut - e / s.n_lut_slots;
+        slot = e % s.n_lut_slots;
+        const uint32_t pr = t.pairs[e];
+        bad = wires[(size_t)(3 * slot) * n + row] != (uint64_t)(pr & 0xFFFF) || wires[(size_t)(3 * slot + 1) * n + row] != (uint64_t)(pr >> 16);
+    }
+    const unsigned long long m = __ballot(bad);
+    if (m == 0) return;
+    if ((threadIdx.x & 63) == (uint32_t)__ffsll((long long)m) - 1) atomicAdd(&block->lookup_slots_bad, (unsigned long long)__popcll(m));
+    if (bad) atomicMin(&block->lookup_first, ((unsigned long long)row << 32) | slot);
+}
+}  // namespace
+void launch_check_lookups(hipStream_t st, const LookupShape& s, const LookupTableDev* d_tabs, const LookupTableDev* h_tabs,
+                          const uint64_t* d_wires, size_t n, CheckBlock* d_block) {
+    uint32_t max_items = 1;
+    for (uint32_t t = 0; t < s.num_luts; t++) max_items = std::max(max_items, h_tabs[t].lookups + h_tabs[t].len);
+    hipLaunchKernelGGL(k_check_lookups, dim3((max_items + 255) / 256, s.num_luts), dim3(256), 0, st, s, d_tabs, d_wires, n, d_block);
+}
+
 void launch_lookup_terms(hipStream_t st, const LookupTermsParams& p) {
     const size_t L = (size_t)1 << (p.log_n + p.rate_bits);
     hipLaunchKernelGGL(k_lookup_terms, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, st, p);

@@ -124,6 +124,11 @@ struct nlx_circuit {
     int32_t* d_idx_of = nullptr;      // [tables][65536]
     uint32_t* d_mult = nullptr;       // multiplicity counters of all tables, then the error word
     size_t mult_words = 0;
+    // the witness checker's (nlx_circuit_check_witness): made by the first check that needs them, null in a circuit never checked
+    uint64_t* d_consts_h = nullptr;     // [n_consts_all][n]: the constants' values on H (build keeps coefficients and LDE only)
+    uint32_t* d_sigma_row = nullptr;    // [routed][n]: sigma(x) decoded to its row ...
+    uint16_t* d_sigma_col = nullptr;    // ... and column
+    CheckBlock* d_check = nullptr;      // the passes' counters and minima
     StageClock clock;
     size_t n() const { return (size_t)1 << d.degree_bits; }
     size_t L() const { return (size_t)1 << (d.degree_bits + d.rate_bits); }
@@ -479,6 +484,10 @@ void nlx_circuit_destroy(nlx_circuit* c) NLX_TRY {
     ctx->release(c->d_mult);
     ctx->release(c->d_tabs);
     ctx->release(c->d_bad);
+    ctx->release(c->d_consts_h);
+    ctx->release(c->d_sigma_row);
+    ctx->release(c->d_sigma_col);
+    ctx->release(c->d_check);
     delete c;   // and with it the constants + sigmas commitment and the stage clock's events
 } NLX_CATCH_VOID(nullptr)
 
@@ -869,6 +878,177 @@ int32_t nlx_batch_prove(nlx_circuit* const* workers, uint32_t n_workers, nlx_pro
         return nlx_prove(c, job.wires, job.public_inputs, job.proof_out, job.proof_cap, &job.proof_len);
     });
 } NLX_CATCH(nullptr)
+
+// ---- the witness checker ----
+}  // extern "C"
+
+namespace {
+// plonky2's type names, by NLX_GATE_*
+const char* const GATE_NAMES[NLX_GATE_KIND_MAX + 1] = {
+    "NoopGate", "ConstantGate", "PublicInputGate", "ArithmeticGate", "BaseSumGate", "PoseidonGate", "ArithmeticExtensionGate",
+    "MulExtensionGate", "ReducingGate", "ReducingExtensionGate", "PoseidonMdsGate", "ExponentiationGate", "RandomAccessGate",
+    "CosetInterpolationGate", "U32AddManyGate", "U32ArithmeticGate", "U32SubtractionGate", "U32RangeCheckGate", "ComparisonGate",
+    "LookupGate", "LookupTableGate"};
+
+// the sigma values as cells, once per circuit: kept only when every cell decoded
+int32_t ensure_sigma_cells(nlx_circuit* c, Scratch& scratch) {
+    if (c->d_sigma_row) return NLX_OK;
+    nlx_ctx* ctx = c->ctx;
+    const nlx_circuit_desc& d = c->d;
+    const size_t n = c->n(), cells = (size_t)d.num_routed_wires * n;
+    const uint32_t routed = d.num_routed_wires;
+    std::vector<uint64_t> h(2 * (size_t)routed);   // k_i^n | 1 / k_i
+    for (uint32_t i = 0; i < routed; i++) {
+        h[i] = gl::exp_pow2(c->k_is[i], d.degree_bits);
+        h[routed + i] = gl::inv(c->k_is[i]);
+    }
+    uint64_t* d_h = scratch.alloc_as<uint64_t>(h.size() * 8);
+    uint32_t* d_row = (uint32_t*)ctx->alloc(cells * 4);
+    uint16_t* d_col = (uint16_t*)ctx->alloc(cells * 2);
+    auto give_back = [&](int32_t rc) {
+        ctx->release(d_row);
+        ctx->release(d_col);
+        return rc;
+    };
+    if (!d_h || !d_row || !d_col) return give_back(ctx->fail(NLX_E_NOMEM, "out of device memory (sigma cells)"));
+    hipError_t e = hipMemcpy(d_h, h.data(), h.size() * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return give_back(ctx->hip_fail(e, "hipMemcpy(coset tables)"));
+    launch_sigma_decode(ctx->stream, c->d_sigma_values, c->d_k_is, d_h, d_h + routed, ctx->tables.fwd[d.degree_bits],
+                        ctx->tables.inv[d.degree_bits], d.degree_bits, routed, d_row, d_col, c->d_check);
+    CheckBlock b;
+    int32_t rc = fetch(ctx, &b, c->d_check, sizeof b);
+    if (rc) return give_back(rc);
+    if (b.sigma_undecodable != CHECK_NONE)
+        return give_back(ctx->fail(NLX_E_INVAL, "sigma value at row %llu, column %llu lies in no coset k_i H of the descriptor's k_is",
+                                   b.sigma_undecodable % n, b.sigma_undecodable / n));
+    c->d_sigma_row = d_row;
+    c->d_sigma_col = d_col;
+    return NLX_OK;
+}
+
+int32_t check_witness(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_inputs, uint32_t what, nlx_witness_report* rep,
+                      Scratch& scratch) {
+    nlx_ctx* ctx = c->ctx;
+    const nlx_circuit_desc& d = c->d;
+    hipStream_t st = ctx->stream;
+    const size_t n = c->n();
+    if (!d.num_luts) what &= ~NLX_CHECK_LOOKUPS;
+    rep->checked = what;
+    rep->satisfied = 1;
+    if (!what) return NLX_OK;
+    Staged sw(ctx, wires, (size_t)d.num_wires * n * 8, true, false);
+    NLX_RC(sw.status);
+    const uint64_t* d_w = sw.as<uint64_t>();
+    if (!c->d_check) {
+        c->d_check = (CheckBlock*)ctx->alloc(256);
+        if (!c->d_check) return ctx->fail(NLX_E_NOMEM, "out of device memory (check block)");
+    }
+    launch_check_reset(st, c->d_check);
+    CheckGatesParams gp{};
+    if (what & NLX_CHECK_GATES) {
+        if (!c->d_consts_h) {
+            // the constants on H: one forward transform of the commitment's coefficients, no coset scale (the LDE lives on g H)
+            uint64_t* t = (uint64_t*)ctx->alloc((size_t)c->n_consts_all * n * 8);
+            if (!t) return ctx->fail(NLX_E_NOMEM, "out of device memory (constants on H)");
+            launch_lde_dit(st, ctx->tables, c->cs->coeffs_br, n, t, n, c->n_consts_all, d.degree_bits, 0, nullptr);
+            c->d_consts_h = t;
+        }
+        std::vector<uint64_t> h_pis(public_inputs, public_inputs + d.num_public_inputs);
+        hash_no_pad_host(h_pis.data(), h_pis.size(), gp.q.pih);
+        gp.q.gates = c->d_gates;
+        gp.q.w_n_table = ctx->tables.fwd[d.degree_bits];
+        gp.q.log_n = d.degree_bits; gp.q.rate_bits = d.rate_bits; gp.q.n_gates = d.num_gates; gp.q.n_selectors = d.num_selectors;
+        gp.q.n_consts_all = c->n_consts_all; gp.q.num_wires = d.num_wires;
+        gp.q.gate_const0 = d.num_selectors + c->n_lk_sel;
+        gp.consts = c->d_consts_h;
+        gp.wires = d_w;
+        gp.block = c->d_check;
+        launch_check_gates(st, gp, 0xFFFFFFFFu);
+    }
+    if (what & NLX_CHECK_COPIES) {
+        NLX_RC(ensure_sigma_cells(c, scratch));
+        launch_check_copies(st, d_w, d.degree_bits, d.num_routed_wires, c->d_sigma_row, c->d_sigma_col, c->d_check);
+    }
+    if (what & NLX_CHECK_LOOKUPS) launch_check_lookups(st, c->lk, c->d_tabs, c->h_tabs.data(), d_w, n, c->d_check);
+    CheckBlock b;
+    NLX_RC(fetch(ctx, &b, c->d_check, sizeof b));
+    rep->gate_rows_bad = b.gate_rows_bad;
+    rep->copy_cells_bad = b.copy_cells_bad;
+    rep->lookup_slots_bad = b.lookup_slots_bad;
+    rep->satisfied = !(b.gate_rows_bad || b.copy_cells_bad || b.lookup_slots_bad);
+    if (rep->satisfied) return NLX_OK;
+    // the details of each first finding: a handful of words from the device, on the failing path only
+    auto word = [&](const uint64_t* src, uint64_t* dst) { return fetch(ctx, dst, src, 8); };
+    char line[3][160] = {"", "", ""};
+    if (b.gate_rows_bad) {
+        rep->gate_row = (uint32_t)(b.gate_first >> 32);
+        launch_check_gates(st, gp, rep->gate_row);
+        NLX_RC(fetch(ctx, &b, c->d_check, sizeof b));
+        rep->gate_index = b.gate_index;
+        rep->gate_kind = c->gates[b.gate_index].kind;
+        rep->gate_constraint = b.gate_constraint;
+        rep->gate_value = b.gate_value;
+        snprintf(line[0], sizeof line[0], "row %u (%s, gate %u): constraint %u = %llu, %llu row(s) with a non-zero constraint", rep->gate_row,
+                 GATE_NAMES[rep->gate_kind], rep->gate_index, rep->gate_constraint, (unsigned long long)rep->gate_value,
+                 (unsigned long long)rep->gate_rows_bad);
+    }
+    if (b.copy_cells_bad) {
+        rep->copy_row = (uint32_t)(b.copy_first >> 32);
+        rep->copy_col = (uint32_t)b.copy_first;
+        const size_t idx = (size_t)rep->copy_col * n + rep->copy_row;
+        uint16_t tc = 0;
+        NLX_RC(fetch(ctx, &rep->copy_to_row, c->d_sigma_row + idx, 4));
+        NLX_RC(fetch(ctx, &tc, c->d_sigma_col + idx, 2));
+        rep->copy_to_col = tc;
+        NLX_RC(word(d_w + idx, &rep->copy_value));
+        NLX_RC(word(d_w + (size_t)tc * n + rep->copy_to_row, &rep->copy_to_value));
+        snprintf(line[1], sizeof line[1], "copy: wire %u of row %u = %llu but sigma sends it to wire %u of row %u = %llu, %llu cell(s) differ from their copy",
+                 rep->copy_col, rep->copy_row, (unsigned long long)rep->copy_value, rep->copy_to_col, rep->copy_to_row,
+                 (unsigned long long)rep->copy_to_value, (unsigned long long)rep->copy_cells_bad);
+    }
+    if (b.lookup_slots_bad) {
+        rep->lookup_row = (uint32_t)(b.lookup_first >> 32);
+        rep->lookup_slot = (uint32_t)b.lookup_first;
+        bool table_row = false;
+        for (uint32_t t = 0; t < d.num_luts; t++)
+            if (rep->lookup_row >= c->h_tabs[t].last_lu && rep->lookup_row <= c->h_tabs[t].first_lut) {
+                rep->lookup_table = t;
+                table_row = rep->lookup_row >= c->h_tabs[t].last_lut;
+            }
+        const uint32_t w0 = (table_row ? 3 : 2) * rep->lookup_slot;
+        NLX_RC(word(d_w + (size_t)w0 * n + rep->lookup_row, &rep->lookup_input));
+        NLX_RC(word(d_w + (size_t)(w0 + 1) * n + rep->lookup_row, &rep->lookup_output));
+        snprintf(line[2], sizeof line[2], "lookup: row %u (%s) slot %u holds (%llu, %llu), not a pair of table %u%s, %llu slot(s) wrong", rep->lookup_row,
+                 GATE_NAMES[table_row ? NLX_GATE_LOOKUP_TABLE : NLX_GATE_LOOKUP], rep->lookup_slot, (unsigned long long)rep->lookup_input,
+                 (unsigned long long)rep->lookup_output, rep->lookup_table, table_row ? " at that entry" : "",
+                 (unsigned long long)rep->lookup_slots_bad);
+    }
+    std::string msg = "the witness does not satisfy the circuit: ";
+    bool any = false;
+    for (const auto& l : line)
+        if (l[0]) {
+            if (any) msg += "; ";
+            msg += l;
+            any = true;
+        }
+    ctx->err = msg;
+    return NLX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t nlx_circuit_check_witness(nlx_circuit* c, const uint64_t* wires, const uint64_t* public_inputs, uint32_t what,
+                                  nlx_witness_report* report) NLX_TRY {
+    if (!c) return NLX_E_INVAL;
+    nlx_ctx* ctx = c->ctx;
+    if (report) memset(report, 0, sizeof *report);
+    if (!wires || !report || (!public_inputs && c->d.num_public_inputs)) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    if (what < 1 || what > NLX_CHECK_ALL) return ctx->fail(NLX_E_INVAL, "what = %u: a non-empty set of NLX_CHECK_* bits (1 .. 7)", what);
+    (void)hipSetDevice(ctx->device);
+    Scratch scratch(ctx);
+    return scratch.finish(check_witness(c, wires, public_inputs, what, report, scratch));
+} NLX_CATCH(c ? c->ctx : nullptr)
 
 // ---- stage-level entry points (the fine seam of INTEGRATION.md §3) ----
 

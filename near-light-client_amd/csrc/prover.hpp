@@ -93,7 +93,38 @@ struct LookupTermsParams {
 };
 void launch_lookup_terms(hipStream_t st, const LookupTermsParams& p);
 
-constexpr int FRI_VIEWS = 33;   // FRI_MAX_ORACLES (fri.hpp) + the trailing column group of plonky2's lookup argument
+// ---- the witness checker (nlx_circuit_check_witness; kernels at the end of prover_kernels.hip) ----
+// The device block every pass reports into (zeroed / set to "none" by launch_check_reset).  A "first" key packs
+// row << 32 | (constraint | column | slot): the smallest key is the lowest row, then the lowest index inside it.
+struct CheckBlock {
+    unsigned long long gate_rows_bad, gate_first;      // gate_first = row << 32 | constraint
+    unsigned long long copy_cells_bad, copy_first;     // row << 32 | column
+    unsigned long long lookup_slots_bad, lookup_first; // row << 32 | slot
+    unsigned long long sigma_undecodable;              // lowest cell index column * n + row whose sigma value lies in no coset
+    unsigned long long gate_value;                     // the report launch: the first bad row's gate, constraint and value
+    uint32_t gate_index, gate_constraint;
+};
+constexpr unsigned long long CHECK_NONE = ~0ull;
+void launch_check_reset(hipStream_t st, CheckBlock* d_block);
+struct CheckGatesParams {
+    QuotientParams q;        // what eval_gate reads: gates, n_gates, gate_const0, pih, w_n_table, log_n (cs / wires unused)
+    const uint64_t* consts;  // [n_consts_all][n]: the constants' values on H
+    const uint64_t* wires;   // [num_wires][n]
+    CheckBlock* block;
+};
+// every row; then, when report_row != 0xFFFFFFFF, that row alone: its gate index, first constraint and value into the block
+void launch_check_gates(hipStream_t st, const CheckGatesParams& p, uint32_t report_row);
+// sigma values k_c' w^r' -> (r', c'); kn / kinv: k_i^n and 1 / k_i (device, routed entries); an undecodable cell gets column
+// 0xFFFF and enters block->sigma_undecodable
+void launch_sigma_decode(hipStream_t st, const uint64_t* d_sigmas, const uint64_t* d_k_is, const uint64_t* d_kn, const uint64_t* d_kinv,
+                         const uint64_t* d_w_n_table, const uint64_t* d_w_n_inv_table, unsigned log_n, uint32_t routed,
+                         uint32_t* d_to_row, uint16_t* d_to_col, CheckBlock* d_block);
+void launch_check_copies(hipStream_t st, const uint64_t* d_wires, unsigned log_n, uint32_t routed, const uint32_t* d_to_row,
+                         const uint16_t* d_to_col, CheckBlock* d_block);
+void launch_check_lookups(hipStream_t st, const LookupShape& s, const LookupTableDev* d_tabs, const LookupTableDev* h_tabs,
+                          const uint64_t* d_wires, size_t n, CheckBlock* d_block);
+
+constexpr int FRI_VIEWS = 33;  // FRI_MAX_ORACLES (fri.hpp) + the trailing column group of plonky2's lookup argument
 struct FriCombineParams {
     const uint64_t* tables[FRI_VIEWS];  // LDE column groups in the zeta batch's order: the oracles, then (plonky2 with lookup
                                         // tables) the trailing columns of one of them as a group of their own

@@ -379,9 +379,9 @@ __device__ __forceinline__ void mds_canon(uint64_t (&s)[12]) {
 // own device schedule (round 4): linear layers on the matrix cores with the next round's constants in the recombination
 // (gl32::mds_layer_mfma), rounds 4 .. 24 as seven fused blocks whose S-box hooks emit `computed - wire` and continue from the
 // wire (gl32::partial_block3).  NLX_POSEIDON_GATE_FAST_BASIS keeps round 3's evaluation (vector-pipe layers, fast formulation).
-template <class WireFn>
+template <class WireFn, class Acc>
 struct GateBlockSboxes {
-    GateAcc& acc;
+    Acc& acc;
     WireFn W;
     uint32_t r0;   // the block's first partial round (0 .. 18): its S-box input is wire 65 + r0, its constraint 41 + r0
     __device__ __forceinline__ gl32::F at(uint32_t r, gl32::F computed) const {
@@ -396,8 +396,8 @@ struct GateBlockSboxes {
     __device__ __forceinline__ void before_matrix_pass() const { acc.stash(); }
 };
 
-template <class WireFn>
-__device__ __forceinline__ void gate_poseidon_mx(WireFn W, GateAcc& acc, uint32_t parts) {
+template <class WireFn, class Acc>
+__device__ __forceinline__ void gate_poseidon_mx(WireFn W, Acc& acc, uint32_t parts) {
     const uint64_t* RC = poseidon::RC_DEV;
     const uint64_t* rcb = poseidon::LAYER_RCB_DEV;   // [l * 24 ..]: the constants round l adds, as the recombination's seeds
     // The matrix operands depend on the lane only: left to itself hipcc hoists them out of k_quotient's item loop - ~32 registers
@@ -455,8 +455,8 @@ __device__ __forceinline__ void gate_poseidon_mx(WireFn W, GateAcc& acc, uint32_
         gl32::mds_layer_mfma<2>(t, afrag, rcb + 4 * 24);
 #pragma unroll 1
         for (uint32_t b = 0; b < NLX_POSEIDON_N_BLOCKS; b++)   // partial rounds 0 .. 20 (rounds 4 .. 24)
-            gl32::partial_block3<NLX_POSEIDON_BLOCK_GAMMA21>(t, op, poseidon::BLOCK_KAPPA_DEV + b * 6, GateBlockSboxes<WireFn>{acc, W, 3 * b});
-        t[0] = GateBlockSboxes<WireFn>{acc, W, 21}.first(t[0]);   // partial round 21 (round 25)
+            gl32::partial_block3<NLX_POSEIDON_BLOCK_GAMMA21>(t, op, poseidon::BLOCK_KAPPA_DEV + b * 6, GateBlockSboxes<WireFn, Acc>{acc, W, 3 * b});
+        t[0] = GateBlockSboxes<WireFn, Acc>{acc, W, 21}.first(t[0]);   // partial round 21 (round 25)
         gl32::mds_layer_mfma<2>(t, afrag, rcb + 26 * 24);
         check_against_wires(63, 87);
     }
@@ -477,8 +477,8 @@ __device__ __forceinline__ void gate_poseidon_mx(WireFn W, GateAcc& acc, uint32_
 
 // round 3's evaluation (vector-pipe layers, upstream's fast formulation of the partial rounds): kept for the parts NLX_PGATE_MX
 // leaves to it, and as the ablation reference
-template <class WireFn>
-__device__ __forceinline__ void gate_poseidon_fast(WireFn W, GateAcc& acc, uint32_t parts) {
+template <class WireFn, class Acc>
+__device__ __forceinline__ void gate_poseidon_fast(WireFn W, Acc& acc, uint32_t parts) {
     const uint64_t* RC = poseidon::RC_DEV;
     uint64_t st[12];
     if (parts & 1u) {
@@ -590,16 +590,18 @@ __device__ __forceinline__ void gate_poseidon_fast(WireFn W, GateAcc& acc, uint3
 #ifndef NLX_PGATE_MX
 #define NLX_PGATE_MX 0u
 #endif
-template <class WireFn>
-__device__ __forceinline__ void gate_poseidon(WireFn W, GateAcc& acc, uint32_t parts) {
+template <class WireFn, class Acc>
+__device__ __forceinline__ void gate_poseidon(WireFn W, Acc& acc, uint32_t parts) {
     if (parts & NLX_PGATE_MX) gate_poseidon_mx(W, acc, parts & NLX_PGATE_MX);
     if (parts & ~NLX_PGATE_MX) gate_poseidon_fast(W, acc, parts & ~NLX_PGATE_MX);
 }
 
 // One gate's unfiltered constraints at this lane's point, folded into `acc` with the alpha powers (Gate::eval_unfiltered_base).
 // W(c): wire c of the point; CC(c): constants column c (selectors first) of the point; n = 2^log_n.
-template <class WireFn, class ConstFn>
-__device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParams& p, WireFn W, ConstFn CC, GateAcc& acc, size_t n,
+// Acc: GateAcc in the quotient kernels; the witness checker's CheckAcc records the lowest non-zero constraint instead (an
+// accumulator brings emit, emit_at, the counter k and stash).
+template <class WireFn, class ConstFn, class Acc>
+__device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParams& p, WireFn W, ConstFn CC, Acc& acc, size_t n,
                                           uint32_t parts) {
     switch (gd.kind) {
         case NLX_GATE_CONSTANT:
@@ -1510,6 +1512,158 @@ __global__ void k_ext_pow_table(uint64_t* __restrict__ out, uint64_t a, uint64_t
 }
 void launch_ext_pow_table(hipStream_t st, uint64_t* d_out, const uint64_t alpha[2], uint32_t count) {
     hipLaunchKernelGGL(k_ext_pow_table, dim3((count + 63) / 64), dim3(64), 0, st, d_out, alpha[0], alpha[1], count);
+}
+
+// =====================================================================================
+// the witness checker (nlx_circuit_check_witness): the circuit on the TRACE ROWS of a witness
+// =====================================================================================
+// eval_gate's accumulator for an exact answer: no alpha powers, the lowest non-zero constraint index and its canonical value.
+// The gates hand over loose values (any u64 congruent to the constraint), hence the canon; PoseidonMdsGate emits out of order
+// (emit_at), hence "lowest index" and not "first emitted".
+struct CheckAcc {
+    uint32_t k, first;
+    uint64_t value;
+    __device__ __forceinline__ void reset() { k = 0; first = 0xFFFFFFFFu; value = 0; }
+    __device__ __forceinline__ void stash() {}
+    __device__ __forceinline__ void emit_at(uint32_t idx, uint64_t c) {
+        const uint64_t v = gl::canon(c);
+        if (v != 0 && idx < first) { first = idx; value = v; }
+    }
+    __device__ __forceinline__ void emit(uint64_t c) { emit_at(k++, c); }
+};
+
+__global__ void k_check_reset(CheckBlock* __restrict__ b) {
+    b->gate_rows_bad = b->copy_cells_bad = b->lookup_slots_bad = 0;
+    b->gate_first = b->copy_first = b->lookup_first = b->sigma_undecodable = CHECK_NONE;
+    b->gate_value = 0;
+    b->gate_index = b->gate_constraint = 0;
+}
+void launch_check_reset(hipStream_t st, CheckBlock* d_block) { hipLaunchKernelGGL(k_check_reset, dim3(1), dim3(1), 0, st, d_block); }
+
+// a wave's count of set lanes onto a counter, and the smallest key of its set lanes into a minimum: one atomic per lane that has
+// something to say (bad cells are rare, and a witness that is wrong everywhere is still only n atomics)
+__device__ __forceinline__ void check_report(bool bad, unsigned long long key, unsigned long long* count, unsigned long long* first) {
+    const unsigned long long m = __ballot(bad);
+    if (m == 0) return;
+    if ((threadIdx.x & 63) == (uint32_t)__ffsll((long long)m) - 1) atomicAdd(count, (unsigned long long)__popcll(m));
+    if (bad) atomicMin(first, key);
+}
+
+// One lane per trace row: the constraints of the row's OWN gate - the one whose selector column holds its index there -
+// unfiltered, on the witness and the constants' values on H, both read column-major straight from memory (coalesced; a gate reads
+// each of its wires once or twice).  Control flow stays wave-uniform as in k_quotient: the loop runs over the gate list with the
+// descriptor in scalar registers, a gate no row of the wave carries is skipped, and lanes whose row carries another gate compute
+// values nobody reads (every address depends on the descriptor alone).  No lane leaves early: the rows past n redo the last row.
+// report_row == 0xFFFFFFFF: count the bad rows and find the first (row, constraint); otherwise the block holding that row runs
+// again and its lane writes the gate, the constraint and the value out (plain stores: one lane).
+__global__ __launch_bounds__(256) void k_check_gates(CheckGatesParams p, uint32_t row0, uint32_t report_row) {
+    const size_t n = (size_t)1 << p.q.log_n;
+    const size_t raw = (size_t)row0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = raw < n;
+    const size_t row = live ? raw : n - 1;
+    auto W = [&](uint32_t c) { return p.wires[(size_t)c * n + row]; };
+    auto CC = [&](uint32_t c) { return p.consts[(size_t)c * n + row]; };
+    uint32_t first = 0xFFFFFFFFu, gate = 0;
+    uint64_t value = 0;
+    for (uint32_t g = 0; g < p.q.n_gates; g++) {
+        const GateDev gd = p.q.gates[g];
+        const bool mine = live && CC(gd.selector_index) == (uint64_t)gd.index;
+        if (__ballot(mine) == 0) continue;
+        CheckAcc acc;
+        acc.reset();
+        eval_gate(gd, p.q, W, CC, acc, n, 7u);
+        if (mine && acc.first != 0xFFFFFFFFu) {
+            first = acc.first;
+            value = acc.value;
+            gate = g;
+        }
+    }
+    const bool bad = first != 0xFFFFFFFFu;
+    if (report_row == 0xFFFFFFFFu) {
+        check_report(bad, ((unsigned long long)row << 32) | first, &p.block->gate_rows_bad, &p.block->gate_first);
+    } else if (bad && row == report_row) {
+        p.block->gate_index = gate;
+        p.block->gate_constraint = first;
+        p.block->gate_value = value;
+    }
+}
+void launch_check_gates(hipStream_t st, const CheckGatesParams& p, uint32_t report_row) {
+    const size_t n = (size_t)1 << p.q.log_n;
+    if (report_row == 0xFFFFFFFFu)
+        hipLaunchKernelGGL(k_check_gates, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p, 0u, report_row);
+    else
+        hipLaunchKernelGGL(k_check_gates, dim3(1), dim3(256), 0, st, p, report_row & ~255u, report_row);
+}
+
+// Sigma values back to cells, one lane per routed cell x = (row r, column c): sigma(x) = k_c' w^r' as a field element.
+//   1. the identity k_c w^r first - most cells of a circuit are routed to themselves;
+//   2. else the coset: v^n = k_c'^n picks c' (the shifts' n-th powers are distinct exactly when their cosets are);
+//   3. then the logarithm of u = v / k_c' in the subgroup of order n = 2^k, bit by bit from the low end: with the low i bits of
+//      the exponent cleared, u^(2^(k-1-i)) is 1 or -1 as bit i is 0 or 1 (k (k - 1) / 2 squarings);
+//   4. and k_c' w^r' == v once more, so that whatever is stored is exact; anything else is undecodable (column 0xFFFF).
+// The shifts are the descriptor's k_is, whatever they are.
+__global__ __launch_bounds__(256) void k_sigma_decode(const uint64_t* __restrict__ sigmas, const uint64_t* __restrict__ k_is,
+                                                      const uint64_t* __restrict__ kn, const uint64_t* __restrict__ kinv,
+                                                      const uint64_t* __restrict__ w_tab, const uint64_t* __restrict__ w_inv_tab,
+                                                      unsigned log_n, uint32_t routed, uint32_t* __restrict__ to_row,
+                                                      uint16_t* __restrict__ to_col, CheckBlock* __restrict__ block) {
+    const size_t n = (size_t)1 << log_n;
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const uint32_t c = blockIdx.y, half = (uint32_t)(n >> 1);
+    const size_t idx = (size_t)c * n + r;
+    const uint64_t v = sigmas[idx];
+    if (v == gl::mul(k_is[c], root_pow(w_tab, (uint32_t)r, half))) {
+        to_row[idx] = (uint32_t)r;
+        to_col[idx] = (uint16_t)c;
+        return;
+    }
+    const uint64_t vn = gl::exp_pow2(v, log_n);
+    uint32_t tc = 0xFFFFu, tr = 0;
+    for (uint32_t j = 0; j < routed; j++)
+        if (vn == kn[j]) { tc = j; break; }
+    if (tc != 0xFFFFu) {
+        uint64_t cur = gl::mul(v, kinv[tc]);
+        for (unsigned i = 0; i < log_n; i++) {
+            if (gl::exp_pow2(cur, log_n - 1 - i) != 1) {
+                tr |= 1u << i;
+                if (i + 1 < log_n) cur = gl::mul(cur, w_inv_tab[(size_t)1 << i]);
+            }
+        }
+        if (gl::mul(k_is[tc], root_pow(w_tab, tr, half)) != v) tc = 0xFFFFu;
+    }
+    if (tc == 0xFFFFu) atomicMin(&block->sigma_undecodable, (unsigned long long)idx);
+    to_row[idx] = tr;
+    to_col[idx] = (uint16_t)tc;
+}
+void launch_sigma_decode(hipStream_t st, const uint64_t* d_sigmas, const uint64_t* d_k_is, const uint64_t* d_kn, const uint64_t* d_kinv,
+                         const uint64_t* d_w_n_table, const uint64_t* d_w_n_inv_table, unsigned log_n, uint32_t routed,
+                         uint32_t* d_to_row, uint16_t* d_to_col, CheckBlock* d_block) {
+    const size_t n = (size_t)1 << log_n;
+    hipLaunchKernelGGL(k_sigma_decode, dim3((unsigned)((n + 255) / 256), routed), dim3(256), 0, st, d_sigmas, d_k_is, d_kn, d_kinv,
+                       d_w_n_table, d_w_n_inv_table, log_n, routed, d_to_row, d_to_col, d_block);
+}
+
+// One lane per routed cell x: w[x] against w[sigma(x)] (canonical forms).  Both ends of a broken copy are bad cells.
+__global__ __launch_bounds__(256) void k_check_copies(const uint64_t* __restrict__ wires, unsigned log_n, uint32_t routed,
+                                                      const uint32_t* __restrict__ to_row, const uint16_t* __restrict__ to_col,
+                                                      CheckBlock* __restrict__ block) {
+    const size_t n = (size_t)1 << log_n;
+    const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t c = blockIdx.y;
+    bool bad = false;
+    if (r < n) {
+        const size_t idx = (size_t)c * n + r;
+        const uint32_t tc = to_col[idx], tr = to_row[idx];
+        if (tc < routed && tr < n) bad = gl::canon(wires[idx]) != gl::canon(wires[(size_t)tc * n + tr]);
+    }
+    check_report(bad, ((unsigned long long)r << 32) | c, &block->copy_cells_bad, &block->copy_first);
+}
+void launch_check_copies(hipStream_t st, const uint64_t* d_wires, unsigned log_n, uint32_t routed, const uint32_t* d_to_row,
+                         const uint16_t* d_to_col, CheckBlock* d_block) {
+    const size_t n = (size_t)1 << log_n;
+    hipLaunchKernelGGL(k_check_copies, dim3((unsigned)((n + 255) / 256), routed), dim3(256), 0, st, d_wires, log_n, routed, d_to_row,
+                       d_to_col, d_block);
 }
 
 }  // namespace nlx

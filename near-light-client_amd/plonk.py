@@ -134,6 +134,36 @@ class SyntheticCircuit:
         return d
 
 
+CHECK_GATES, CHECK_COPIES, CHECK_LOOKUPS, CHECK_ALL = 1, 2, 4, 7
+_CHECK_BITS = {"gates": CHECK_GATES, "copies": CHECK_COPIES, "lookups": CHECK_LOOKUPS, "all": CHECK_ALL}
+
+
+class WitnessReport(ctypes.Structure):
+    """nlx_witness_report (include/nlx.h): what nlx_circuit_check_witness found; `message` is the library's line"""
+    _fields_ = [("checked", ctypes.c_uint32), ("satisfied", ctypes.c_uint32),
+                ("gate_rows_bad", ctypes.c_uint64), ("gate_row", ctypes.c_uint32), ("gate_index", ctypes.c_uint32),
+                ("gate_kind", ctypes.c_uint32), ("gate_constraint", ctypes.c_uint32), ("gate_value", ctypes.c_uint64),
+                ("copy_cells_bad", ctypes.c_uint64), ("copy_row", ctypes.c_uint32), ("copy_col", ctypes.c_uint32),
+                ("copy_to_row", ctypes.c_uint32), ("copy_to_col", ctypes.c_uint32), ("copy_value", ctypes.c_uint64),
+                ("copy_to_value", ctypes.c_uint64),
+                ("lookup_slots_bad", ctypes.c_uint64), ("lookup_row", ctypes.c_uint32), ("lookup_slot", ctypes.c_uint32),
+                ("lookup_table", ctypes.c_uint32), ("lookup_pad_", ctypes.c_uint32), ("lookup_input", ctypes.c_uint64),
+                ("lookup_output", ctypes.c_uint64)]
+    message = ""
+
+    @property
+    def ok(self):
+        return self.satisfied == 1
+
+    def __str__(self):
+        return self.message if not self.ok else "the witness satisfies the circuit (checked = %d)" % self.checked
+
+    def raise_if_unsatisfied(self):
+        if not self.ok:
+            raise ValueError(self.message)
+        return self
+
+
 class CircuitData:
     """Prover-side circuit data resident on the GPU (CircuitBuilder::build output)."""
 
@@ -187,6 +217,21 @@ class CircuitData:
         self.ctx.check(dll.nlx_prove(self.handle, ptr(wires), ptr(pis) if pis.size else None,
                                      self._buf.ctypes.data, self._buf.size, ctypes.byref(ln)))
         return self._buf[:ln.value].tobytes()
+
+    def check_witness(self, wires, public_inputs, what="all"):
+        """nlx_circuit_check_witness: which row, gate and constraint (or copy, or lookup slot) the witness breaks.  what: "all",
+        "gates", "copies", "lookups", a "+"-joined set of these, or the NLX_CHECK_* bits.  The witness is never written."""
+        bits = what
+        if not isinstance(what, int):
+            bits = 0
+            for w in what.split("+"):
+                bits |= _CHECK_BITS[w]
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        rep = WitnessReport()
+        self.ctx.check(dll.nlx_circuit_check_witness(self.handle, ptr(wires), ptr(pis) if pis.size else None, bits, ctypes.byref(rep)))
+        if not rep.ok:
+            rep.message = dll.nlx_last_error(self.ctx.handle).decode()
+        return rep
 
     # ---- stage-level calls (the fine seam) ----
     def constants_sigmas_batch(self):

@@ -4,6 +4,7 @@ ctx = nlx.Context(0)
 syn = nlx.SyntheticCircuit(14, seed=1, pct_poseidon=25, pct_arithmetic=20, pct_u32=15)
 cd = nlx.CircuitData.from_synthetic(ctx, syn)
 proof = cd.prove(syn.wires, syn.public_inputs)
+cd.check_witness(syn.wires, syn.public_inputs).raise_if_unsatisfied()
 print("plonky2 proof", len(proof))
 S = nlx.stark
 air = S.Air(2, 3)
