@@ -886,6 +886,52 @@ int32_t nlx_stark_stage_times(const nlx_stark* s, uint32_t* n_stages, const char
 /* As nlx_batch_prove, for STARK jobs: workers = provers built from the SAME description on DISTINCT contexts;
  * a job's `wires` field is its trace (n_cols x n, host or device). */
 int32_t nlx_stark_batch_prove(nlx_stark* const* workers, uint32_t n_workers, nlx_prove_job* jobs, size_t n_jobs);
+
+/* ---- trace checker: which row and which constraint a trace breaks ----
+ * nlx_stark_prove and nlx_stark_prove_rounds never ask whether the trace satisfies the AIR: a wrong trace becomes proof bytes
+ * that a verifier rejects.  The checker runs the STARK's register program on the n TRACE ROWS (local = row i, next = row
+ * (i + 1) mod n, NLX_AIR_PERIODIC = periodic[a * period + (i mod period)]; no LDE, no hashing, no random combination) with the
+ * quotient's filters as row predicates: EMIT_FIRST counts on row 0 only, EMIT_LAST on row n - 1 only, EMIT_TRANSITION on rows
+ * 0 .. n - 2, EMIT / EMIT_BOOL / EMIT_LOGUP on every row, the wrap at n - 1 included; a constraint outside its rows counts as
+ * zero.  That is the condition under which a verifier accepts an honest proof: the filtered constraints vanish on H.
+ * A constraint's index is its position in emission order over the whole program (segment boundaries do not count; EMIT_BOOL
+ * counts one per column, EMIT_LOGUP two: X^0, then X^1); nlx_stark_num_constraints is how many there are. */
+typedef struct {
+    uint32_t satisfied;        /* 1: every constraint is zero on every row it applies to */
+    uint32_t n_constraints;    /* what the program emits */
+    uint64_t rows_bad;         /* rows with at least one non-zero constraint */
+    uint64_t pairs_bad;        /* non-zero (row, constraint) pairs */
+    /* first = lowest row, then lowest constraint index */
+    uint32_t row, constraint, kind /* NLX_AIR_EMIT* opcode */, word /* index of the emitting program word */;
+    uint32_t sub;              /* EMIT_BOOL: column offset; EMIT_LOGUP: 0 / 1; else 0 */
+    uint32_t pad_;
+    uint64_t value;            /* canonical */
+} nlx_trace_report;
+
+uint32_t nlx_stark_num_constraints(const nlx_stark* s);
+/* trace and public_inputs as nlx_stark_prove takes them (n_cols x n column-major, host or device, canonical words); the trace is
+ * never written.  per_constraint: NULL, or a host array of n_constraints words that receives, per constraint, the number of
+ * rows on which it is not zero.
+ * Both entries return NLX_OK whenever the check ran - the verdict is in *report, which is zero-filled before anything else
+ * happens; when report->satisfied == 0, nlx_last_error holds one line naming the row, the constraint index, its kind, the word
+ * index and the value.  NLX_E_INVAL: a NULL s, trace, round_fn or report; public_inputs NULL while the STARK has public inputs;
+ * nlx_stark_check_trace on a STARK with more than one round or with round challenges; a round callback that returns NULL (the
+ * message of nlx_stark_prove_rounds).  NLX_E_RANGE: a public input, or a caller's challenge, that is not canonical.  The checker
+ * always runs the register program, whichever kernel nlx_stark_quotient_kernel names.  The first check of a STARK uploads the periodic table as it stands and each segment's first constraint index; the
+ * STARK keeps both until nlx_stark_destroy, and one that is never checked pays nothing for them at nlx_stark_build. */
+int32_t nlx_stark_check_trace(nlx_stark* s, const uint64_t* trace, const uint64_t* public_inputs,
+                              nlx_trace_report* report, uint64_t* per_constraint /* host, n_constraints words, or NULL */);
+/* The multi-round form.  round_fn is called exactly as nlx_stark_prove_rounds calls it - the same `known` array, the round's
+ * values taken from values_out - but nothing is committed.  challenges == NULL: each round's challenges are drawn from a host
+ * transcript that has observed the AIR digest, the public inputs and every earlier round's values (deterministic; there is no
+ * cap to observe, so they are NOT the challenges of the proof).  Otherwise the caller's values are used, in the order a prover
+ * would draw them (NLX_E_RANGE if one is not canonical).  A correct trace writer satisfies the constraints for any challenges,
+ * with one proviso: a LogUp helper h = 1 / (alpha + v) has no value where alpha + v = 0 in the quadratic extension, which for a
+ * challenge drawn from a transcript happens with probability about n_lookups / 2^128 - negligible, but a caller who passes
+ * challenges of their own choosing can make it happen. */
+int32_t nlx_stark_check_rounds(nlx_stark* s, nlx_round_fn round_fn, void* user, const uint64_t* public_inputs,
+                               const uint64_t* challenges /* NULL, or sum(round_challenges) canonical values */,
+                               nlx_trace_report* report, uint64_t* per_constraint);
 /* a12: range-check lookups for multi-round AIRs - the log-derivative argument with the challenge in the quadratic
  * extension (starkyx's lookup / bus accumulators are the reason it commits in rounds; its own constraints are not in
  * the reference tree, Cargo.lock:6515).  Constraint side: near-light-client_amd/logup.py.  Witness side, on the device:

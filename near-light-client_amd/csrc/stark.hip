@@ -22,6 +22,7 @@
 #include "prover.hpp"
 #include "transcript.hpp"
 #include "air_vm.hpp"
+#include "stark.hpp"
 
 using namespace nlx;
 
@@ -230,31 +231,6 @@ static void host_ntt(std::vector<uint64_t>& a, unsigned log_len, bool inverse) {
     }
 }
 
-struct nlx_stark {
-    nlx_ctx* ctx = nullptr;
-    nlx_stark_desc d{};
-    std::vector<uint64_t> program;  // canonicalised copy
-    uint32_t qdb = 0, nq = 0, n_regs = 0, n_fri_rounds = 0;
-    uint32_t n_rounds = 1, round_cols[3] = {0, 0, 0}, round_challenges[3] = {0, 0, 0}, round_values[3] = {0, 0, 0},
-             n_round_challenges = 0;  // n_round_challenges: round values + challenges, i.e. the values array minus public inputs
-    uint64_t air_digest[4] = {0, 0, 0, 0};  // the statement digest the transcript opens with (air_digest_host)
-    uint64_t* d_program = nullptr;
-    const AirGenEntry* gen = nullptr;   // a straight-line kernel generated from exactly this program (csrc/airgen/), or nullptr: the interpreter
-    std::vector<uint32_t> seg;        // {first word, end word} per program segment
-    std::vector<uint32_t> seg_after;  // constraints emitted after each segment
-    std::vector<uint32_t> seg_regs;   // registers each segment uses (table sorted by this)
-    std::vector<uint32_t> seg_group;  // first segment of each launch group
-    uint32_t* d_seg = nullptr;
-    uint64_t* d_small = nullptr;  // FRI coset tables (rate_bits) | quotient coset tables (qdb) | w_A^-i
-    uint64_t *d_coset_base = nullptr, *d_q_coset_base = nullptr, *d_q_zh_inv = nullptr, *d_q_wR_inv = nullptr,
-             *d_q_chunk_scale = nullptr, *d_wA_inv = nullptr;
-    uint64_t* d_l_inv = nullptr;               // [2^qdb][n]
-    uint64_t* d_periodic = nullptr;            // [n_periodic][2^qdb][period]
-    std::vector<uint64_t> periodic;            // canonicalised host copy
-    const uint64_t* d_q_inv_scale_br = nullptr;  // ctx-owned
-    StageClock clock;
-};
-
 static size_t stark_proof_max_bytes(const nlx_stark_desc& d, uint32_t n_rounds) {
     const size_t capb = (size_t)32 << d.cap_height;
     const unsigned log_L = d.degree_bits + d.rate_bits;
@@ -430,6 +406,7 @@ int32_t nlx_stark_build(nlx_ctx* ctx, const nlx_stark_desc* desc, nlx_stark** ou
     s->program.swap(prog);
     s->d.program = s->program.data();
     s->n_regs = n_regs;
+    s->n_constraints = n_emits;
     {
         // Segment table, sorted by register need: the quotient kernel is launched once per group of segments with a
         // similar register file, because the LDS a launch reserves per wave is that of its hungriest segment (one
@@ -557,6 +534,9 @@ void nlx_stark_destroy(nlx_stark* s) NLX_TRY {
     ctx->release(s->d_seg);
     ctx->release(s->d_l_inv);
     ctx->release(s->d_periodic);
+    ctx->release(s->d_seg_first);
+    ctx->release(s->d_periodic_rows);
+    ctx->release(s->d_check);
     delete s;   // and with it the stage clock's events
 } NLX_CATCH_VOID(nullptr)
 

@@ -826,6 +826,12 @@ class Ed25519Prover:
         t0 = self.generate_trace(slots)
         return self.prover.prove_rounds(lambda rnd, known: t0 if rnd == 0 else self.round1(known), self.step_tag or [])
 
+    def check(self, slots, challenges=None):
+        """A stark.TraceReport for the trace of these slots: the rounds prove() would run, checked against the AIR instead of
+        proved (StarkProver.check_rounds)."""
+        t0 = self.generate_trace(slots)
+        return self.prover.check_rounds(lambda rnd, known: t0 if rnd == 0 else self.round1(known), self.step_tag or [], challenges)
+
     def close(self):
         self.prover.close()
         self._t0 = self._t1 = None

@@ -430,6 +430,12 @@ class Sha256Prover:
         pis = [int(v) for v in digest] + (self.step_tag or [])
         return self.prover.prove_rounds(lambda rnd, known: self._trace if rnd == 0 else self.round1(known), pis)
 
+    def check_trace(self, digest, challenges=None):
+        """A stark.TraceReport for the trace generate_trace() left on the device: the rounds prove_trace() would run, checked
+        against the AIR instead of proved (StarkProver.check_rounds)."""
+        pis = [int(v) for v in digest] + (self.step_tag or [])
+        return self.prover.check_rounds(lambda rnd, known: self._trace if rnd == 0 else self.round1(known), pis, challenges)
+
     def prove(self, messages):
         """Returns (proof bytes, digest words of the last message in the batch)."""
         blocks, first, want = blocks_for_messages(messages, self.log_blocks)

@@ -467,6 +467,12 @@ class Sha512Prover:
         pis = [int(v) for v in public_inputs] + (self.step_tag or [])
         return self.prover.prove_rounds(lambda rnd, known: self._trace if rnd == 0 else self.round1(known), pis)
 
+    def check_trace(self, public_inputs, challenges=None):
+        """A stark.TraceReport for the trace generate_trace() left on the device: the rounds prove_trace() would run, checked
+        against the AIR instead of proved (StarkProver.check_rounds)."""
+        pis = [int(v) for v in public_inputs] + (self.step_tag or [])
+        return self.prover.check_rounds(lambda rnd, known: self._trace if rnd == 0 else self.round1(known), pis, challenges)
+
     def close(self):
         self.prover.close()
         self._trace = self._acc = None

@@ -12,6 +12,7 @@ interprets (include/nlx.h NLX_AIR_*), mirroring starky's
 constraint_first_row, constraint_last_row}`.
 """
 import ctypes
+import sys
 
 import numpy as np
 
@@ -185,6 +186,12 @@ def step_tag(data):
     return [int.from_bytes(h[7 * i:7 * i + 7], "little") for i in range(STEP_TAG_LEN)]
 
 
+def _caller_site():
+    """"file:line" of whoever called the Air method that called this"""
+    f = sys._getframe(2)
+    return "%s:%d" % (f.f_code.co_filename, f.f_lineno)
+
+
 class Air:
     """An AIR over `n_cols` trace columns and `num_public_inputs` public inputs."""
 
@@ -203,6 +210,7 @@ class Air:
             if not 1 <= len(rounds) <= 3 or sum(c for c, _ in rounds) != n_cols or any(c < 1 for c, _ in rounds):
                 raise ValueError("rounds must split the columns into 1..3 non-empty groups")
         self._emits = []  # (op, expr)
+        self._sites = []  # per entry of _emits: "file:line" of the call that declared it (TraceReport.site)
         self.segment_nodes = AIR_SEGMENT_NODES
         self.max_resident_leaves = AIR_MAX_RESIDENT_LEAVES   # more: fewer re-loads, a larger register file (LDS) per wave
         self._leaf_cache = {}
@@ -293,21 +301,26 @@ class Air:
     # ConstraintConsumer
     def constraint_transition(self, e):
         self._emits.append((AIR_EMIT_TRANSITION, e, 1))
+        self._sites.append(_caller_site())
 
     def constraint_first_row(self, e):
         self._emits.append((AIR_EMIT_FIRST, e, 1))
+        self._sites.append(_caller_site())
 
     def constraint_last_row(self, e):
         self._emits.append((AIR_EMIT_LAST, e, 1))
+        self._sites.append(_caller_site())
 
     def constraint(self, e):
         self._emits.append((AIR_EMIT, e, 1))
+        self._sites.append(_caller_site())
 
     def constraint_boolean(self, col, count=1):
         """constraint(x * (x - 1)) for x = local(col) .. local(col + count - 1), in column order, as one VM
         instruction (eight loads in flight)."""
         assert 0 <= col and count >= 1 and col + count <= self.n_cols
         self._emits.append((AIR_EMIT_BOOL, self._leaf(AIR_LOCAL, col, 1), count))
+        self._sites.append(_caller_site())
 
     def constraint_logup(self, v1_col, v2_col, h_col, challenge=0):
         """The two base-field constraints of one LogUp helper h = 1/(alpha + v1) + 1/(alpha + v2) in the quadratic
@@ -321,6 +334,7 @@ class Air:
         for c in (v1_col, h_col, h_col + 1) + (() if v2_col is None else (v2_col,)):
             assert 0 <= c < self.n_cols
         self._emits.append((AIR_EMIT_LOGUP, (v1_col, 0xFFFF if v2_col is None else v2_col, h_col, challenge), 2))
+        self._sites.append(_caller_site())
 
     @property
     def num_constraints(self):
@@ -582,6 +596,7 @@ class Stark:
         self.air = air
         self.config = config or StarkConfig()
         self.program = air.compile() if program is None else np.ascontiguousarray(program, dtype=np.uint64)
+        self.own_program = program is None   # constraint indices are then positions in air._emits (TraceReport.site)
         cfg = self.config
         qdf = air.quotient_degree_factor()
         if qdf > (1 << cfg.rate_bits):
@@ -613,6 +628,40 @@ _ROUND_FN = ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, 
                              ctypes.POINTER(ctypes.c_uint64))
 
 
+EMIT_KIND_NAMES = {AIR_EMIT_TRANSITION: "transition", AIR_EMIT_FIRST: "first row", AIR_EMIT_LAST: "last row", AIR_EMIT: "every row",
+                   AIR_EMIT_BOOL: "boolean", AIR_EMIT_LOGUP: "logup"}
+
+
+class TraceReport(ctypes.Structure):
+    """nlx_trace_report (include/nlx.h): what nlx_stark_check_trace / nlx_stark_check_rounds found.  `per_constraint`: for every
+    constraint the number of rows on which it is not zero; `message`: the library's line; `site`: "file:line" of the Air call
+    that declared the first failing constraint (None when the trace is satisfied or the STARK runs a caller-supplied program)."""
+    _fields_ = [("satisfied", ctypes.c_uint32), ("n_constraints", ctypes.c_uint32), ("rows_bad", ctypes.c_uint64),
+                ("pairs_bad", ctypes.c_uint64), ("row", ctypes.c_uint32), ("constraint", ctypes.c_uint32), ("kind", ctypes.c_uint32),
+                ("word", ctypes.c_uint32), ("sub", ctypes.c_uint32), ("pad_", ctypes.c_uint32), ("value", ctypes.c_uint64)]
+    message = ""
+    site = None
+    per_constraint = None
+
+    @property
+    def ok(self):
+        return self.satisfied == 1
+
+    @property
+    def kind_name(self):
+        return EMIT_KIND_NAMES.get(self.kind, "?")
+
+    def __str__(self):
+        if self.ok:
+            return "the trace satisfies the AIR (%d constraints)" % self.n_constraints
+        return self.message + (" [declared at %s]" % self.site if self.site else "")
+
+    def raise_if_unsatisfied(self):
+        if not self.ok:
+            raise ValueError(str(self))
+        return self
+
+
 class StarkProver:
     """Device-resident prover for one Stark (nlx_stark_build / nlx_stark_prove)."""
 
@@ -639,14 +688,8 @@ class StarkProver:
                                            self._buf.ctypes.data, self._buf.size, ctypes.byref(ln)))
         return self._buf[:ln.value].tobytes()
 
-    def prove_rounds(self, round_fn, public_inputs=()):
-        """Multi-round proving (nlx_stark_prove_rounds).  round_fn(round, known: list[int]) returns round r's
-        columns - a (round_cols[r], n) uint64 host array or a device tensor - computed from `known`, everything after
-        the public inputs in the values array so far (round values and challenges of the earlier rounds); a round
-        with round values returns (columns, values)."""
-        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
-        if pis.size != self.stark.air.num_public_inputs:
-            raise ValueError("expected %d public inputs" % self.stark.air.num_public_inputs)
+    def _round_callback(self, round_fn):
+        """(the C callback around round_fn, the exceptions it caught, the arrays it keeps alive) for prove_rounds / check_rounds"""
         desc = self.stark.desc
         keep, errors = [], []
 
@@ -671,7 +714,17 @@ class StarkProver:
                 errors.append(e)
                 return None
 
-        fn = _ROUND_FN(cb)
+        return _ROUND_FN(cb), errors, keep
+
+    def prove_rounds(self, round_fn, public_inputs=()):
+        """Multi-round proving (nlx_stark_prove_rounds).  round_fn(round, known: list[int]) returns round r's
+        columns - a (round_cols[r], n) uint64 host array or a device tensor - computed from `known`, everything after
+        the public inputs in the values array so far (round values and challenges of the earlier rounds); a round
+        with round values returns (columns, values)."""
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if pis.size != self.stark.air.num_public_inputs:
+            raise ValueError("expected %d public inputs" % self.stark.air.num_public_inputs)
+        fn, errors, _keep = self._round_callback(round_fn)
         ln = ctypes.c_size_t()
         rc = dll.nlx_stark_prove_rounds(self.handle, fn, None, ptr(pis) if pis.size else None, self._buf.ctypes.data,
                                         self._buf.size, ctypes.byref(ln))
@@ -679,6 +732,58 @@ class StarkProver:
             raise errors[0]
         self.ctx.check(rc)
         return self._buf[:ln.value].tobytes()
+
+    def _finish_report(self, rep, counts):
+        rep.per_constraint = counts
+        if not rep.ok:
+            rep.message = dll.nlx_last_error(self.ctx.handle).decode()
+            if self.stark.own_program:
+                at = 0
+                for (_, _, cnt), site in zip(self.stark.air._emits, self.stark.air._sites):
+                    if at <= rep.constraint < at + cnt:
+                        rep.site = site
+                    at += cnt
+        return rep
+
+    def check(self, trace, public_inputs=()):
+        """nlx_stark_check_trace: which row and which constraint the trace breaks (a TraceReport); trace and public inputs as
+        prove() takes them.  The trace is never written."""
+        air = self.stark.air
+        if tuple(trace.shape) != (air.n_cols, 1 << self.stark.degree_bits):
+            raise ValueError("trace must be (n_cols, n)")
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if pis.size != air.num_public_inputs:
+            raise ValueError("expected %d public inputs" % air.num_public_inputs)
+        if isinstance(trace, np.ndarray):
+            trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        rep = TraceReport()
+        counts = np.zeros(dll.nlx_stark_num_constraints(self.handle), dtype=np.uint64)
+        self.ctx.check(dll.nlx_stark_check_trace(self.handle, ptr(trace), ptr(pis) if pis.size else None, ctypes.byref(rep),
+                                                 counts.ctypes.data))
+        return self._finish_report(rep, counts)
+
+    def check_rounds(self, round_fn, public_inputs=(), challenges=None):
+        """nlx_stark_check_rounds: as check(), for a multi-round STARK.  round_fn is what prove_rounds() takes and is called the
+        same way.  challenges: None - drawn from a transcript of the statement and the earlier rounds' values, so deterministic
+        but not those of a proof - or sum(round_challenges) values in the order a prover draws them."""
+        pis = np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if pis.size != self.stark.air.num_public_inputs:
+            raise ValueError("expected %d public inputs" % self.stark.air.num_public_inputs)
+        desc = self.stark.desc
+        chs = None
+        if challenges is not None:
+            chs = np.array([int(v) % P for v in challenges], dtype=np.uint64)
+            if chs.size != sum(desc.round_challenges[r] for r in range(desc.n_rounds)):
+                raise ValueError("expected %d challenges" % sum(desc.round_challenges[r] for r in range(desc.n_rounds)))
+        fn, errors, _keep = self._round_callback(round_fn)
+        rep = TraceReport()
+        counts = np.zeros(dll.nlx_stark_num_constraints(self.handle), dtype=np.uint64)
+        rc = dll.nlx_stark_check_rounds(self.handle, fn, None, ptr(pis) if pis.size else None,
+                                        chs.ctypes.data if chs is not None and chs.size else None, ctypes.byref(rep), counts.ctypes.data)
+        if errors:
+            raise errors[0]
+        self.ctx.check(rc)
+        return self._finish_report(rep, counts)
 
     def prove_into(self, trace, public_inputs_ptr):
         ln = ctypes.c_size_t()

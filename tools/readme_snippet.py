@@ -12,6 +12,7 @@ air.constraint_transition(air.next(0) - air.local(1))
 air.constraint_transition(air.next(1) - air.local(0) - air.local(1))
 prover = S.Stark(air, 10).build(ctx)
 proof = prover.prove(*S.fibonacci_trace(10)[:1], [0, 1, 0])
+prover.check(*S.fibonacci_trace(10)[:1], [0, 1, 0]).raise_if_unsatisfied()
 print("stark proof", len(proof))
 digest_proof, digest = nlx.sha256_air.Sha256Prover(ctx, 4).prove([b"abc", b"hello"])
 print("sha256", len(digest_proof))
