@@ -109,6 +109,12 @@ int32_t nlx_ctx_kernel_units(nlx_ctx* ctx, const char* name, double* units);
  * row 0 a*b, row 1 a+b, row 2 a-b, row 3 a^-1 (0 if a = 0), row 4 the raw multiply path applied to
  * the UNREDUCED inputs (carry/borrow edges), all canonical. */
 int32_t nlx_field_ops(nlx_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
+/* The lazily reduced forms (one reduction per sum of products).  a, b: n pairs of arbitrary u64, NOT reduced first.
+ * out: 8 x n, all canonical: rows 0-1 the extension product (a[2i] + a[2i+1] X)(b[2i] + b[2i+1] X), X^2 = 7; rows 2-3
+ * (a[2i] + a[2i+1] X) b[2i]; row 4 the 160-bit integer with 32-bit limbs (a[2i] lo, a[2i] hi, a[2i+1] lo, a[2i+1] hi,
+ * b[2i+1] lo), lowest first, reduced mod p; rows 5-6 and row 7 the LOOSE device forms of the extension product and of that
+ * reduction (any u64 congruent to the value), made canonical afterwards: equal to rows 0-1 and row 4. */
+int32_t nlx_ext_ops(nlx_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);
 
 /* ---- a5: plonky2::hash::poseidon::Poseidon::poseidon ----
  * states: n x 12 u64, row-major, permuted in place. */

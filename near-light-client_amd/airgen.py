@@ -62,21 +62,70 @@ def _segments(words):
     return segs
 
 
-def _emit_constraint(lines, expr):
-    lines.append("    c = %s;" % expr)
-    lines.append("    acc0 = gl::add(gl::mul(acc0, g.a0), c); acc1 = gl::add(gl::mul(acc1, g.a1), c);")
+# How a segment folds its K constraints with the powers of alpha.  Horner gives constraint k the power alpha^(K - 1 - k)
+# (segment_exponents), so a WIDE segment multiply-accumulates c_k * alpha^(K - 1 - k) for both challenges into GateAcc's
+# unreduced column sums (gate_acc.hpp: 16 instructions per constraint, the powers read from the per-proof table
+# AirParams::alpha_pows through the constant address space) and folds once at its end; c_k may be loose.  The accumulator holds
+# 24 registers where Horner's two sums hold 4: a segment that would take its kernel over a wave's register limit (168 for three
+# waves, 256 for two) is listed in HORNER_SEGMENTS and keeps Horner, with loose steps: acc = add_loose(mul_loose(acc, alpha), c),
+# 20 instructions per challenge (the canonical step costs 24), c canonical as every value of a segment is; its sums are reduced
+# by the multiplications of the kernel's epilogue (gl::mul takes any u64).  The interpreter keeps canonical Horner.
+HORNER = "acc0 = gl::add_loose(gl::mul_loose(acc0, g.a0), %s); acc1 = gl::add_loose(gl::mul_loose(acc1, g.a1), %s);"
+# {program: first words of the segments that keep Horner}, from the per-function register counts of an all-wide build
+# (profiles/lazy_constraints_resource_usage.txt)
+HORNER_SEGMENTS = {
+    # parts 0 and 1 sit at 162 registers, three waves (<= 168); these segments came out at 177 - 198 with the wide accumulator
+    "ed25519_2p7_tagged": (2646, 6297, 6956, 7679, 8370, 9093, 14490, 15181, 15872),
+    # parts 1 and 2 sit at 152, three waves; every one of their segments came out at 210 - 215
+    "sha512_tagged": (8982, 10259, 11536, 12813, 14090, 15367, 16644, 17921, 19198, 20475, 21752, 23029, 24306, 25583, 26144, 26705,
+                      27266),
+}
+
+
+def segment_exponents(words, lo, hi):
+    """the power of alpha each constraint of words[lo:hi] meets, in the order emitted: Horner over K constraints is
+    sum_k alpha^(K - 1 - k) c_k.  EMIT_LOGUP emits two constraints, EMIT_BOOL one per column."""
+    n, i = 0, lo
+    while i < hi:
+        w = int(words[i])
+        op = w & 0xFF
+        if op in (EMIT_TRANSITION, EMIT_FIRST, EMIT_LAST, EMIT):
+            n += 1
+        elif op == EMIT_LOGUP:
+            n += 2
+        elif op == EMIT_BOOL:
+            n += ((w >> 40) & 0xFFFF) or 1
+        i += 2 if op == CONST else 1
+    return [n - 1 - k for k in range(n)]
+
+
+class _Fold:
+    """writes the statements that fold one constraint after the other: wide (exponents from segment_exponents) or Horner"""
+
+    def __init__(self, exponents, wide):
+        self.exponents, self.wide, self.k = exponents, wide, 0
+
+    def emit(self, lines, expr, indent="    ", canonical=False):
+        """expr: 'gl::mul(...)' or a canonical value's name; a wide segment takes the product loose"""
+        if self.wide:
+            e = self.exponents[self.k]
+            lines.append("%sacc.mac(%s, AP0(%d), AP1(%d));" % (indent, expr if canonical else expr.replace("gl::mul(", "gl::mul_loose(", 1), e, e))
+        else:
+            lines.append("%sc = %s; " % (indent, expr) + HORNER % ("c", "c"))
+        self.k += 1
 
 
 SCHED_EVERY = 4
 
 
-def _segment_body(words, lo, hi):
+def _segment_body(words, lo, hi, wide=False):
     """C++ statements for words[lo:hi]; every statement mirrors the interpreter's case for its opcode (csrc/stark.hip).
     hipcc schedules a long straight-line block for instruction-level parallelism and keeps everything it hoisted alive: the
     multiplier segments of the Ed25519 AIR (43 live values in the assembler's plan = 86 registers) came out at 214 - 241
     registers, two waves per SIMD.  A barrier after every SCHED_EVERY register-writing words keeps the order the assembler
     planned (its plan bounds the live values); the wave-level parallelism comes from the other waves."""
     L, i, since = [], lo, 0
+    fold = _Fold(segment_exponents(words, lo, hi), wide)
     R = lambda k: "r%d" % k
     while i < hi:
         if since >= SCHED_EVERY:
@@ -131,7 +180,7 @@ def _segment_body(words, lo, hi):
                 for k in range(m):
                     L.append("      v[%d] = COL(%d, g.row);" % (k, a + i0 + k))
                 for k in range(m):
-                    L.append("      c = gl::mul(v[%d], gl::sub(v[%d], 1)); acc0 = gl::add(gl::mul(acc0, g.a0), c); acc1 = gl::add(gl::mul(acc1, g.a1), c);" % (k, k))
+                    fold.emit(L, "gl::mul(v[%d], gl::sub(v[%d], 1))" % (k, k), indent="      ")
                 L.append("    }")
         elif op == EMIT_LOGUP:
             L.append("    { const uint64_t al0 = PIS(g.n_pis + %d), al1 = PIS(g.n_pis + %d);" % (sh, sh + 1))
@@ -150,23 +199,25 @@ def _segment_body(words, lo, hi):
                 L.append("      const uint64_t hu = gl::mul(h1, u1);")
                 L.append("      c0 = gl::sub(gl::add(gl::mul(h0, u0), gl::sub(mul_pow2(hu, 3), hu)), s2);")
                 L.append("      c1 = gl::sub(gl::add(gl::mul(h0, u1), gl::mul(h1, u0)), gl::add(al1, al1));")
-            L.append("      acc0 = gl::add(gl::mul(gl::add(gl::mul(acc0, g.a0), c0), g.a0), c1);")
-            L.append("      acc1 = gl::add(gl::mul(gl::add(gl::mul(acc1, g.a1), c0), g.a1), c1); }")
+            fold.emit(L, "c0", indent="      ", canonical=True)
+            fold.emit(L, "c1", indent="      ", canonical=True)
+            L.append("    }")
         elif op == LOADV:
             # the interpreter's hint "the next words are independent loads" marks where the assembler wants a batch of loads in
             # flight: a scheduling barrier there keeps hipcc from hoisting EVERY load of the segment to its top (354 registers and
             # scratch without it) - live values stay what the assembler planned, the batch's loads still issue together
             L.append("    __builtin_amdgcn_sched_barrier(0);")
         elif op == EMIT_TRANSITION:
-            _emit_constraint(L, "gl::mul(%s, g.z_last)" % R(a))
+            fold.emit(L, "gl::mul(%s, g.z_last)" % R(a))
         elif op == EMIT_FIRST:
-            _emit_constraint(L, "gl::mul(%s, g.l_first)" % R(a))
+            fold.emit(L, "gl::mul(%s, g.l_first)" % R(a))
         elif op == EMIT_LAST:
-            _emit_constraint(L, "gl::mul(%s, g.l_last)" % R(a))
+            fold.emit(L, "gl::mul(%s, g.l_last)" % R(a))
         elif op == EMIT:
-            _emit_constraint(L, R(a))
+            fold.emit(L, R(a), canonical=True)
         else:
             raise ValueError("unknown opcode %d at word %d" % (op, i - 1))
+    assert fold.k == len(fold.exponents)
     return L
 
 
@@ -218,7 +269,9 @@ def generate_sources(name, words):
                "typedef const char __attribute__((address_space(1)))* airgen_gptr;",
                "#define COL(c, off) (*(const uint64_t __attribute__((address_space(1)))*)((airgen_gptr)((airgen_kptr)g.cols)[c] + (off)))",
                "#define PIS(i) (((airgen_kptr)g.pis)[i])",
-               "struct G {", "    uint64_t cols, pis; const uint64_t* per;",
+               "#define AP0(j) (((airgen_kptr)g.ap0)[j])",
+               "#define AP1(j) (((airgen_kptr)g.ap1)[j])",
+               "struct G {", "    uint64_t cols, pis, ap0, ap1; const uint64_t* per;",
                "    size_t per_stride, per_off; uint64_t a0, a1, z_last, l_first, l_last; uint32_t row, row_next, n_pis;", "};",
                "struct Acc { uint64_t a0, a1; };",
                "template <typename T> __device__ __forceinline__ T* uni(T* p) {",
@@ -234,11 +287,20 @@ def generate_sources(name, words):
             out.append("    G g = gv;")
             out.append("    g.cols = uni(gv.cols); g.pis = uni(gv.pis); g.per = uni(gv.per); g.per_stride = uni((uint64_t)gv.per_stride);")
             out.append("    g.a0 = uni(gv.a0); g.a1 = uni(gv.a1); g.n_pis = (uint32_t)__builtin_amdgcn_readfirstlane((int)gv.n_pis);")
-            out.append("    uint64_t c, acc0 = 0, acc1 = 0;")
+            wide = lo not in HORNER_SEGMENTS.get(name, ())
+            if wide:
+                out.append("    g.ap0 = uni(gv.ap0); g.ap1 = uni(gv.ap1);")
+                out.append("    GateAcc acc;")
+                out.append("    acc.reset();")
+            else:
+                out.append("    uint64_t c, acc0 = 0, acc1 = 0;")
             if regs:
                 out.append("    uint64_t %s;" % ", ".join("r%d" % r for r in regs))
-            out += _segment_body(words, lo, hi)
-            out.append("    return Acc{acc0, acc1};")
+            out += _segment_body(words, lo, hi, wide)
+            if wide:
+                out.append("    return Acc{GateAcc::fold_columns(acc.a, acc.kc), GateAcc::fold_columns(acc.a + 4, acc.kc + 4)};")
+            else:
+                out.append("    return Acc{acc0, acc1};")
             out.append("}")
             out.append("")
         out += [
@@ -262,6 +324,7 @@ def generate_sources(name, words):
             "    g.per_stride = (size_t)1 << (p.qdb + p.period_bits);",
             "    g.per_off = ((size_t)rq << p.period_bits) + (k & ((1u << p.period_bits) - 1));",
             "    g.a0 = p.alphas[0]; g.a1 = p.alphas[1];",
+            "    g.ap0 = (uint64_t)p.alpha_pows; g.ap1 = (uint64_t)(p.alpha_pows + p.alpha_stride);",
             "    g.z_last = gl::sub(x, p.g_inv); g.l_first = gl::mul(zh, p.l_inv[pos]); g.l_last = gl::mul(zh, p.l_inv[qrow_next]);",
             "    Acc acc{0, 0};",
             "    switch (first) {",

@@ -29,6 +29,19 @@ def field_ops(ctx, a, b):
     return out
 
 
+def ext_ops(ctx, a, b):
+    """the lazily reduced device forms on n pairs of UNREDUCED u64 (a, b: (n, 2)): the extension product (rows 0-1), the
+    product by b[:, 0] (rows 2-3), reduce160 of the limbs (a0 lo, a0 hi, a1 lo, a1 hi, b1 lo) (row 4), and the loose forms of the
+    product (rows 5-6) and of reduce160 (row 7) made canonical: (8, n) uint64"""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape != b.shape:
+        raise ValueError("a and b must both have shape (n, 2)")
+    out = np.zeros((8, a.shape[0]), dtype=np.uint64)
+    ctx.check(dll.nlx_ext_ops(ctx.handle, ptr(a), ptr(b), a.shape[0], ptr(out)))
+    return out
+
+
 def hash_rows(ctx, rows):
     """PoseidonHash::hash_or_noop of every row of a row-major (n_rows, row_len) matrix."""
     r = np.ascontiguousarray(rows, dtype=np.uint64)

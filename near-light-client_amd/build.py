@@ -74,7 +74,7 @@ def _headers_mtime(only=None):
     return m
 
 
-AIRGEN_HEADERS = ("air_vm.hpp", "gl.hpp", "nlx.h", "nlx_field.h")
+AIRGEN_HEADERS = ("air_vm.hpp", "gate_acc.hpp", "gl.hpp", "nlx.h", "nlx_field.h")
 
 
 def _compile(src, verbose):

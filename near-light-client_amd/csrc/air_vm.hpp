@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gl.hpp"
+#include "gate_acc.hpp"
 #include "nlx.h"
 
 namespace nlx {
@@ -24,6 +25,9 @@ struct AirParams {
     uint64_t* part;             // [segment][challenge][r'][k] partial sums (n_seg > 1)
     uint32_t n_seg;
     uint64_t alphas[2];
+    const uint64_t* alpha_pows; // device, per proof: [challenge][j] = alpha_c^j, j < alpha_stride (> the largest segment's constraint
+                                // count); the generated kernels' lazily reduced accumulators read it, the interpreter does not
+    uint32_t alpha_stride;
     uint64_t g_inv;             // last = g^-1 (g generates the size-n subgroup)
     uint32_t log_n, rate_bits, qdb, n_words, nc, n_regs, period_bits, n_pis;
 };

@@ -189,6 +189,22 @@ int32_t nlx_field_ops(nlx_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t
     return NLX_OK;
 } NLX_CATCH(ctx)
 
+int32_t nlx_ext_ops(nlx_ctx* ctx, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (n == 0) return NLX_OK;
+    if (!a || !b || !out) return ctx->fail(NLX_E_INVAL, "NULL buffer");
+    (void)hipSetDevice(ctx->device);
+    Staged sa(ctx, a, 2 * n * 8, true, false), sb(ctx, b, 2 * n * 8, true, false), so(ctx, out, 8 * n * 8, false, true);
+    if (sa.status) return sa.status;
+    if (sb.status) return sb.status;
+    if (so.status) return so.status;
+    launch_ext_ops(ctx->stream, sa.as<uint64_t>(), sb.as<uint64_t>(), n, so.as<uint64_t>());
+    int32_t rc = so.finish();
+    if (rc) return rc;
+    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NLX_OK;
+} NLX_CATCH(ctx)
+
 int32_t nlx_poseidon_permute_batch(nlx_ctx* ctx, uint64_t* states, size_t n) NLX_TRY {
     if (!ctx) return NLX_E_INVAL;
     if (n == 0) return NLX_OK;

@@ -177,6 +177,55 @@ __device__ __forceinline__ uint64_t mul_loose_asm(uint64_t a, uint64_t b) {
 }
 #endif
 
+#if defined(__HIP__)
+// (w4 : w3 : w2 : w1 : w0) mod p, any five 32-bit limbs -> canonical.  2^64 = EPS, 2^96 = -1, 2^128 = -2^32:
+//   (w1:w0) - w3 [borrow -> -EPS] + w2 EPS [carry -> +EPS], made canonical, minus w4 2^32 (canonical for every w4: at most P - 1).
+// One reduction for a whole sum of products: GateAcc's columns (prover_kernels.hip) and the extension product below.
+// reduce160_loose skips the canonical step: sub takes any u64 on its left, and the result is any u64 congruent to the value.
+template <bool CANON>
+__device__ __forceinline__ uint64_t reduce160_impl(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4) {
+    uint32_t r0, r1, t0;
+    asm("v_sub_co_u32 %[r0], vcc, %[w0], %[w3]\n\t"
+        "v_subbrev_co_u32 %[r1], vcc, 0, %[w1], vcc\n\t"
+        "v_cndmask_b32_e64 %[t0], 0, -1, vcc\n\t"
+        "v_sub_co_u32 %[r0], vcc, %[r0], %[t0]\n\t"
+        "v_subbrev_co_u32 %[r1], vcc, 0, %[r1], vcc"
+        : [r0] "=&v"(r0), [r1] "=&v"(r1), [t0] "=&v"(t0)
+        : [w0] "v"(w0), [w1] "v"(w1), [w3] "v"(w3)
+        : "vcc");
+    const uint64_t base = ((uint64_t)r1 << 32) | r0;
+    uint64_t r;
+    uint32_t tm;
+    asm("v_mad_u64_u32 %[r], vcc, %[w2], -1, %[base]\n\t"
+        "v_cndmask_b32_e64 %[t], 0, -1, vcc\n\t"
+        "v_mad_u64_u32 %[r], vcc, %[t], 1, %[r]"
+        : [r] "=&v"(r), [t] "=&v"(tm)
+        : [w2] "v"(w2), [base] "v"(base)
+        : "vcc");
+    return sub(CANON ? canon(r) : r, (uint64_t)w4 << 32);
+}
+__device__ __forceinline__ uint64_t reduce160(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4) {
+    return reduce160_impl<true>(w0, w1, w2, w3, w4);
+}
+__device__ __forceinline__ uint64_t reduce160_loose(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4) {
+    return reduce160_impl<false>(w0, w1, w2, w3, w4);
+}
+// the full 128-bit product (w32 : w1 : w0), by mul_loose_asm's chain of five multiply-adds
+struct Wide128 {
+    uint32_t w0, w1;
+    uint64_t w32;  // limbs 2 and 3
+};
+__device__ __forceinline__ Wide128 mul_wide(uint64_t a, uint64_t b) {
+    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
+    const uint64_t p0 = (uint64_t)a0 * b0;
+    const uint64_t p1 = (uint64_t)a0 * b1 + (p0 >> 32);
+    const uint64_t p2 = (uint64_t)a1 * b0 + (uint32_t)p1;
+    uint64_t p3 = (uint64_t)a1 * b1 + (p1 >> 32), sink;
+    asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(p3), "=s"(sink) : "v"((uint32_t)(p2 >> 32)), "v"(p3));
+    return Wide128{(uint32_t)p0, (uint32_t)p2, p3};
+}
+#endif
+
 // loose * loose -> loose
 GL_HD uint64_t mul_loose(uint64_t a, uint64_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -225,7 +274,41 @@ struct Ext {
 GL_HD Ext ext(uint64_t a, uint64_t b = 0) { return Ext{a, b}; }
 GL_HD Ext add(Ext x, Ext y) { return Ext{add(x.a, y.a), add(x.b, y.b)}; }
 GL_HD Ext sub(Ext x, Ext y) { return Ext{sub(x.a, y.a), sub(x.b, y.b)}; }
-GL_HD Ext mul(Ext x, Ext y) {
+#if defined(__HIP__)
+// Device form, any u64 in, canonical out: the four 128-bit products are ADDED AS INTEGERS and each component is reduced once
+//   c1 = a0 b1 + a1 b0 < 2^129;   c0 = a0 b0 + 7 a1 b1 < 2^131   (fifth limb < 2 and < 8)
+// instead of four canonical multiplies, a generic 7 * bb and two canonical adds (98 vector instructions measured; this is 82).  The
+// product by 7 rides on the addition: limb_i * 7 + q_i + carry <= 8 (2^32 - 1) + 7 fits 64 bits, so the chain never overflows.
+template <bool CANON>
+__device__ __forceinline__ Ext mul_impl(Ext x, Ext y) {
+    const Wide128 ab = mul_wide(x.a, y.b), ba = mul_wide(x.b, y.a);
+    uint32_t s0, s1, s2, s3, s4;
+    asm("v_add_co_u32 %[s0], vcc, %[x0], %[y0]\n\t"
+        "v_addc_co_u32 %[s1], vcc, %[x1], %[y1], vcc\n\t"
+        "v_addc_co_u32 %[s2], vcc, %[x2], %[y2], vcc\n\t"
+        "v_addc_co_u32 %[s3], vcc, %[x3], %[y3], vcc\n\t"
+        "v_addc_co_u32 %[s4], vcc, 0, 0, vcc"
+        : [s0] "=&v"(s0), [s1] "=&v"(s1), [s2] "=&v"(s2), [s3] "=&v"(s3), [s4] "=&v"(s4)
+        : [x0] "v"(ab.w0), [x1] "v"(ab.w1), [x2] "v"((uint32_t)ab.w32), [x3] "v"((uint32_t)(ab.w32 >> 32)), [y0] "v"(ba.w0),
+          [y1] "v"(ba.w1), [y2] "v"((uint32_t)ba.w32), [y3] "v"((uint32_t)(ba.w32 >> 32))
+        : "vcc");
+    const uint64_t c1 = reduce160_impl<CANON>(s0, s1, s2, s3, s4);
+    // one component at a time: with all four products in flight a caller holds 16 more registers (k_fri_fold lost a wave)
+    __builtin_amdgcn_sched_barrier(0);
+    const Wide128 aa = mul_wide(x.a, y.a), bb = mul_wide(x.b, y.b);
+    const uint64_t t0 = (uint64_t)bb.w0 * (uint32_t)W + aa.w0;
+    const uint64_t t1 = (uint64_t)bb.w1 * (uint32_t)W + (((uint64_t)aa.w1) + (t0 >> 32));
+    const uint64_t t2 = (uint64_t)(uint32_t)bb.w32 * (uint32_t)W + ((aa.w32 & EPS) + (t1 >> 32));
+    const uint64_t t3 = (uint64_t)(uint32_t)(bb.w32 >> 32) * (uint32_t)W + ((aa.w32 >> 32) + (t2 >> 32));
+    const uint64_t c0 = reduce160_impl<CANON>((uint32_t)t0, (uint32_t)t1, (uint32_t)t2, (uint32_t)t3, (uint32_t)(t3 >> 32));
+    return Ext{c0, c1};
+}
+__device__ __forceinline__ Ext mul(Ext x, Ext y) { return mul_impl<true>(x, y); }
+// any u64 in, LOOSE out (three instructions fewer per component): for products that only feed another multiply, the left of a
+// sub or the first operand of add_loose
+__device__ __forceinline__ Ext mul_loose(Ext x, Ext y) { return mul_impl<false>(x, y); }
+#endif
+GL_H Ext mul(Ext x, Ext y) {
     uint64_t bb = mul(x.b, y.b);
     // 7*bb without a full multiply: 8*bb - bb, done in 128 bits
     uint64_t c0 = add(mul(x.a, y.a), reduce128(bb * W, mulhi64(bb, W)));

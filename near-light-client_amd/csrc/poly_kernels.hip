@@ -349,4 +349,28 @@ void launch_field_ops(hipStream_t st, const uint64_t* d_a, const uint64_t* d_b, 
     hipLaunchKernelGGL(k_field_ops, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_a, d_b, n, d_out);
 }
 
+// ---- the lazily reduced field forms (self-test entry point nlx_ext_ops) ----
+// a, b: n pairs, taken WITHOUT prior canonicalisation.  out[0..1][i] = (a[2i] + a[2i+1] X)(b[2i] + b[2i+1] X),
+// out[2..3][i] = (a[2i] + a[2i+1] X) b[2i], out[4][i] = reduce160 of the limbs (a[2i] lo, hi, a[2i+1] lo, hi, b[2i+1] lo);
+// out[5..6][i] and out[7][i]: the LOOSE forms of the product and of reduce160 on the same operands, made canonical for the comparison
+__global__ void k_ext_ops(const uint64_t* __restrict__ a, const uint64_t* __restrict__ b, size_t n, uint64_t* __restrict__ out) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const gl::Ext x{a[2 * i], a[2 * i + 1]}, y{b[2 * i], b[2 * i + 1]};
+    const gl::Ext pr = gl::mul(x, y), sc = gl::mul(x, y.a);
+    out[i] = pr.a;
+    out[n + i] = pr.b;
+    out[2 * n + i] = sc.a;
+    out[3 * n + i] = sc.b;
+    out[4 * n + i] = gl::reduce160((uint32_t)x.a, (uint32_t)(x.a >> 32), (uint32_t)x.b, (uint32_t)(x.b >> 32), (uint32_t)y.b);
+    const gl::Ext lp = gl::mul_loose(x, y);
+    out[5 * n + i] = gl::canon(lp.a);
+    out[6 * n + i] = gl::canon(lp.b);
+    out[7 * n + i] = gl::canon(gl::reduce160_loose((uint32_t)x.a, (uint32_t)(x.a >> 32), (uint32_t)x.b, (uint32_t)(x.b >> 32), (uint32_t)y.b));
+}
+void launch_ext_ops(hipStream_t st, const uint64_t* d_a, const uint64_t* d_b, size_t n, uint64_t* d_out) {
+    if (!n) return;
+    hipLaunchKernelGGL(k_ext_ops, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_a, d_b, n, d_out);
+}
+
 }  // namespace nlx

@@ -230,6 +230,13 @@ int32_t circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t
     c->hasher = hasher;
     c->gates.assign(d.gates, d.gates + d.num_gates);
     for (const nlx_gate_desc& gt : c->gates) c->max_gate_constraints = std::max(c->max_gate_constraints, gate_num_constraints(gt));
+#ifdef NLX_GATEACC_LIMBS3
+    // the three-limb accumulator has no carry counters: a gate folds once, so its constraints must fit the columns' headroom
+    if (c->max_gate_constraints > GATEACC3_MAX_TERMS || d.num_partial_products + 1 > GATEACC3_MAX_TERMS) {
+        delete c;
+        return ctx->fail(NLX_E_INVAL, "a gate with more than %u constraints (this build accumulates them without carry counters)", GATEACC3_MAX_TERMS);
+    }
+#endif
     c->k_is.assign(d.k_is, d.k_is + d.num_routed_wires);
     c->d.gates = c->gates.data();
     c->d.k_is = c->k_is.data();
@@ -631,6 +638,12 @@ int32_t quotient_stage(nlx_circuit* c, const nlx_commit* cw, const nlx_commit* c
     if (!d_alpha_pows || !d_qvals || !d_qchunks) return NLX_E_NOMEM;
     launch_pow_table(st, d_alpha_pows, alphas[0], alphas[1], c->n_terms, c->n_terms);
     QuotientParams qp{};
+#ifdef NLX_GATEACC_LIMBS3
+    uint32_t* d_alpha_limbs = scratch.alloc_as<uint32_t>((size_t)2 * c->n_terms * 16);
+    if (!d_alpha_limbs) return NLX_E_NOMEM;
+    launch_pow_limbs(st, d_alpha_limbs, d_alpha_pows, 2 * c->n_terms);
+    qp.alpha_limbs = d_alpha_limbs;
+#endif
     qp.cs = c->cs->lde; qp.wires = cw->lde; qp.zs = cz->lde;
     qp.gates = c->d_gates; qp.k_is = c->d_k_is; qp.coset_base = c->d_coset_base;
     qp.w_n_table = ctx->tables.fwd[log_n];

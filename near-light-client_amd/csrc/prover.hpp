@@ -35,6 +35,8 @@ struct QuotientParams {
     const uint64_t* zh_inv;      // device: 1 / Z_H on coset r
     const uint64_t* l0_scaled;   // device: 1 / (n (x - 1)) per LDE point
     const uint64_t* alpha_pows;  // device: [2][alpha_stride]
+    const uint32_t* alpha_limbs; // device: [2][alpha_stride][4] = the same powers as three 22-bit limbs (+ one unused word), for
+                                 // GateAcc3 (prover_kernels.hip); nullptr unless the library is built with NLX_GATEACC_LIMBS3
     uint64_t* out;               // [nc][L]
     uint64_t betas[2], gammas[2], pih[4];
     uint32_t alpha_stride;
@@ -163,6 +165,8 @@ void launch_fri_gather_leaf(hipStream_t st, const uint64_t* d_values, unsigned l
                             size_t out_stride_words);
 void launch_shift_indices(hipStream_t st, const uint64_t* d_in, uint64_t* d_out, uint32_t n, unsigned shift);
 void launch_pow_table(hipStream_t st, uint64_t* d_out, uint64_t a0, uint64_t a1, uint32_t count, uint32_t stride);
+void launch_pow_limbs(hipStream_t st, uint32_t* d_out, const uint64_t* d_pows, uint32_t count);   // count words -> count x 4 limbs
+constexpr uint32_t GATEACC3_MAX_TERMS = 1024;   // products of a 32-bit half and a 22-bit limb one column takes without a carry
 void launch_ext_pow_table(hipStream_t st, uint64_t* d_out, const uint64_t alpha[2], uint32_t count);
 
 }  // namespace nlx

@@ -14,6 +14,7 @@
 // transform at all between rounds.
 #include <hip/hip_runtime.h>
 #include "gl.hpp"
+#include "gate_acc.hpp"
 #include "poseidon.hpp"
 #include "poseidon_fast_constants.inc"
 #include "prover.hpp"
@@ -201,87 +202,71 @@ size_t zs_scratch_words(unsigned log_n, uint32_t nc) {
 // =====================================================================================
 // a9: constraint / quotient combiner
 // =====================================================================================
-// Running sums S_c = sum_k alpha_c^k * constraint_k of the gate being evaluated, for both challenges, with
-// LAZY reduction: each 64x64 product is accumulated as four 32x32 partial products into four 64-bit columns
-// (+ a carry counter each) - two instructions per partial product - and the 160-bit total is reduced once per
-// gate.  A reduced multiply-add costs ~30 instructions; this costs 8 per challenge.
-struct GateAcc {
-    const uint64_t* __restrict__ ap0;  // alpha_0^(T0 + k), wave-uniform
-    const uint64_t* __restrict__ ap1;
-    uint64_t a[8];
-    uint32_t kc[8];
+// GateAcc - running sums S_c = sum_k alpha_c^k * constraint_k with lazy reduction - lives in gate_acc.hpp (the generated AIR
+// kernels use it too)
+// GateAcc with a THREE-LIMB multiplier (compile-time switch NLX_GATEACC_LIMBS3, measured against the two-limb form: DESIGN.md §27):
+// every alpha power is three 22-bit limbs (QuotientParams::alpha_limbs), a product of a 32-bit half of the constraint and a limb
+// is below 2^54, so each of the six columns per challenge takes GATEACC3_MAX_TERMS = 1 024 products WITHOUT a carry counter: six
+// multiply-adds per challenge instead of four and four carry additions, in the same 24 registers.  Column (h, j) has the weight
+// 2^(32 h + 22 j); the fold adds them as one integer below 2^141.
+struct GateAcc3 {
+    const uint32_t* __restrict__ lp0;  // limbs of alpha_0^(T0 + k), four words per power, wave-uniform
+    const uint32_t* __restrict__ lp1;
+    uint64_t a[12];
     uint32_t k;
-    uint64_t base[2];   // what stash() folded away so far (canonical)
+    uint64_t base[2];
     __device__ __forceinline__ void reset() {
 #pragma unroll
-        for (int i = 0; i < 8; i++) { a[i] = 0; kc[i] = 0; }
+        for (int i = 0; i < 12; i++) a[i] = 0;
         k = 0;
         base[0] = base[1] = 0;
     }
-    // the 24 registers of the columns -> two canonical sums (PoseidonGate's fused partial rounds need the registers for the
-    // matrix pass between two groups of constraints); the constraint counter keeps running
     __device__ __forceinline__ void stash() {
-        base[0] = gl::add(base[0], fold_columns(a, kc));
-        base[1] = gl::add(base[1], fold_columns(a + 4, kc + 4));
+        base[0] = gl::add(base[0], fold(0));
+        base[1] = gl::add(base[1], fold(1));
 #pragma unroll
-        for (int i = 0; i < 8; i++) { a[i] = 0; kc[i] = 0; }
+        for (int i = 0; i < 12; i++) a[i] = 0;
     }
-    __device__ __forceinline__ void emit_at(uint32_t idx, uint64_t c) { mac(c, ap0[idx], ap1[idx]); }
-    // sums 0 and 1 += c * b0, c * b1 (b0, b1 wave-uniform)
-    __device__ __forceinline__ void mac(uint64_t c, uint64_t b0, uint64_t b1) {
+    __device__ __forceinline__ void emit_at(uint32_t idx, uint64_t c) {
         const uint32_t c0 = (uint32_t)c, c1 = (uint32_t)(c >> 32);
-        asm("v_mad_u64_u32 %[a0], vcc, %[c0], %[p0], %[a0]\n\t"
-            "v_addc_co_u32 %[k0], vcc, 0, %[k0], vcc\n\t"
-            "v_mad_u64_u32 %[a1], vcc, %[c0], %[p1], %[a1]\n\t"
-            "v_addc_co_u32 %[k1], vcc, 0, %[k1], vcc\n\t"
-            "v_mad_u64_u32 %[a2], vcc, %[c1], %[p0], %[a2]\n\t"
-            "v_addc_co_u32 %[k2], vcc, 0, %[k2], vcc\n\t"
-            "v_mad_u64_u32 %[a3], vcc, %[c1], %[p1], %[a3]\n\t"
-            "v_addc_co_u32 %[k3], vcc, 0, %[k3], vcc\n\t"
-            "v_mad_u64_u32 %[a4], vcc, %[c0], %[q0], %[a4]\n\t"
-            "v_addc_co_u32 %[k4], vcc, 0, %[k4], vcc\n\t"
-            "v_mad_u64_u32 %[a5], vcc, %[c0], %[q1], %[a5]\n\t"
-            "v_addc_co_u32 %[k5], vcc, 0, %[k5], vcc\n\t"
-            "v_mad_u64_u32 %[a6], vcc, %[c1], %[q0], %[a6]\n\t"
-            "v_addc_co_u32 %[k6], vcc, 0, %[k6], vcc\n\t"
-            "v_mad_u64_u32 %[a7], vcc, %[c1], %[q1], %[a7]\n\t"
-            "v_addc_co_u32 %[k7], vcc, 0, %[k7], vcc"
-            : [a0] "+v"(a[0]), [a1] "+v"(a[1]), [a2] "+v"(a[2]), [a3] "+v"(a[3]), [a4] "+v"(a[4]), [a5] "+v"(a[5]),
-              [a6] "+v"(a[6]), [a7] "+v"(a[7]), [k0] "+v"(kc[0]), [k1] "+v"(kc[1]), [k2] "+v"(kc[2]), [k3] "+v"(kc[3]),
-              [k4] "+v"(kc[4]), [k5] "+v"(kc[5]), [k6] "+v"(kc[6]), [k7] "+v"(kc[7])
-            : [c0] "v"(c0), [c1] "v"(c1), [p0] "s"((uint32_t)b0), [p1] "s"((uint32_t)(b0 >> 32)), [q0] "s"((uint32_t)b1),
-              [q1] "s"((uint32_t)(b1 >> 32))
-            : "vcc");
+#pragma unroll
+        for (int j = 0; j < 3; j++) {   // plain products: hipcc selects v_mad_u64_u32 with the limb in a scalar register
+            const uint32_t l0 = lp0[4 * idx + j], l1 = lp1[4 * idx + j];
+            a[j] += (uint64_t)c0 * l0;
+            a[3 + j] += (uint64_t)c1 * l0;
+            a[6 + j] += (uint64_t)c0 * l1;
+            a[9 + j] += (uint64_t)c1 * l1;
+        }
     }
     __device__ __forceinline__ void emit(uint64_t c) { emit_at(k++, c); }
-    // sum for challenge ch: A0 + (A1 + A2) 2^32 + A3 2^64 + K0 2^64 + (K1 + K2) 2^96 + K3 2^128 (mod p)
-    __device__ __forceinline__ uint64_t finish(int ch) const { return gl::add(fold_columns(a + 4 * ch, kc + 4 * ch), base[ch]); }
-    // The four 64-bit columns and their carry counts as ONE 160-bit integer (t4 : t3 : t2 : t1 : t0), reduced with
-    // 2^64 = 2^32 - 1, 2^96 = -1, 2^128 = -2^32: (t1:t0) + t2 EPS - t3 - t4 2^32.  ~35 instructions (the first version
-    // reduced every column on its own: ~110, twice per item of k_quotient).
-    static __device__ __forceinline__ uint64_t fold_columns(const uint64_t* A, const uint32_t* K) {
-        uint32_t t1, t2, t3, t4, m0, m1, cm;
-        asm("v_add_co_u32 %[m0], vcc, %[a1l], %[a2l]\n\t"
-            "v_addc_co_u32 %[m1], vcc, %[a1h], %[a2h], vcc\n\t"
-            "v_addc_co_u32 %[cm], vcc, 0, 0, vcc\n\t"
-            "v_add_co_u32 %[t1], vcc, %[a0h], %[m0]\n\t"
-            "v_addc_co_u32 %[t2], vcc, %[m1], %[a3l], vcc\n\t"
-            "v_addc_co_u32 %[t3], vcc, %[cm], %[a3h], vcc\n\t"
-            "v_addc_co_u32 %[t4], vcc, 0, %[k3], vcc\n\t"
-            "v_add_co_u32 %[t2], vcc, %[t2], %[k0]\n\t"
-            "v_addc_co_u32 %[t3], vcc, %[t3], %[k1], vcc\n\t"
-            "v_addc_co_u32 %[t4], vcc, 0, %[t4], vcc\n\t"
-            "v_add_co_u32 %[t3], vcc, %[t3], %[k2]\n\t"
-            "v_addc_co_u32 %[t4], vcc, 0, %[t4], vcc"
-            : [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [t4] "=&v"(t4), [m0] "=&v"(m0), [m1] "=&v"(m1), [cm] "=&v"(cm)
-            : [a0h] "v"((uint32_t)(A[0] >> 32)), [a1l] "v"((uint32_t)A[1]), [a1h] "v"((uint32_t)(A[1] >> 32)), [a2l] "v"((uint32_t)A[2]),
-              [a2h] "v"((uint32_t)(A[2] >> 32)), [a3l] "v"((uint32_t)A[3]), [a3h] "v"((uint32_t)(A[3] >> 32)), [k0] "v"(K[0]),
-              [k1] "v"(K[1]), [k2] "v"(K[2]), [k3] "v"(K[3])
-            : "vcc");
-        const uint64_t r = gl::canon(gl32::to_u64(gl32::reduce128((uint32_t)A[0], t1, t2, t3)));
-        return gl::sub(r, (uint64_t)t4 << 32);
+    __device__ __forceinline__ uint64_t finish(int ch) const { return gl::add(fold(ch), base[ch]); }
+    // sum_{h, j} A[h][j] 2^(32 h + 22 j): all but the top column as one 128-bit integer (< 2^119); of the top column
+    // A 2^76 = (A mod 2^20) 2^76 + (A >> 20) 2^96, the first part joins the integer (still < 2^120) and the second is SUBTRACTED
+    // after the reduction (2^96 = -1; A >> 20 < 2^44 is canonical)
+    __device__ __forceinline__ uint64_t fold(int ch) const {
+        const uint64_t* A = a + 6 * ch;
+        typedef unsigned __int128 u128;
+        const u128 t = (u128)A[0] + ((u128)A[1] << 22) + ((u128)A[2] << 44) + ((u128)A[3] << 32) + ((u128)A[4] << 54) +
+                       ((u128)(A[5] & 0xFFFFFu) << 76);
+        const uint64_t lo = (uint64_t)t, hi = (uint64_t)(t >> 64);
+        return gl::sub(gl::reduce160((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32), 0u), A[5] >> 20);
     }
 };
+#ifdef NLX_GATEACC_LIMBS3
+typedef GateAcc3 QuotAcc;
+#else
+typedef GateAcc QuotAcc;
+#endif
+// points the quotient kernels' accumulator at the alpha powers from term `first` on
+__device__ __forceinline__ void quot_acc_base(QuotAcc& acc, const QuotientParams& p, uint32_t first) {
+#ifdef NLX_GATEACC_LIMBS3
+    acc.lp0 = p.alpha_limbs + 4 * (size_t)first;
+    acc.lp1 = p.alpha_limbs + 4 * ((size_t)p.alpha_stride + first);
+#else
+    acc.ap0 = p.alpha_pows + first;
+    acc.ap1 = p.alpha_pows + p.alpha_stride + first;
+#endif
+}
 
 // sum_i x_i c_i for wave-uniform constants c_i, as ONE running 160-bit sum (GateAcc's columns for a single sum): eight
 // instructions per product and one reduction, where a reduced multiply-add costs 24
@@ -320,6 +305,7 @@ struct Sum128 {
         hi += th + (lo < tl ? 1u : 0u);
     }
     __device__ __forceinline__ uint64_t value() const { return gl::reduce128(lo, hi); }
+    __device__ __forceinline__ uint64_t loose() const { return gl::reduce128_loose(lo, hi); }   // for the left of a gl::sub
 };
 
 // prod_{x < 4} (l - x): the 2-bit limb range check of the u32 gates, as u (u + 2) with u = l (l - 3)
@@ -341,7 +327,9 @@ __device__ __forceinline__ uint64_t sbox7c(uint64_t x) {
     return r;
 }
 // The permutation's linear layer on any-u64 inputs, canonical outputs: 32-bit halves, twelve multiply-accumulates per half
-// and output, the four-instruction fold of gl32.hpp - one output row at a time (a fence per row: see sbox7c)
+// and output, the four-instruction fold of gl32.hpp - one output row at a time (a fence per row: see sbox7c).  CANON = false leaves
+// the outputs loose (three instructions fewer each) for callers that only feed them to an S-box, gl::add_loose or the left of a gl::sub.
+template <bool CANON = true>
 __device__ __forceinline__ void mds_canon(uint64_t (&s)[12]) {
     constexpr uint32_t C[12] = {17, 15, 41, 16, 2, 28, 13, 13, 39, 18, 34, 20};
     uint64_t o[12];
@@ -357,7 +345,7 @@ __device__ __forceinline__ void mds_canon(uint64_t (&s)[12]) {
             al += (uint64_t)(uint32_t)s[0] * 8u;
             ah += (uint64_t)(uint32_t)(s[0] >> 32) * 8u;
         }
-        o[r] = gl::canon(gl32::to_u64(gl32::fold_acc(al, ah)));
+        o[r] = CANON ? gl::canon(gl32::to_u64(gl32::fold_acc(al, ah))) : gl32::to_u64(gl32::fold_acc(al, ah));
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -424,12 +412,12 @@ __device__ __forceinline__ void gate_poseidon_mx(WireFn W, Acc& acc, uint32_t pa
     };
     if (parts & 1u) {
         const uint64_t swap = W(24);
-        acc.emit_at(0, gl::mul(swap, gl::sub(swap, 1)));
+        acc.emit_at(0, gl::mul_loose(swap, gl::sub(swap, 1)));
         uint64_t st[12];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint64_t lhs = W(i), rhs = W(i + 4), delta = W(25 + i);
-            acc.emit_at(1 + i, gl::sub(gl::mul(swap, gl::sub(rhs, lhs)), delta));
+            acc.emit_at(1 + i, gl::sub(gl::mul_loose(swap, gl::sub(rhs, lhs)), delta));
             st[i] = gl::add(lhs, delta);
             st[i + 4] = gl::sub(rhs, delta);
         }
@@ -483,11 +471,11 @@ __device__ __forceinline__ void gate_poseidon_fast(WireFn W, Acc& acc, uint32_t 
     uint64_t st[12];
     if (parts & 1u) {
         const uint64_t swap = W(24);
-        acc.emit_at(0, gl::mul(swap, gl::sub(swap, 1)));
+        acc.emit_at(0, gl::mul_loose(swap, gl::sub(swap, 1)));
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const uint64_t lhs = W(i), rhs = W(i + 4), delta = W(25 + i);
-            acc.emit_at(1 + i, gl::sub(gl::mul(swap, gl::sub(rhs, lhs)), delta));
+            acc.emit_at(1 + i, gl::sub(gl::mul_loose(swap, gl::sub(rhs, lhs)), delta));
             st[i] = gl::add(lhs, delta);
             st[i + 4] = gl::sub(rhs, delta);
         }
@@ -501,12 +489,12 @@ __device__ __forceinline__ void gate_poseidon_fast(WireFn W, Acc& acc, uint32_t 
         for (int r = 0; r < 3; r++) {
 #pragma unroll
             for (int i = 0; i < 12; i++) st[i] = sbox7c(st[i]);
-            mds_canon(st);
+            mds_canon<false>(st);   // loose: each output meets one canonical constant and the left of a gl::sub
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < 12; i++) {
                 const uint64_t in = W(29 + 12 * r + i);
-                acc.emit_at(5 + 12 * r + i, gl::sub(gl::add(st[i], RC[(r + 1) * 12 + i]), in));
+                acc.emit_at(5 + 12 * r + i, gl::sub(gl::add_loose(st[i], RC[(r + 1) * 12 + i]), in));
                 st[i] = in;
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -565,13 +553,13 @@ __device__ __forceinline__ void gate_poseidon_fast(WireFn W, Acc& acc, uint32_t 
             if (r != 0) {
 #pragma unroll
                 for (int i = 0; i < 12; i++) {
-                    acc.emit_at(63 + 12 * r + i, gl::sub(gl::add(st[i], RC[(26 + r) * 12 + i]), W(87 + 12 * r + i)));
+                    acc.emit_at(63 + 12 * r + i, gl::sub(gl::add_loose(st[i], RC[(26 + r) * 12 + i]), W(87 + 12 * r + i)));
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
 #pragma unroll
             for (int i = 0; i < 12; i++) st[i] = sbox7c(W(87 + 12 * r + i));
-            mds_canon(st);
+            mds_canon<false>(st);   // loose: the left of the gl::sub of the next check, or of the output check below
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
@@ -598,6 +586,9 @@ __device__ __forceinline__ void gate_poseidon(WireFn W, Acc& acc, uint32_t parts
 
 // One gate's unfiltered constraints at this lane's point, folded into `acc` with the alpha powers (Gate::eval_unfiltered_base).
 // W(c): wire c of the point; CC(c): constants column c (selectors first) of the point; n = 2^log_n.
+// Reductions are spent only where a contract asks for them: a product that feeds another multiply, the left of a gl::sub (any
+// u64 there, canonical on its right) or acc.emit stays loose (gl::mul_loose, gl::add_loose with the canonical summand second), so
+// a satisfied constraint may reach the accumulator as p instead of 0.
 // Acc: GateAcc in the quotient kernels; the witness checker's CheckAcc records the lowest non-zero constraint instead (an
 // accumulator brings emit, emit_at, the counter k and stash).
 template <class WireFn, class ConstFn, class Acc>
@@ -614,19 +605,19 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
             const uint64_t c0 = CC(p.gate_const0), c1 = CC(p.gate_const0 + 1);
             for (uint32_t i = 0; i < gd.param0; i++) {
                 const uint64_t m0 = W(4 * i), m1 = W(4 * i + 1), ad = W(4 * i + 2), o = W(4 * i + 3);
-                acc.emit(gl::sub(o, gl::add(gl::mul(gl::mul(m0, m1), c0), gl::mul(ad, c1))));
+                acc.emit(gl::sub(o, gl::canon(gl::add_loose(gl::mul_loose(gl::mul_loose(m0, m1), c0), gl::mul(ad, c1)))));
             }
             break;
         }
         case NLX_GATE_BASE_SUM: {
             const uint32_t B = gd.param0, nl = gd.param1;
             uint64_t sum = 0;
-            for (uint32_t i = nl; i-- > 0;) sum = gl::add(gl::mul(sum, (uint64_t)B), W(1 + i));
+            for (uint32_t i = nl; i-- > 0;) sum = gl::add_loose(gl::mul_loose(sum, (uint64_t)B), W(1 + i));
             acc.emit(gl::sub(sum, W(0)));
             for (uint32_t i = 0; i < nl; i++) {
                 const uint64_t limb = W(1 + i);
                 uint64_t prod = 1;
-                for (uint32_t t = 0; t < B; t++) prod = gl::mul(prod, gl::sub(limb, (uint64_t)t));
+                for (uint32_t t = 0; t < B; t++) prod = gl::mul_loose(prod, gl::sub(limb, (uint64_t)t));
                 acc.emit(prod);
             }
             break;
@@ -664,12 +655,12 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
             for (uint32_t i = 0; i < nco; i++) {
                 const uint32_t aw = (i == nco - 1) ? 0 : start_accs + 2 * i;  // last accumulator = output wires
                 const gl::Ext nxt{W(aw), W(aw + 1)};
-                const gl::Ext pr = gl::mul(a, alpha);
+                const gl::Ext pr = gl::mul_loose(a, alpha);
                 if (ext) {
-                    acc.emit(gl::sub(gl::add(pr.a, W(start_coeffs + 2 * i)), nxt.a));
-                    acc.emit(gl::sub(gl::add(pr.b, W(start_coeffs + 2 * i + 1)), nxt.b));
+                    acc.emit(gl::sub(gl::add_loose(pr.a, W(start_coeffs + 2 * i)), nxt.a));
+                    acc.emit(gl::sub(gl::add_loose(pr.b, W(start_coeffs + 2 * i + 1)), nxt.b));
                 } else {
-                    acc.emit(gl::sub(gl::add(pr.a, W(start_coeffs + i)), nxt.a));
+                    acc.emit(gl::sub(gl::add_loose(pr.a, W(start_coeffs + i)), nxt.a));
                     acc.emit(gl::sub(pr.b, nxt.b));
                 }
                 a = nxt;
@@ -700,11 +691,11 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
             const uint64_t base = W(0);
             uint64_t prev_iv = 1;
             for (uint32_t i = 0; i < nb; i++) {
-                const uint64_t prev = i ? gl::mul(prev_iv, prev_iv) : 1;
+                const uint64_t prev = i ? gl::mul_loose(prev_iv, prev_iv) : 1;
                 const uint64_t bit = W(1 + (nb - 1 - i));
-                const uint64_t sel = gl::add(gl::mul(bit, base), gl::sub(1, bit));
+                const uint64_t sel = gl::add_loose(gl::mul_loose(bit, base), gl::sub(1, bit));
                 const uint64_t iv = W(2 + nb + i);
-                acc.emit(gl::sub(gl::mul(prev, sel), iv));
+                acc.emit(gl::sub(gl::mul_loose(prev, sel), iv));
                 prev_iv = iv;
             }
             acc.emit(gl::sub(W(1 + nb), prev_iv));
@@ -717,7 +708,7 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                 uint64_t computed = W(b0 + na);
                 for (uint32_t j = 0; j < na; j++) computed = gl::add(computed, W(b0 + j));
                 const uint64_t res = W(b0 + na + 1), cy = W(b0 + na + 2);
-                acc.emit(gl::sub(gl::add(gl::mul(cy, 1ULL << 32), res), computed));
+                acc.emit(gl::sub(gl::add_loose(gl::mul_loose(cy, 1ULL << 32), res), computed));
                 Sum128 cr, cc;
                 for (uint32_t j = nl; j-- > 0;) {
                     const uint64_t l = W(lb + j);
@@ -725,8 +716,8 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                     if (j < nrl) cr.add(l, 2 * j);
                     else cc.add(l, 2 * (j - nrl));
                 }
-                acc.emit(gl::sub(cr.value(), res));
-                acc.emit(gl::sub(cc.value(), cy));
+                acc.emit(gl::sub(cr.loose(), res));
+                acc.emit(gl::sub(cc.loose(), cy));
             }
             break;
         }
@@ -736,9 +727,9 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                 const uint32_t b0 = 6 * i, lb = 6 * nops + 32 * i;
                 const uint64_t computed = gl::add(gl::mul(W(b0), W(b0 + 1)), W(b0 + 2));
                 const uint64_t lo = W(b0 + 3), hi = W(b0 + 4), inv = W(b0 + 5);
-                const uint64_t hi_not_max = gl::sub(gl::mul(inv, gl::sub(0xFFFFFFFFULL, hi)), 1);
-                acc.emit(gl::mul(hi_not_max, lo));
-                acc.emit(gl::sub(gl::add(gl::mul(hi, 1ULL << 32), lo), computed));
+                const uint64_t hi_not_max = gl::sub(gl::mul_loose(inv, gl::sub(0xFFFFFFFFULL, hi)), 1);
+                acc.emit(gl::mul_loose(hi_not_max, lo));
+                acc.emit(gl::sub(gl::add_loose(gl::mul_loose(hi, 1ULL << 32), lo), computed));
                 Sum128 cl, ch;
                 for (uint32_t j = 32; j-- > 0;) {
                     const uint64_t l = W(lb + j);
@@ -746,8 +737,8 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                     if (j < 16) cl.add(l, 2 * j);
                     else ch.add(l, 2 * (j - 16));
                 }
-                acc.emit(gl::sub(cl.value(), lo));
-                acc.emit(gl::sub(ch.value(), hi));
+                acc.emit(gl::sub(cl.loose(), lo));
+                acc.emit(gl::sub(ch.loose(), hi));
             }
             break;
         }
@@ -764,8 +755,8 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                     acc.emit(limb4(l));
                     c.add(l, 2 * j);
                 }
-                acc.emit(gl::sub(c.value(), res));
-                acc.emit(gl::mul(bo, gl::sub(1, bo)));
+                acc.emit(gl::sub(c.loose(), res));
+                acc.emit(gl::mul_loose(bo, gl::sub(1, bo)));
             }
             break;
         }
@@ -775,7 +766,7 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                 const uint32_t ab = nin + 16 * i;
                 Sum128 sum;
                 for (uint32_t j = 0; j < 16; j++) sum.add(W(ab + j), 2 * j);
-                acc.emit(gl::sub(sum.value(), W(i)));
+                acc.emit(gl::sub(sum.loose(), W(i)));
                 for (uint32_t j = 0; j < 16; j++) acc.emit(limb4(W(ab + j)));
             }
             break;
@@ -788,8 +779,8 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                 fcomb.add(W(fc + i), cb * i);
                 scomb.add(W(sc + i), cb * i);
             }
-            acc.emit(gl::sub(fcomb.value(), W(0)));
-            acc.emit(gl::sub(scomb.value(), W(1)));
+            acc.emit(gl::sub(fcomb.loose(), W(0)));
+            acc.emit(gl::sub(scomb.loose(), W(1)));
             uint64_t msd = 0;
             for (uint32_t i = 0; i < nch; i++) {
                 const uint64_t f = W(fc + i), s2 = W(sc + i);
@@ -801,23 +792,23 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                     p1 = f;
                     p2 = s2;
                     for (uint32_t x2 = 1; x2 < (1u << cb); x2++) {
-                        p1 = gl::mul(p1, gl::sub(f, (uint64_t)x2));
-                        p2 = gl::mul(p2, gl::sub(s2, (uint64_t)x2));
+                        p1 = gl::mul_loose(p1, gl::sub(f, (uint64_t)x2));
+                        p2 = gl::mul_loose(p2, gl::sub(s2, (uint64_t)x2));
                     }
                 }
                 acc.emit(p1);
                 acc.emit(p2);
                 const uint64_t diff = gl::sub(s2, f), e = W(ceq + i), ivv = W(iv + i);
-                acc.emit(gl::sub(gl::mul(diff, W(eqd + i)), gl::sub(1, e)));
-                acc.emit(gl::mul(e, diff));
+                acc.emit(gl::sub(gl::mul_loose(diff, W(eqd + i)), gl::sub(1, e)));
+                acc.emit(gl::mul_loose(e, diff));
                 acc.emit(gl::sub(ivv, gl::mul(e, msd)));
-                msd = gl::add(ivv, gl::mul(gl::sub(1, e), diff));
+                msd = gl::add_loose(gl::mul_loose(gl::sub(1, e), diff), ivv);   // loose: a multiplicand until the last chunk
             }
-            acc.emit(gl::sub(W(3), msd));
+            acc.emit(gl::sub(W(3), gl::canon(msd)));
             uint64_t bc = 0;
             for (uint32_t b = 0; b <= cb; b++) {
                 const uint64_t bit = W(msb + b);
-                acc.emit(gl::mul(bit, gl::sub(1, bit)));
+                acc.emit(gl::mul_loose(bit, gl::sub(1, bit)));
             }
             for (uint32_t b = cb + 1; b-- > 0;) bc = gl::add(gl::add(bc, bc), W(msb + b));
             acc.emit(gl::sub(gl::add(1ULL << cb, W(3)), bc));
@@ -844,11 +835,16 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                 for (uint32_t j = start; j < end; j++) {
                     const uint64_t xj = root_pow(p.w_n_table, j * stride, half);
                     const gl::Ext term{gl::sub(pt.a, xj), pt.b};
-                    const gl::Ext vp = gl::mul(gl::Ext{W(1 + 2 * j), W(2 + 2 * j)}, pr);
-                    ev = gl::add(gl::mul(ev, term), gl::mul(vp, gl::mul(xj, np_inv)));
-                    pr = gl::mul(pr, term);
+                    // ev and pr run loose between two checks: they are multiplicands there (any u64), and each new ev is a
+                    // loose product plus a canonical one
+                    const gl::Ext vp = gl::mul_loose(gl::Ext{W(1 + 2 * j), W(2 + 2 * j)}, pr);
+                    const gl::Ext et = gl::mul_loose(ev, term), vs = gl::mul(vp, gl::mul(xj, np_inv));
+                    ev = gl::Ext{gl::add_loose(et.a, vs.a), gl::add_loose(et.b, vs.b)};
+                    pr = gl::mul_loose(pr, term);
                 }
+                ev = gl::Ext{gl::canon(ev.a), gl::canon(ev.b)};   // the right of a gl::sub below
                 if (c < ni) {
+                    pr = gl::Ext{gl::canon(pr.a), gl::canon(pr.b)};
                     const gl::Ext ie{W(si + 2 * c), W(si + 2 * c + 1)}, ip{W(si + 2 * (ni + c)), W(si + 2 * (ni + c) + 1)};
                     acc.emit(gl::sub(ie.a, ev.a));
                     acc.emit(gl::sub(ie.b, ev.b));
@@ -869,7 +865,7 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                 const uint32_t b0 = (2 + vec) * cpy, bw = rt + cpy * bits;
                 for (uint32_t i = 0; i < bits; i++) {
                     const uint64_t b = W(bw + i);
-                    acc.emit(gl::mul(b, gl::sub(b, 1)));
+                    acc.emit(gl::mul_loose(b, gl::sub(b, 1)));
                 }
                 uint64_t rec = 0;
                 for (uint32_t i = bits; i-- > 0;) rec = gl::add(gl::add(rec, rec), W(bw + i));
@@ -887,10 +883,10 @@ __device__ __forceinline__ void eval_gate(const GateDev& gd, const QuotientParam
                     while (sp > 0 && depth_of[sp - 1] == lvl) {
                         const uint64_t left = stack[--sp];
                         const uint64_t b = W(bw + lvl);
-                        v = gl::add(left, gl::mul(b, gl::sub(v, left)));
+                        v = gl::add_loose(gl::mul_loose(b, gl::sub(v, left)), left);
                         lvl++;
                     }
-                    stack[sp] = v;
+                    stack[sp] = lvl ? gl::canon(v) : v;   // a stacked value is the `left` of a later step: canonical
                     depth_of[sp] = lvl;
                     sp++;
                 }
@@ -964,9 +960,7 @@ __global__ __launch_bounds__(64 * QW, NLX_QMINW) void k_quotient(QuotientParams 
     const uint64_t* ap1 = p.alpha_pows + p.alpha_stride;
     uint64_t tot0 = 0, tot1 = 0;  // sum over all terms EXCEPT the L_0 terms (divided by Z_H later)
     uint64_t l0a = 0, l0b = 0;    // sum_i (Z_i - 1) alpha_c^i, multiplied by L_0(x)/Z_H(x) below
-    GateAcc acc;
-    acc.ap0 = ap0 + T0;
-    acc.ap1 = ap1 + T0;
+    QuotAcc acc;
     const uint32_t* work = p.work + (size_t)wv * p.work_stride;
     for (uint32_t wi = 0;; wi++) {
         const uint32_t word = __builtin_amdgcn_readfirstlane(work[wi]);  // wave-uniform: item in the low half, for a gate evaluated in parts the part mask above it
@@ -978,9 +972,10 @@ __global__ __launch_bounds__(64 * QW, NLX_QMINW) void k_quotient(QuotientParams 
             const uint64_t s = CC(gd.selector_index);
             uint64_t f = 1;
             for (uint32_t i = gd.group_start; i < gd.group_end; i++)
-                if (i != gd.index) f = gl::mul(f, gl::sub((uint64_t)i, s));
-            if (p.n_selectors > 1) f = gl::mul(f, gl::sub(0xFFFFFFFFULL, s));
+                if (i != gd.index) f = gl::mul_loose(f, gl::sub((uint64_t)i, s));   // loose: a multiplicand only
+            if (p.n_selectors > 1) f = gl::mul_loose(f, gl::sub(0xFFFFFFFFULL, s));
             acc.reset();
+            quot_acc_base(acc, p, T0);
             eval_gate(gd, p, W, CC, acc, n, parts);
             tot0 = gl::add(tot0, gl::mul(f, acc.finish(0)));
             tot1 = gl::add(tot1, gl::mul(f, acc.finish(1)));
@@ -1003,6 +998,11 @@ __global__ __launch_bounds__(64 * QW, NLX_QMINW) void k_quotient(QuotientParams 
             l0a = gl::add(l0a, gl::mul(zm1, ap0[c]));
             l0b = gl::add(l0b, gl::mul(zm1, ap1[c]));
             uint64_t accv = z_x;
+            // the partial-product checks of this challenge as unreduced column sums, folded once per item: 16 instructions per
+            // term where two reduced multiply-adds cost 48.  The L_0 term above is ONE product per item and sum: a fold (~30)
+            // would cost more than its reduced multiply-add.
+            acc.reset();
+            quot_acc_base(acc, p, nc + c * (npp + 1));
 #pragma unroll 1
             for (uint32_t q = 0; q < n_chunks; q++) {
                 // numerator / denominator products in loose form (any u64 congruent to the value): w + gamma is shared and
@@ -1015,12 +1015,12 @@ __global__ __launch_bounds__(64 * QW, NLX_QMINW) void k_quotient(QuotientParams 
                     dn = gl::mul_loose(dn, gl::add_loose(gl::mul_loose(beta, sg), wg));
                 }
                 const uint64_t new_acc = (q + 1 < n_chunks) ? ZS(nc + c * npp + q) : z_gx;
-                const uint64_t term = gl::sub(gl::mul(accv, nm), gl::mul(new_acc, dn));
-                const uint32_t t = nc + c * (npp + 1) + q;
-                tot0 = gl::add(tot0, gl::mul(term, ap0[t]));
-                tot1 = gl::add(tot1, gl::mul(term, ap1[t]));
+                const uint64_t term = gl::sub(gl::mul_loose(accv, nm), gl::mul(new_acc, dn));
+                acc.emit_at(q, term);
                 accv = new_acc;
             }
+            tot0 = gl::add(tot0, acc.finish(0));
+            tot1 = gl::add(tot1, acc.finish(1));
         }
     }
     // ---- the waves' partial sums meet in LDS (the tile is dead once every wave is past its last item) ----
@@ -1084,9 +1084,8 @@ __global__ __launch_bounds__(256, 3) void k_quotient_poseidon(QuotientParams p, 
         if (i != gd.index) f = gl::mul(f, gl::sub((uint64_t)i, s));
     if (p.n_selectors > 1) f = gl::mul(f, gl::sub(0xFFFFFFFFULL, s));
     const uint32_t T0 = p.nc + p.nc * (p.npp + 1) + p.nc * p.n_lk_terms;
-    GateAcc acc;
-    acc.ap0 = p.alpha_pows + T0;
-    acc.ap1 = p.alpha_pows + p.alpha_stride + T0;
+    QuotAcc acc;
+    quot_acc_base(acc, p, T0);
     acc.reset();
     gate_poseidon_mx(W, acc, 2u);
     uint64_t t0 = gl::mul(f, acc.finish(0)), t1 = gl::mul(f, acc.finish(1));
@@ -1498,6 +1497,19 @@ __global__ void k_pow_table(uint64_t* __restrict__ out, uint64_t a0, uint64_t a1
     if (t >= count) return;
     out[t] = gl::pow(a0, t);
     out[stride + t] = gl::pow(a1, t);
+}
+// the powers again as three 22-bit limbs each (GateAcc3), four words per power
+__global__ void k_pow_limbs(uint32_t* __restrict__ out, const uint64_t* __restrict__ pows, uint32_t count) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= count) return;
+    const uint64_t v = pows[t];
+    out[4 * t] = (uint32_t)v & 0x3FFFFFu;
+    out[4 * t + 1] = (uint32_t)(v >> 22) & 0x3FFFFFu;
+    out[4 * t + 2] = (uint32_t)(v >> 44);
+    out[4 * t + 3] = 0;
+}
+void launch_pow_limbs(hipStream_t st, uint32_t* d_out, const uint64_t* d_pows, uint32_t count) {
+    hipLaunchKernelGGL(k_pow_limbs, dim3((count + 63) / 64), dim3(64), 0, st, d_out, d_pows, count);
 }
 void launch_pow_table(hipStream_t st, uint64_t* d_out, uint64_t a0, uint64_t a1, uint32_t count, uint32_t stride) {
     hipLaunchKernelGGL(k_pow_table, dim3((count + 63) / 64), dim3(64), 0, st, d_out, a0, a1, count, stride);

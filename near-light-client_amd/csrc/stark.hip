@@ -638,7 +638,12 @@ int32_t stark_stages(nlx_stark* s, StarkCall& sc, nlx_round_fn round_fn, void* u
     uint64_t* d_qvals = scratch.alloc_as<uint64_t>((size_t)nc * Q * 8);
     uint64_t* d_qchunks = scratch.alloc_as<uint64_t>((size_t)nc * Q * 8);
     uint64_t* d_part = n_seg > 1 ? scratch.alloc_as<uint64_t>((size_t)n_seg * nc * Q * 8) : nullptr;
-    if (!d_pis || !d_cols || !d_qvals || !d_qchunks || (n_seg > 1 && !d_part)) return NLX_E_NOMEM;
+    // alpha_c^j for j up to the program's constraint count (no segment emits more): the generated kernels multiply-accumulate
+    // constraint k of a segment of K by alpha^(K - 1 - k), which is what Horner over the segment gives it
+    const uint32_t n_apow = s->n_constraints + 1;
+    uint64_t* d_apow = s->gen ? scratch.alloc_as<uint64_t>((size_t)2 * n_apow * 8) : nullptr;
+    if (!d_pis || !d_cols || !d_qvals || !d_qchunks || (n_seg > 1 && !d_part) || (s->gen && !d_apow)) return NLX_E_NOMEM;
+    if (s->gen) launch_pow_table(st, d_apow, alphas[0], alphas[1], n_apow, n_apow);
     NLX_HIP(ctx, hipMemcpyAsync(d_pis, values.data(), values.size() * 8, hipMemcpyHostToDevice, st));
     NLX_HIP(ctx, hipMemcpyAsync(d_cols, h_cols.data(), (size_t)ncols * 8, hipMemcpyHostToDevice, st));
     {
@@ -649,6 +654,7 @@ int32_t stark_stages(nlx_stark* s, StarkCall& sc, nlx_round_fn round_fn, void* u
         ap.w_n_table = ctx->tables.fwd[log_n];
         ap.out = d_qvals;
         ap.alphas[0] = alphas[0]; ap.alphas[1] = alphas[1];
+        ap.alpha_pows = d_apow; ap.alpha_stride = n_apow;
         ap.g_inv = gl::inv(gl::root_of_unity(log_n));
         ap.log_n = log_n; ap.rate_bits = d.rate_bits; ap.qdb = qdb; ap.n_words = d.n_words; ap.nc = nc;
         ap.n_regs = s->n_regs; ap.n_pis = d.num_public_inputs;
