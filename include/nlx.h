@@ -938,6 +938,48 @@ int32_t nlx_stark_check_trace(nlx_stark* s, const uint64_t* trace, const uint64_
 int32_t nlx_stark_check_rounds(nlx_stark* s, nlx_round_fn round_fn, void* user, const uint64_t* public_inputs,
                                const uint64_t* challenges /* NULL, or sum(round_challenges) canonical values */,
                                nlx_trace_report* report, uint64_t* per_constraint);
+
+/* ---- STARK verifier: does a proof verify, and if not, which check breaks ----
+ * starky::verifier::verify_stark_proof for the proofs nlx_stark_prove / nlx_stark_prove_rounds write (wire format: DESIGN.md
+ * section 8), one proof or a batch of proofs of the same STARK.  The host parses the proof against the layout the descriptor
+ * implies, replays the transcript, checks the proof of work and draws the query indices; the device hashes every Merkle path
+ * (one quad of lanes per proof x query x tree), does the FRI arithmetic (one wave per proof x query) and evaluates the register
+ * program at zeta over the quadratic extension (one lane per proof, one block per program segment).
+ * The verdict names the FIRST failing check in this order: malformed structure; the caller's public inputs; the constraints
+ * at zeta; the proof of work; then the lowest failing query and within it the trace paths in tree order (trace batches, then
+ * the quotient), per FRI layer the fold before the path, and the final polynomial.  Fields that do not apply are 0. */
+#define NLX_VERIFY_ACCEPT        0
+#define NLX_VERIFY_MALFORMED     1  /* length, public-input count, a path-length byte, trailing bytes, a field word >= p */
+#define NLX_VERIFY_PUBLIC_INPUTS 2  /* the caller's expected public inputs differ from the proof's */
+#define NLX_VERIFY_CONSTRAINTS   3  /* sum alpha^i c_i(zeta) != Z_H(zeta) * sum zeta^(n k) q_k(zeta) for `challenge` */
+#define NLX_VERIFY_POW           4
+#define NLX_VERIFY_TRACE_PATH    5  /* an opened row of commitment `tree` does not hash up to its cap, query `query` */
+#define NLX_VERIFY_FRI_FOLD      6  /* layer `layer`: evals[x mod arity] != the value folded so far */
+#define NLX_VERIFY_FRI_PATH      7  /* layer `layer`'s coset does not hash up to that layer's cap */
+#define NLX_VERIFY_FINAL_POLY    8
+typedef struct {
+    uint32_t accepted;   /* 1: the proof verifies */
+    uint32_t reason;     /* NLX_VERIFY_* */
+    uint32_t challenge;  /* CONSTRAINTS: which alpha's identity fails */
+    uint32_t query;      /* from TRACE_PATH on (and a MALFORMED path-length byte): the query */
+    uint32_t tree;       /* TRACE_PATH (and a MALFORMED path-length byte of a commitment): the commitment, in proof order */
+    uint32_t layer;      /* FRI_FOLD, FRI_PATH (and a MALFORMED path-length byte of a FRI layer): the layer */
+    uint64_t x_index;    /* from TRACE_PATH on: the query's index into the LDE, as drawn from the transcript */
+} nlx_stark_verdict;
+/* Both entries return NLX_OK whenever the check ran - the verdict is in *verdict (verdicts[i] for proof i), zero-filled before
+ * anything else happens; on a rejection (of the first rejected proof of a batch) nlx_last_error holds one line naming reason,
+ * query, tree and layer.  public_inputs: NULL - the statement is the one the proof carries - or num_public_inputs canonical
+ * words (per proof, back to back, for a batch) that the proof's must equal.  NLX_E_INVAL: a NULL s, proof, lens or verdict;
+ * NLX_E_RANGE: a caller's public input that is not canonical.  No device address and no loop bound depends on a byte of the
+ * proof.  The first verify of a STARK uploads the periodic columns' interpolation coefficients, which the STARK keeps until
+ * nlx_stark_destroy (each segment's constraint count and the table of the proof's trees travel with every launch); a STARK that
+ * is never verified pays nothing for them at nlx_stark_build.  The register program always runs on the interpreter. */
+int32_t nlx_stark_verify(nlx_stark* s, const uint8_t* proof, size_t len, const uint64_t* public_inputs,
+                         nlx_stark_verdict* verdict);
+int32_t nlx_stark_verify_batch(nlx_stark* s, const uint8_t* const* proofs, const size_t* lens, size_t n_proofs,
+                               const uint64_t* public_inputs, nlx_stark_verdict* verdicts);
+/* the exact length of a proof of this STARK (0 for NULL) */
+size_t nlx_stark_proof_bytes(const nlx_stark* s);
 /* a12: range-check lookups for multi-round AIRs - the log-derivative argument with the challenge in the quadratic
  * extension (starkyx's lookup / bus accumulators are the reason it commits in rounds; its own constraints are not in
  * the reference tree, Cargo.lock:6515).  Constraint side: near-light-client_amd/logup.py.  Witness side, on the device:

@@ -537,6 +537,7 @@ void nlx_stark_destroy(nlx_stark* s) NLX_TRY {
     ctx->release(s->d_seg_first);
     ctx->release(s->d_periodic_rows);
     ctx->release(s->d_check);
+    ctx->release(s->d_verify);
     delete s;   // and with it the stage clock's events
 } NLX_CATCH_VOID(nullptr)
 

@@ -32,5 +32,7 @@ struct nlx_stark {
     uint32_t* d_seg_first = nullptr;
     uint64_t* d_periodic_rows = nullptr;       // [n_periodic][period]: `periodic` as it stands
     uint64_t* d_check = nullptr;               // the checker's counters and minimum (CheckBlock)
+    // the verifier's (stark_verify.hip): made by the first verify, null in a STARK that is never verified
+    uint64_t* d_verify = nullptr;              // [n_periodic][period]: coefficients of the periodic columns' interpolations
     nlx::StageClock clock;
 };

@@ -832,6 +832,10 @@ class Ed25519Prover:
         t0 = self.generate_trace(slots)
         return self.prover.check_rounds(lambda rnd, known: t0 if rnd == 0 else self.round1(known), self.step_tag or [], challenges)
 
+    def verify(self, proof, public_inputs=None):
+        """does the proof verify, and which check breaks if not (StarkProver.verify)"""
+        return self.prover.verify(proof, public_inputs)
+
     def close(self):
         self.prover.close()
         self._t0 = self._t1 = None

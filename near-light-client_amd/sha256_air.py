@@ -443,6 +443,10 @@ class Sha256Prover:
         assert np.array_equal(digest, want)  # the GPU's chaining value is the real SHA-256 digest
         return self.prove_trace(digest), digest
 
+    def verify(self, proof, public_inputs=None):
+        """does the proof verify, and which check breaks if not (StarkProver.verify)"""
+        return self.prover.verify(proof, public_inputs)
+
     def close(self):
         self.prover.close()
         self._trace = self._acc = None

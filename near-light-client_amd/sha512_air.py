@@ -473,6 +473,10 @@ class Sha512Prover:
         pis = [int(v) for v in public_inputs] + (self.step_tag or [])
         return self.prover.check_rounds(lambda rnd, known: self._trace if rnd == 0 else self.round1(known), pis, challenges)
 
+    def verify(self, proof, public_inputs=None):
+        """does the proof verify, and which check breaks if not (StarkProver.verify)"""
+        return self.prover.verify(proof, public_inputs)
+
     def close(self):
         self.prover.close()
         self._trace = self._acc = None

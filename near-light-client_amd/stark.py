@@ -662,6 +662,113 @@ class TraceReport(ctypes.Structure):
         return self
 
 
+VERIFY_REASON_NAMES = ("accept", "malformed", "public inputs", "constraints", "proof of work", "trace path", "FRI fold", "FRI path",
+                       "final polynomial")
+(VERIFY_ACCEPT, VERIFY_MALFORMED, VERIFY_PUBLIC_INPUTS, VERIFY_CONSTRAINTS, VERIFY_POW, VERIFY_TRACE_PATH, VERIFY_FRI_FOLD,
+ VERIFY_FRI_PATH, VERIFY_FINAL_POLY) = range(9)
+
+
+class Verdict(ctypes.Structure):
+    """nlx_stark_verdict (include/nlx.h): what nlx_stark_verify / nlx_stark_verify_batch found.  `message`: the library's line
+    (for the first rejected proof of a batch; a generic one for the others)."""
+    _fields_ = [("accepted", ctypes.c_uint32), ("reason", ctypes.c_uint32), ("challenge", ctypes.c_uint32), ("query", ctypes.c_uint32),
+                ("tree", ctypes.c_uint32), ("layer", ctypes.c_uint32), ("x_index", ctypes.c_uint64)]
+    message = ""
+
+    @property
+    def ok(self):
+        return self.accepted == 1
+
+    @property
+    def reason_name(self):
+        return VERIFY_REASON_NAMES[self.reason] if self.reason < len(VERIFY_REASON_NAMES) else "?"
+
+    def __str__(self):
+        if self.ok:
+            return "the proof verifies"
+        return self.message or "the proof does not verify: %s, challenge %d, query %d (x_index %d), tree %d, layer %d" % (
+            self.reason_name, self.challenge, self.query, self.x_index, self.tree, self.layer)
+
+    def raise_if_rejected(self):
+        if not self.ok:
+            raise ValueError(str(self))
+        return self
+
+
+def fri_num_layers(degree_bits, rate_bits, cap_height, arity_bits, final_poly_bits):
+    """FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits): reduction rounds of a proof"""
+    r = 0
+    while degree_bits > final_poly_bits and degree_bits + rate_bits >= cap_height + arity_bits:
+        if degree_bits < arity_bits:
+            break
+        degree_bits -= arity_bits
+        r += 1
+    return r
+
+
+class _Span(tuple):
+    """(byte offset, byte length) of a part of a proof"""
+    __slots__ = ()
+    offset = property(lambda self: self[0])
+    length = property(lambda self: self[1])
+
+
+def proof_layout(stark):
+    """Where everything lies in a proof of `stark` (a Stark, or anything with a `.desc`), from the descriptor alone: a dict of
+    (byte offset, byte length) pairs - "caps" (and "cap"[o] per commitment: the trace batches, then the quotient), "openings"
+    ("local", "next", "quotient"), "fri_caps" ("fri_cap"[k]), "query"[q] = {"row"[o], "path_len"[o], "path"[o], "layer"[k] =
+    {"evals", "path_len", "path"}}, "final_poly", "pow_witness", "num_public_inputs", "public_inputs", "round_values" - and
+    "total", the length of the proof; "oracle_cols", "n_layers" and "arity" describe the shape (csrc/stark_proof_layout.hpp)."""
+    d = stark.desc if hasattr(stark, "desc") else stark
+    n_rounds = d.n_rounds if d.n_rounds else 1
+    oracle_cols = []
+    for r in range(n_rounds):
+        rc = d.round_cols[r] if d.n_rounds else d.n_cols
+        nb = -(-rc // d.batch_cols) if d.batch_cols and rc > d.batch_cols else 1
+        oracle_cols += [rc if nb == 1 else min(d.batch_cols, rc - k * d.batch_cols) for k in range(nb)]
+    nq = d.num_challenges * d.quotient_degree_factor
+    oracle_cols.append(nq)
+    n_rv = sum(d.round_values[r] for r in range(d.n_rounds))
+    log_l = d.degree_bits + d.rate_bits
+    layers = fri_num_layers(d.degree_bits, d.rate_bits, d.cap_height, d.fri_arity_bits, d.fri_final_poly_bits)
+    arity = 1 << d.fri_arity_bits
+    capb = 32 << d.cap_height
+    out = {"oracle_cols": oracle_cols, "n_layers": layers, "arity": arity}
+    at = 0
+
+    def take(n):
+        nonlocal at
+        sp = _Span((at, n))
+        at += n
+        return sp
+
+    out["cap"] = [take(capb) for _ in oracle_cols]
+    out["caps"] = _Span((0, at))
+    out["local"], out["next"], out["quotient"] = take(16 * d.n_cols), take(16 * d.n_cols), take(16 * nq)
+    out["openings"] = _Span((out["local"][0], at - out["local"][0]))
+    out["fri_cap"] = [take(capb) for _ in range(layers)]
+    out["fri_caps"] = _Span((out["openings"][0] + out["openings"][1], capb * layers))
+    out["query"] = []
+    for _ in range(d.fri_num_queries):
+        q = {"row": [], "path_len": [], "path": [], "layer": []}
+        for w in oracle_cols:
+            q["row"].append(take(8 * w))
+            q["path_len"].append(take(1))
+            q["path"].append(take(32 * (log_l - d.cap_height)))
+        lg = log_l
+        for _k in range(layers):
+            lg -= d.fri_arity_bits
+            q["layer"].append({"evals": take(16 * arity), "path_len": take(1), "path": take(32 * max(lg - d.cap_height, 0))})
+        out["query"].append(q)
+    out["final_poly"] = take(16 << (d.degree_bits - layers * d.fri_arity_bits))
+    out["pow_witness"] = take(8)
+    out["num_public_inputs"] = take(8)
+    out["public_inputs"] = take(8 * d.num_public_inputs)
+    out["round_values"] = take(8 * n_rv)
+    out["total"] = at
+    return out
+
+
 class StarkProver:
     """Device-resident prover for one Stark (nlx_stark_build / nlx_stark_prove)."""
 
@@ -784,6 +891,44 @@ class StarkProver:
             raise errors[0]
         self.ctx.check(rc)
         return self._finish_report(rep, counts)
+
+    @property
+    def proof_bytes(self):
+        """the exact length of a proof of this STARK (nlx_stark_proof_bytes)"""
+        return dll.nlx_stark_proof_bytes(self.handle)
+
+    def verify(self, proof, public_inputs=None):
+        """nlx_stark_verify: does the proof verify, and which check breaks if not (a Verdict).  public_inputs: None - the
+        statement is the one the proof carries - or the values the proof's public inputs must equal."""
+        return self.verify_many([proof], None if public_inputs is None else [public_inputs])[0]
+
+    def verify_many(self, proofs, public_inputs=None):
+        """nlx_stark_verify_batch: a list of proofs of this STARK in one pass over the GPU; a Verdict per proof.
+        public_inputs: None, or one sequence of values per proof."""
+        proofs = [bytes(p) for p in proofs]
+        n = len(proofs)
+        if n == 0:
+            return []
+        n_pis = self.stark.air.num_public_inputs
+        pis = None
+        if public_inputs is not None:
+            pis = np.ascontiguousarray([[int(v) for v in row] for row in public_inputs], dtype=np.uint64).reshape(n, -1)
+            if pis.shape != (n, n_pis):
+                raise ValueError("expected %d public inputs per proof" % n_pis)
+        keep = [ctypes.create_string_buffer(p, max(len(p), 1)) for p in proofs]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in keep])
+        lens = (ctypes.c_size_t * n)(*[len(p) for p in proofs])
+        verdicts = (Verdict * n)()
+        self.ctx.check(dll.nlx_stark_verify_batch(self.handle, ptrs, lens, n, pis.ctypes.data if pis is not None and pis.size else None,
+                                                  verdicts))
+        out = list(verdicts)
+        first = True
+        for v in out:
+            v._keep = verdicts   # the elements are views of the array
+            if not v.ok and first:
+                v.message = dll.nlx_last_error(self.ctx.handle).decode()
+                first = False
+        return out
 
     def prove_into(self, trace, public_inputs_ptr):
         ln = ctypes.c_size_t()
