@@ -182,6 +182,13 @@ SIGNATURES = {
     "nlx_stark_verify_batch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                 ctypes.c_void_p]),
     "nlx_stark_proof_bytes": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "nlx_verifier_from_circuit": (ctypes.c_int32, [ctypes.c_void_p, c_void_pp]),
+    "nlx_verifier_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
+    "nlx_verifier_destroy": (None, [ctypes.c_void_p]),
+    "nlx_verifier_proof_bytes": (ctypes.c_size_t, [ctypes.c_void_p]),
+    "nlx_verify": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_verify_batch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
     "nlx_logup_multiplicities": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
                                                   ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]),
     "nlx_logup_round_cols": (ctypes.c_uint32, [ctypes.c_uint32, ctypes.c_uint32]),

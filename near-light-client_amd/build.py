@@ -95,6 +95,12 @@ def build_lib(force=False, verbose=False):
     if WITH_AIRGEN:
         _generate_air_kernels()
     hm, hm_gen = _headers_mtime(), _headers_mtime(AIRGEN_HEADERS)
+    # both libraries there and no source or header newer than either: nothing to do, whether or not the object cache came along
+    # (a tree copied without its objects must not recompile what it already carries linked)
+    if not force and os.path.exists(LIB) and os.path.exists(SYNTH_LIB):
+        newest = max([hm] + [os.path.getmtime(os.path.join(CSRC, s)) for s in _sources()])
+        if newest <= min(os.path.getmtime(LIB), os.path.getmtime(SYNTH_LIB)):
+            return LIB
     todo, objs, synth_objs = [], [], []
     for src in _sources():
         obj = os.path.join(OBJ, src.replace(os.sep, "_") + ".o")

@@ -134,19 +134,21 @@ struct nlx_circuit {
     size_t L() const { return (size_t)1 << (d.degree_bits + d.rate_bits); }
 };
 
+namespace nlx {
+nlx_ctx* circuit_ctx(const nlx_circuit* c) { return c->ctx; }
+const nlx_circuit_desc& circuit_desc(const nlx_circuit* c) { return c->d; }
+}  // namespace nlx
+
 namespace {
 // every commitment of a circuit's proofs carries the circuit's hasher
 int32_t commit_for(nlx_circuit* c, const uint64_t* d_in, CommitInput kind, uint32_t n_cols, CommitPtr& out) {
     return commit_build(c->ctx, d_in, c->n(), kind, n_cols, c->d.degree_bits, c->d.rate_bits, c->d.cap_height, out, 0, 0, c->hasher, c->d_bad);
 }
 
-int32_t circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants, const uint64_t* sigmas,
-                      uint32_t hasher, nlx_circuit** out) {
-    if (!ctx) return NLX_E_INVAL;
-    if (!desc || !constants || !sigmas || !out || !desc->gates || !desc->k_is)
-        return ctx->fail(NLX_E_INVAL, "NULL argument");
-    *out = nullptr;
-    const nlx_circuit_desc& d = *desc;
+// The descriptor checks every consumer of a circuit shares: nlx_circuit_build and the verifier built from a verifying key alone
+// (plonk_verify.hip).  The message is left in ctx.
+}  // namespace
+int32_t nlx::validate_circuit_desc(nlx_ctx* ctx, const nlx_circuit_desc& d, uint32_t hasher) {
     if (d.num_challenges < 1 || d.num_challenges > 2) return ctx->fail(NLX_E_UNSUPPORTED, "num_challenges must be 1 or 2");
     if (d.rate_bits < 1 || d.rate_bits > 3) return ctx->fail(NLX_E_UNSUPPORTED, "rate_bits must be in [1, 3]");
     if ((1u << d.rate_bits) != d.quotient_degree_factor)
@@ -222,6 +224,17 @@ int32_t circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t
                 return ctx->fail(NLX_E_INVAL, "table %u: row counts do not match its lookups / entries", t);
         }
     }
+    return NLX_OK;
+}
+namespace {
+int32_t circuit_build(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants, const uint64_t* sigmas,
+                      uint32_t hasher, nlx_circuit** out) {
+    if (!ctx) return NLX_E_INVAL;
+    if (!desc || !constants || !sigmas || !out || !desc->gates || !desc->k_is)
+        return ctx->fail(NLX_E_INVAL, "NULL argument");
+    *out = nullptr;
+    const nlx_circuit_desc& d = *desc;
+    NLX_RC(validate_circuit_desc(ctx, d, hasher));
     (void)hipSetDevice(ctx->device);
     nlx_circuit* c = new (std::nothrow) nlx_circuit();
     if (!c) return ctx->fail(NLX_E_NOMEM, "host allocation failed");

@@ -11,6 +11,14 @@ struct GateDev {
     uint32_t kind, selector_index, group_start, group_end, index, param0, param1;
 };
 
+// What the verifier's constructor reads of a built circuit (plonk_verify.hip; struct nlx_circuit stays private to prover.hip):
+// its context, and its descriptor with the circuit's own copies of the gates, k_is and lookup tables and the digest filled in.
+nlx_ctx* circuit_ctx(const nlx_circuit* c);
+const nlx_circuit_desc& circuit_desc(const nlx_circuit* c);
+// nlx_circuit_build's checks of a descriptor (parameter ranges, every gate within the wires, the lookup rows), shared with
+// nlx_verifier_create; the message goes to ctx
+int32_t validate_circuit_desc(nlx_ctx* ctx, const nlx_circuit_desc& d, uint32_t hasher);
+
 struct ZsParams {
     const uint64_t* wires;      // [col][n] subgroup values
     size_t wires_stride;

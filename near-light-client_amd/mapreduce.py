@@ -254,6 +254,12 @@ class GpuTreeProver:
         finally:
             self.free.put(wk)
 
+    def verify_many(self, kind, level, proofs):
+        """The proofs of one (kind, level) - all of one circuit - through nlx_verify_batch on worker 0's circuit of that (kind,
+        level): a Verdict per proof.  Nothing calls this by default."""
+        _, cd, _ = self.workers[0]["circ"][(kind, level if kind == "reduce" else 0)]
+        return cd.verify_many(proofs)
+
     def prove_many(self, jobs):
         if len(self.workers) == 1 or len(jobs) <= 1:
             return [self(*job) for job in jobs]

@@ -164,6 +164,147 @@ class WitnessReport(ctypes.Structure):
         return self
 
 
+def _lookup_polys(d):
+    """num_challenges * (1 + S) lookup polynomials of a descriptor with tables, else 0"""
+    if not d.num_luts:
+        return 0
+    lu_degree = d.quotient_degree_factor - 1
+    return d.num_challenges * (1 + (d.num_routed_wires // 2 + lu_degree - 1) // lu_degree)
+
+
+def proof_layout(circuit):
+    """Where everything lies in a ProofWithPublicInputs of a circuit (a VerifierData, a CircuitData, a SyntheticCircuit, or a
+    CircuitDesc), from the descriptor alone: a dict of (byte offset, byte length) pairs - "caps" ("cap"[0 .. 2]: wires,
+    zs_partial, quotient), "openings" and its classes "constants", "sigmas", "wires", "zs", "zs_next", "lookup_zs",
+    "lookup_zs_next", "partial_products", "quotient", "fri_caps" ("fri_cap"[k]), "query"[q] = {"row"[t], "path_len"[t], "path"[t]
+    for the trees t = constants_sigmas, wires, zs_partial, quotient, "layer"[k] = {"evals", "path_len", "path"}}, "final_poly",
+    "pow_witness", "num_public_inputs", "public_inputs" - and "total", the length of the proof; "tree_cols", "n_layers" and
+    "arity" describe the shape (csrc/plonk_proof_layout.hpp)."""
+    from .stark import _Span, fri_num_layers
+    d = circuit
+    if hasattr(d, "_desc"):
+        d = d._desc
+    elif hasattr(d, "desc"):
+        d = d.desc()
+    nc, nlk = d.num_challenges, _lookup_polys(d)
+    n_consts = d.num_selectors + (4 + d.num_luts if d.num_luts else 0) + d.num_constants
+    n_q = nc * d.quotient_degree_factor
+    tree_cols = [n_consts + d.num_routed_wires, d.num_wires, nc * (1 + d.num_partial_products) + nlk, n_q]
+    log_l = d.degree_bits + d.rate_bits
+    layers = fri_num_layers(d.degree_bits, d.rate_bits, d.cap_height, d.fri_arity_bits, d.fri_final_poly_bits)
+    arity = 1 << d.fri_arity_bits
+    capb = 32 << d.cap_height
+    out = {"tree_cols": tree_cols, "n_layers": layers, "arity": arity}
+    at = 0
+
+    def take(n):
+        nonlocal at
+        sp = _Span((at, n))
+        at += n
+        return sp
+
+    out["cap"] = [take(capb) for _ in range(3)]
+    out["caps"] = _Span((0, at))
+    for name, count in (("constants", n_consts), ("sigmas", d.num_routed_wires), ("wires", d.num_wires), ("zs", nc), ("zs_next", nc),
+                        ("lookup_zs", nlk), ("lookup_zs_next", nlk), ("partial_products", nc * d.num_partial_products),
+                        ("quotient", n_q)):
+        out[name] = take(16 * count)
+    out["openings"] = _Span((out["constants"][0], at - out["constants"][0]))
+    out["fri_cap"] = [take(capb) for _ in range(layers)]
+    out["fri_caps"] = _Span((out["openings"][0] + out["openings"][1], capb * layers))
+    out["query"] = []
+    for _ in range(d.fri_num_queries):
+        q = {"row": [], "path_len": [], "path": [], "layer": []}
+        for w in tree_cols:
+            q["row"].append(take(8 * w))
+            q["path_len"].append(take(1))
+            q["path"].append(take(32 * (log_l - d.cap_height)))
+        lg = log_l
+        for _k in range(layers):
+            lg -= d.fri_arity_bits
+            q["layer"].append({"evals": take(16 * arity), "path_len": take(1), "path": take(32 * max(lg - d.cap_height, 0))})
+        out["query"].append(q)
+    out["final_poly"] = take(16 << (d.degree_bits - layers * d.fri_arity_bits))
+    out["pow_witness"] = take(8)
+    out["num_public_inputs"] = take(8)
+    out["public_inputs"] = take(8 * d.num_public_inputs)
+    out["total"] = at
+    return out
+
+
+class VerifierData:
+    """plonky2's VerifierCircuitData on the GPU (nlx_verifier): the common data - the descriptor - and the verifier-only data,
+    constants_sigmas_cap and circuit_digest.  Needs none of the prover's tables.  verify / verify_many return Verdicts
+    (stark.Verdict: .ok, .reason_name, .message, .raise_if_rejected())."""
+
+    def __init__(self, ctx, desc, constants_sigmas_cap, circuit_digest, _from_circuit=None):
+        self.ctx = ctx
+        self._desc = desc   # keeps gates / k_is / tables alive while the library copies them
+        h = ctypes.c_void_p()
+        if _from_circuit is not None:
+            ctx.check(dll.nlx_verifier_from_circuit(_from_circuit, ctypes.byref(h)))
+        else:
+            cap = np.ascontiguousarray(constants_sigmas_cap, dtype=np.uint64).reshape(-1)
+            if cap.size != 4 << desc.cap_height:
+                raise ValueError("constants_sigmas_cap must hold %d words" % (4 << desc.cap_height))
+            dig = np.ascontiguousarray(circuit_digest, dtype=np.uint64).reshape(-1)
+            if dig.size != 4:
+                raise ValueError("circuit_digest must hold 4 words")
+            ctx.check(dll.nlx_verifier_create(ctx.handle, ctypes.byref(desc), ptr(cap), ptr(dig), ctypes.byref(h)))
+        self.handle = h
+        self.num_public_inputs = desc.num_public_inputs
+        ctx._adopt(self)
+
+    @property
+    def proof_bytes(self):
+        """the exact length of a proof of this circuit (nlx_verifier_proof_bytes)"""
+        return dll.nlx_verifier_proof_bytes(self.handle)
+
+    def verify(self, proof, public_inputs=None):
+        """nlx_verify: does the proof verify, and which check breaks if not (a Verdict).  public_inputs: None - the statement is
+        the one the proof carries - or the values the proof's public inputs must equal."""
+        return self.verify_many([proof], None if public_inputs is None else [public_inputs])[0]
+
+    def verify_many(self, proofs, public_inputs=None):
+        """nlx_verify_batch: a list of proofs of this circuit in one pass over the GPU; a Verdict per proof.  public_inputs:
+        None, or one sequence of values per proof."""
+        from .stark import Verdict
+        proofs = [bytes(p) for p in proofs]
+        n = len(proofs)
+        if n == 0:
+            return []
+        pis = None
+        if public_inputs is not None:
+            pis = np.ascontiguousarray([[int(v) for v in row] for row in public_inputs], dtype=np.uint64).reshape(n, -1)
+            if pis.shape != (n, self.num_public_inputs):
+                raise ValueError("expected %d public inputs per proof" % self.num_public_inputs)
+        keep = [ctypes.create_string_buffer(p, max(len(p), 1)) for p in proofs]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in keep])
+        lens = (ctypes.c_size_t * n)(*[len(p) for p in proofs])
+        verdicts = (Verdict * n)()
+        self.ctx.check(dll.nlx_verify_batch(self.handle, ptrs, lens, n, pis.ctypes.data if pis is not None and pis.size else None,
+                                            verdicts))
+        out = list(verdicts)
+        first = True
+        for v in out:
+            v._keep = verdicts   # the elements are views of the array
+            if not v.ok and first:
+                v.message = dll.nlx_last_error(self.ctx.handle).decode()
+                first = False
+        return out
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            dll.nlx_verifier_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class CircuitData:
     """Prover-side circuit data resident on the GPU (CircuitBuilder::build output)."""
 
@@ -233,6 +374,22 @@ class CircuitData:
             rep.message = dll.nlx_last_error(self.ctx.handle).decode()
         return rep
 
+    def verifier_data(self):
+        """the circuit's VerifierData (nlx_verifier_from_circuit), made on first use and kept; NlxError NLX_E_UNSUPPORTED for a
+        circuit under the PoseidonBN128 config"""
+        if getattr(self, "_verifier", None) is None or not self._verifier.handle:
+            self._verifier = VerifierData(self.ctx, self._desc, None, None, _from_circuit=self.handle)
+        return self._verifier
+
+    def verify(self, proof, public_inputs=None):
+        """does `proof` verify on the device, and which check breaks if not: cd.verify(proof).raise_if_rejected()"""
+        return self.verifier_data().verify(proof, public_inputs)
+
+    def verify_many(self, proofs, public_inputs=None):
+        """a list of proofs of this circuit in one pass over the GPU; a Verdict per proof"""
+        proofs = list(proofs)
+        return self.verifier_data().verify_many(proofs, public_inputs) if proofs else []
+
     # ---- stage-level calls (the fine seam) ----
     def constants_sigmas_batch(self):
         """The circuit's constants + sigmas commitment (FRI oracle 0); borrowed, lives as long as the circuit."""
@@ -279,6 +436,9 @@ class CircuitData:
         return [(names[i].decode(), ms[i]) for i in range(n.value)]
 
     def close(self):
+        if getattr(self, "_verifier", None) is not None:
+            self._verifier.close()
+            self._verifier = None
         if self.handle and self.ctx.handle:
             dll.nlx_circuit_destroy(self.handle)
         self.handle = None

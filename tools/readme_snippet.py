@@ -5,6 +5,7 @@ syn = nlx.SyntheticCircuit(14, seed=1, pct_poseidon=25, pct_arithmetic=20, pct_u
 cd = nlx.CircuitData.from_synthetic(ctx, syn)
 proof = cd.prove(syn.wires, syn.public_inputs)
 cd.check_witness(syn.wires, syn.public_inputs).raise_if_unsatisfied()
+cd.verify(proof).raise_if_rejected()
 print("plonky2 proof", len(proof))
 S = nlx.stark
 air = S.Air(2, 3)
