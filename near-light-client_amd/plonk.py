@@ -180,7 +180,7 @@ def proof_layout(circuit):
     for the trees t = constants_sigmas, wires, zs_partial, quotient, "layer"[k] = {"evals", "path_len", "path"}}, "final_poly",
     "pow_witness", "num_public_inputs", "public_inputs" - and "total", the length of the proof; "tree_cols", "n_layers" and
     "arity" describe the shape (csrc/plonk_proof_layout.hpp)."""
-    from .stark import _Span, fri_num_layers
+    from .stark import _Span, _Taker, _layout_queries_and_tail
     d = circuit
     if hasattr(d, "_desc"):
         d = d._desc
@@ -190,45 +190,17 @@ def proof_layout(circuit):
     n_consts = d.num_selectors + (4 + d.num_luts if d.num_luts else 0) + d.num_constants
     n_q = nc * d.quotient_degree_factor
     tree_cols = [n_consts + d.num_routed_wires, d.num_wires, nc * (1 + d.num_partial_products) + nlk, n_q]
-    log_l = d.degree_bits + d.rate_bits
-    layers = fri_num_layers(d.degree_bits, d.rate_bits, d.cap_height, d.fri_arity_bits, d.fri_final_poly_bits)
-    arity = 1 << d.fri_arity_bits
-    capb = 32 << d.cap_height
-    out = {"tree_cols": tree_cols, "n_layers": layers, "arity": arity}
-    at = 0
-
-    def take(n):
-        nonlocal at
-        sp = _Span((at, n))
-        at += n
-        return sp
-
-    out["cap"] = [take(capb) for _ in range(3)]
-    out["caps"] = _Span((0, at))
+    out = {"tree_cols": tree_cols}
+    take = _Taker()
+    out["cap"] = [take(32 << d.cap_height) for _ in range(3)]
+    out["caps"] = _Span((0, take.at))
     for name, count in (("constants", n_consts), ("sigmas", d.num_routed_wires), ("wires", d.num_wires), ("zs", nc), ("zs_next", nc),
                         ("lookup_zs", nlk), ("lookup_zs_next", nlk), ("partial_products", nc * d.num_partial_products),
                         ("quotient", n_q)):
         out[name] = take(16 * count)
-    out["openings"] = _Span((out["constants"][0], at - out["constants"][0]))
-    out["fri_cap"] = [take(capb) for _ in range(layers)]
-    out["fri_caps"] = _Span((out["openings"][0] + out["openings"][1], capb * layers))
-    out["query"] = []
-    for _ in range(d.fri_num_queries):
-        q = {"row": [], "path_len": [], "path": [], "layer": []}
-        for w in tree_cols:
-            q["row"].append(take(8 * w))
-            q["path_len"].append(take(1))
-            q["path"].append(take(32 * (log_l - d.cap_height)))
-        lg = log_l
-        for _k in range(layers):
-            lg -= d.fri_arity_bits
-            q["layer"].append({"evals": take(16 * arity), "path_len": take(1), "path": take(32 * max(lg - d.cap_height, 0))})
-        out["query"].append(q)
-    out["final_poly"] = take(16 << (d.degree_bits - layers * d.fri_arity_bits))
-    out["pow_witness"] = take(8)
-    out["num_public_inputs"] = take(8)
-    out["public_inputs"] = take(8 * d.num_public_inputs)
-    out["total"] = at
+    out["openings"] = _Span((out["constants"][0], take.at - out["constants"][0]))
+    _layout_queries_and_tail(out, take, d, tree_cols)
+    out["total"] = take.at
     return out
 
 
@@ -268,30 +240,8 @@ class VerifierData:
     def verify_many(self, proofs, public_inputs=None):
         """nlx_verify_batch: a list of proofs of this circuit in one pass over the GPU; a Verdict per proof.  public_inputs:
         None, or one sequence of values per proof."""
-        from .stark import Verdict
-        proofs = [bytes(p) for p in proofs]
-        n = len(proofs)
-        if n == 0:
-            return []
-        pis = None
-        if public_inputs is not None:
-            pis = np.ascontiguousarray([[int(v) for v in row] for row in public_inputs], dtype=np.uint64).reshape(n, -1)
-            if pis.shape != (n, self.num_public_inputs):
-                raise ValueError("expected %d public inputs per proof" % self.num_public_inputs)
-        keep = [ctypes.create_string_buffer(p, max(len(p), 1)) for p in proofs]
-        ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in keep])
-        lens = (ctypes.c_size_t * n)(*[len(p) for p in proofs])
-        verdicts = (Verdict * n)()
-        self.ctx.check(dll.nlx_verify_batch(self.handle, ptrs, lens, n, pis.ctypes.data if pis is not None and pis.size else None,
-                                            verdicts))
-        out = list(verdicts)
-        first = True
-        for v in out:
-            v._keep = verdicts   # the elements are views of the array
-            if not v.ok and first:
-                v.message = dll.nlx_last_error(self.ctx.handle).decode()
-                first = False
-        return out
+        from .stark import verify_many
+        return verify_many(self.ctx, dll.nlx_verify_batch, self.handle, self.num_public_inputs, proofs, public_inputs)
 
     def close(self):
         if self.handle and self.ctx.handle:

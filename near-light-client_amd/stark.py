@@ -713,6 +713,70 @@ class _Span(tuple):
     length = property(lambda self: self[1])
 
 
+class _Taker:
+    """take(n): the span of the next n bytes of a proof; .at: where the next one starts"""
+    at = 0
+
+    def __call__(self, n):
+        sp = _Span((self.at, n))
+        self.at += n
+        return sp
+
+
+def _layout_queries_and_tail(out, take, d, tree_cols):
+    """What every proof with a FRI proof in it has after its openings, for both proof_layout functions (here and in plonk.py):
+    "n_layers", "arity", "fri_cap"[k], "fri_caps", "query"[q] over the initial trees of widths tree_cols and the layers,
+    "final_poly", "pow_witness", "num_public_inputs", "public_inputs"."""
+    log_l = d.degree_bits + d.rate_bits
+    layers = out["n_layers"] = fri_num_layers(d.degree_bits, d.rate_bits, d.cap_height, d.fri_arity_bits, d.fri_final_poly_bits)
+    arity = out["arity"] = 1 << d.fri_arity_bits
+    out["fri_cap"] = [take(32 << d.cap_height) for _ in range(layers)]
+    out["fri_caps"] = _Span((out["openings"][0] + out["openings"][1], (32 << d.cap_height) * layers))
+    out["query"] = []
+    for _ in range(d.fri_num_queries):
+        q = {"row": [], "path_len": [], "path": [], "layer": []}
+        for w in tree_cols:
+            q["row"].append(take(8 * w))
+            q["path_len"].append(take(1))
+            q["path"].append(take(32 * (log_l - d.cap_height)))
+        lg = log_l
+        for _k in range(layers):
+            lg -= d.fri_arity_bits
+            q["layer"].append({"evals": take(16 * arity), "path_len": take(1), "path": take(32 * max(lg - d.cap_height, 0))})
+        out["query"].append(q)
+    out["final_poly"] = take(16 << (d.degree_bits - layers * d.fri_arity_bits))
+    out["pow_witness"] = take(8)
+    out["num_public_inputs"] = take(8)
+    out["public_inputs"] = take(8 * d.num_public_inputs)
+
+
+def verify_many(ctx, batch_fn, handle, n_pis, proofs, public_inputs):
+    """The marshalling of nlx_stark_verify_batch and nlx_verify_batch (batch_fn) for the proofs of one STARK or circuit (handle): a
+    Verdict per proof, the library's line on the first rejected one.  public_inputs: None, or n_pis values per proof."""
+    proofs = [bytes(p) for p in proofs]
+    n = len(proofs)
+    if n == 0:
+        return []
+    pis = None
+    if public_inputs is not None:
+        pis = np.ascontiguousarray([[int(v) for v in row] for row in public_inputs], dtype=np.uint64).reshape(n, -1)
+        if pis.shape != (n, n_pis):
+            raise ValueError("expected %d public inputs per proof" % n_pis)
+    keep = [ctypes.create_string_buffer(p, max(len(p), 1)) for p in proofs]
+    ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in keep])
+    lens = (ctypes.c_size_t * n)(*[len(p) for p in proofs])
+    verdicts = (Verdict * n)()
+    ctx.check(batch_fn(handle, ptrs, lens, n, pis.ctypes.data if pis is not None and pis.size else None, verdicts))
+    out = list(verdicts)
+    first = True
+    for v in out:
+        v._keep = verdicts   # the elements are views of the array
+        if not v.ok and first:
+            v.message = dll.nlx_last_error(ctx.handle).decode()
+            first = False
+    return out
+
+
 def proof_layout(stark):
     """Where everything lies in a proof of `stark` (a Stark, or anything with a `.desc`), from the descriptor alone: a dict of
     (byte offset, byte length) pairs - "caps" (and "cap"[o] per commitment: the trace batches, then the quotient), "openings"
@@ -729,43 +793,15 @@ def proof_layout(stark):
     nq = d.num_challenges * d.quotient_degree_factor
     oracle_cols.append(nq)
     n_rv = sum(d.round_values[r] for r in range(d.n_rounds))
-    log_l = d.degree_bits + d.rate_bits
-    layers = fri_num_layers(d.degree_bits, d.rate_bits, d.cap_height, d.fri_arity_bits, d.fri_final_poly_bits)
-    arity = 1 << d.fri_arity_bits
-    capb = 32 << d.cap_height
-    out = {"oracle_cols": oracle_cols, "n_layers": layers, "arity": arity}
-    at = 0
-
-    def take(n):
-        nonlocal at
-        sp = _Span((at, n))
-        at += n
-        return sp
-
-    out["cap"] = [take(capb) for _ in oracle_cols]
-    out["caps"] = _Span((0, at))
+    out = {"oracle_cols": oracle_cols}
+    take = _Taker()
+    out["cap"] = [take(32 << d.cap_height) for _ in oracle_cols]
+    out["caps"] = _Span((0, take.at))
     out["local"], out["next"], out["quotient"] = take(16 * d.n_cols), take(16 * d.n_cols), take(16 * nq)
-    out["openings"] = _Span((out["local"][0], at - out["local"][0]))
-    out["fri_cap"] = [take(capb) for _ in range(layers)]
-    out["fri_caps"] = _Span((out["openings"][0] + out["openings"][1], capb * layers))
-    out["query"] = []
-    for _ in range(d.fri_num_queries):
-        q = {"row": [], "path_len": [], "path": [], "layer": []}
-        for w in oracle_cols:
-            q["row"].append(take(8 * w))
-            q["path_len"].append(take(1))
-            q["path"].append(take(32 * (log_l - d.cap_height)))
-        lg = log_l
-        for _k in range(layers):
-            lg -= d.fri_arity_bits
-            q["layer"].append({"evals": take(16 * arity), "path_len": take(1), "path": take(32 * max(lg - d.cap_height, 0))})
-        out["query"].append(q)
-    out["final_poly"] = take(16 << (d.degree_bits - layers * d.fri_arity_bits))
-    out["pow_witness"] = take(8)
-    out["num_public_inputs"] = take(8)
-    out["public_inputs"] = take(8 * d.num_public_inputs)
+    out["openings"] = _Span((out["local"][0], take.at - out["local"][0]))
+    _layout_queries_and_tail(out, take, d, oracle_cols)
     out["round_values"] = take(8 * n_rv)
-    out["total"] = at
+    out["total"] = take.at
     return out
 
 
@@ -905,30 +941,7 @@ class StarkProver:
     def verify_many(self, proofs, public_inputs=None):
         """nlx_stark_verify_batch: a list of proofs of this STARK in one pass over the GPU; a Verdict per proof.
         public_inputs: None, or one sequence of values per proof."""
-        proofs = [bytes(p) for p in proofs]
-        n = len(proofs)
-        if n == 0:
-            return []
-        n_pis = self.stark.air.num_public_inputs
-        pis = None
-        if public_inputs is not None:
-            pis = np.ascontiguousarray([[int(v) for v in row] for row in public_inputs], dtype=np.uint64).reshape(n, -1)
-            if pis.shape != (n, n_pis):
-                raise ValueError("expected %d public inputs per proof" % n_pis)
-        keep = [ctypes.create_string_buffer(p, max(len(p), 1)) for p in proofs]
-        ptrs = (ctypes.c_void_p * n)(*[ctypes.addressof(b) for b in keep])
-        lens = (ctypes.c_size_t * n)(*[len(p) for p in proofs])
-        verdicts = (Verdict * n)()
-        self.ctx.check(dll.nlx_stark_verify_batch(self.handle, ptrs, lens, n, pis.ctypes.data if pis is not None and pis.size else None,
-                                                  verdicts))
-        out = list(verdicts)
-        first = True
-        for v in out:
-            v._keep = verdicts   # the elements are views of the array
-            if not v.ok and first:
-                v.message = dll.nlx_last_error(self.ctx.handle).decode()
-                first = False
-        return out
+        return verify_many(self.ctx, dll.nlx_stark_verify_batch, self.handle, self.stark.air.num_public_inputs, proofs, public_inputs)
 
     def prove_into(self, trace, public_inputs_ptr):
         ln = ctypes.c_size_t()

@@ -82,7 +82,7 @@ def word_at(proof, off, plb):
 
 
 def shape_args(syn, lay):
-    """the descriptor's numbers as tests/tools/plonk_layout_check.cpp takes them"""
+    """the descriptor's numbers as tests/tools/layout_check.cpp takes them in its plonk mode"""
     d = syn.desc()
     nc = d.num_challenges
     n_consts = lay["constants"][1] // 16

@@ -133,6 +133,40 @@ def test_layer_evaluations(nlx, orc, tamper_target):
             assert (v.query, v.layer, v.x_index) == (q, 0, x_index)
 
 
+def _plus_one(proof, off):
+    """the word at `off` replaced by itself + 1 mod p"""
+    word = (int.from_bytes(proof[off:off + 8], "little") + 1) % P
+    return proof[:off] + word.to_bytes(8, "little") + proof[off + 8:]
+
+
+@pytest.mark.parametrize("name", ["wide16-batch12", "fib7-nondefault"])
+def test_opened_word_plus_one(nlx, ctx, orc, name):
+    """An opened trace word of query 0 plus 1 mod p, in the first trace commitment and in the last (two runs of columns that enter
+    both FRI batches for wide16-batch12, one for fib7-nondefault): the commitment's path fails, before anything of FRI is judged.
+    Then a layer's evaluation at the query's own position, evals[x mod arity]: the fold check of that layer.  Reason, query, tree
+    and layer are the oracle verifier's."""
+    c, pr = case(nlx, orc, name), prover(nlx, ctx, orc, name)
+    proof = c.oracle_proof(orc)
+    lay = nlx.stark.proof_layout(c.st)
+    d = c.st.desc
+    Q = lay["query"][0]
+    n_trace = len(lay["oracle_cols"]) - 1
+    assert n_trace == (2 if name == "wide16-batch12" else 1) and lay["n_layers"] >= 1
+    x_index = None
+    for o in sorted({0, n_trace - 1}):
+        bad = _plus_one(proof, Q["row"][o][0] + 8 * (lay["oracle_cols"][o] // 2))
+        rc, v = orc.stark_verify(d, bad), pr.verify(bad)
+        assert rc == -5 and v.reason == REASON_OF_ORACLE[rc] == 5, (o, rc, str(v))
+        assert (v.query, v.tree, v.layer) == (0, o, 0), (o, str(v))
+        x_index = v.x_index
+    for k in range(lay["n_layers"]):
+        within = (x_index >> (k * d.fri_arity_bits)) % lay["arity"]
+        bad = _plus_one(proof, Q["layer"][k]["evals"][0] + 16 * within)
+        rc, v = orc.stark_verify(d, bad), pr.verify(bad)
+        assert rc == -7 and v.reason == REASON_OF_ORACLE[rc] == 6, (k, rc, str(v))
+        assert (v.query, v.layer, v.x_index) == (0, k, x_index), (k, str(v))
+
+
 def test_public_inputs_argument(nlx, orc, tamper_target):
     c, pr, proof, lay = tamper_target
     assert pr.verify(proof, c.pis).ok

@@ -83,7 +83,7 @@ def _shape_args(st, lay):
 
 @pytest.fixture(scope="module")
 def layout_check(tmp_path_factory):
-    """tests/tools/stark_layout_check.cpp built with -fsanitize=address,undefined; skipped where a trivial program does not link
+    """tests/tools/layout_check.cpp built with -fsanitize=address,undefined; skipped where a trivial program does not link
     that way"""
     tmp = tmp_path_factory.mktemp("layout_check")
     trivial = tmp / "trivial.cpp"
@@ -96,8 +96,8 @@ def layout_check(tmp_path_factory):
         ok = False
     if not ok:
         pytest.skip("no g++ with AddressSanitizer here")
-    exe = tmp / "stark_layout_check"
-    r = subprocess.run(san + [os.path.join(ROOT, "tests", "tools", "stark_layout_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    exe = tmp / "layout_check"
+    r = subprocess.run(san + [os.path.join(ROOT, "tests", "tools", "layout_check.cpp"), "-o", str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     return str(exe)
 
@@ -114,7 +114,7 @@ def test_layout_parser_under_sanitizers(nlx, orc, layout_check, tmp_path, name):
     path = tmp_path / "proof.bin"
     path.write_bytes(proof)
     seed, n_mut = 20240 + len(name), 1000
-    r = subprocess.run([layout_check, str(path), str(seed), str(n_mut)] + _shape_args(c.st, lay), capture_output=True, text=True)
+    r = subprocess.run([layout_check, "stark", str(path), str(seed), str(n_mut)] + _shape_args(c.st, lay), capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", r.stderr[-2000:]
     lines = r.stdout.split("\n")
     assert lines[0] == "total %d" % len(proof) and lines[1] == "file 0"

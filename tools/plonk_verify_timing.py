@@ -1,7 +1,7 @@
 """Time of the plonky2 verifier for 1, 16 and 64 proofs of one circuit in one call:
   python3 tools/plonk_verify_timing.py [--reps 5] [--warmup 2] [--log-n 12,16,18] [--timeout 600]
 The nearx gate mix (bench.py GATE_MIXES["nearx"], 64 public inputs) at 2^12, 2^16 and 2^18 rows.  Per shape and batch size:
-  * device_ms: the three launches' device time (HIP events around k_plonk_paths, k_plonk_fri and k_plonk_constraints), summed per
+  * device_ms: the three launches' device time (HIP events around k_fri_paths, k_fri_queries and k_plonk_constraints), summed per
     call, median of --reps calls after --warmup; paths_ms / fri_ms / constraints_ms are its parts;
   * wall_ms: the whole call, host side included (parsing, the transcript, the copies), median likewise;
   * oracle_ms: for scale only, the oracle's one-thread host verifier (test infrastructure) on the same proof.

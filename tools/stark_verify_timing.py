@@ -2,7 +2,7 @@
   python3 tools/stark_verify_timing.py [--reps 5] [--warmup 2] [--only NAME]
 wide_air(64) at 2^12 rows and the three STARKs of a Sync step at bench.py's shapes (the step main_1 -> main_2 of
 tests/golden/near, tagged), each with StarkConfig(batch_cols=0) and StarkConfig(batch_cols=512).  Per STARK and batch size:
-  * device_ms: the three launches' device time (HIP events around k_verify_paths, k_verify_fri and the k_verify_constraints
+  * device_ms: the three launches' device time (HIP events around k_fri_paths, k_fri_queries and the k_verify_constraints
     launch groups), summed per call, median of --reps calls after --warmup; paths_ms / fri_ms / constraints_ms are its parts;
   * wall_ms: the whole call, host side included (parsing, the transcript, the copies), median likewise;
   * oracle_ms: for scale only, the oracle's one-thread host verifier (test infrastructure) on the same proof.
