@@ -461,6 +461,65 @@ int32_t nlx_bn254_fr_eval_many(nlx_ctx* ctx, uint32_t n_polys, const uint64_t* c
  * big-endian, mod r.  Host only, needs no context; dst_len <= 255. */
 int32_t nlx_bn254_hash_to_field(const uint8_t* msg, size_t len, const uint8_t* dst, size_t dst_len, uint64_t out[4]);
 
+/* ---- f.4: the optimal ate pairing on BN254 and the Groth16 verifier that stands on it (csrc/bn254_pairing.hpp / .hip; DESIGN.md
+ * section 30; the big-integer model is tools/bn254_pairing_model.py).
+ * The n reduced pairings e(g1[i], g2[i]).  g1: n x 8 words (G1Affine), g2: n x 16 words (G2Affine), Montgomery as for the MSM, (0, 0)
+ * = the point at infinity (the pairing is then 1, as in gnark-crypto); host or device.  gt_out: n x 48 words, host or device:
+ * twelve Fq elements in gnark-crypto's E12 order (C0.B0.A0, C0.B0.A1, C0.B1.A0, ... C1.B2.A1), four words each - Montgomery with
+ * flags = NLX_BN254_MONTGOMERY, canonical integers with flags = 0.  Every coordinate must be below q, every point on its curve and
+ * every G2 point in the subgroup of order r: otherwise NLX_E_RANGE, the message naming the first offending pair, and nothing is
+ * written.  n <= 2^20.  Kernel-timing names "bn254_pairing_points", "bn254_pairing_miller", "bn254_pairing_final_exp". */
+int32_t nlx_bn254_pairing(nlx_ctx* ctx, const uint64_t* g1, const uint64_t* g2, size_t n, uint32_t flags, uint64_t* gt_out);
+/* n_checks product checks: ok_out[c] = 1 if prod_i e(P_i, Q_i) = 1 over check c's n_pairs[c] pairs, else 0.  g1 / g2 hold the
+ * pairs of all checks back to back (host or device); n_pairs and ok_out are host arrays.  One Miller launch over all pairs and one
+ * final exponentiation per check, whatever the number of pairs; a check of no pairs, or of pairs at infinity, gives 1.  The
+ * points are checked as for nlx_bn254_pairing.  flags must be 0; at most 2^20 pairs in all. */
+int32_t nlx_bn254_pairing_check(nlx_ctx* ctx, const uint64_t* g1, const uint64_t* g2, const uint32_t* n_pairs, size_t n_checks, uint32_t flags,
+                                uint8_t* ok_out);
+/* gnark's groth16 VerifyingKey resident on the device.  All points are gnark-crypto's words (Montgomery), all arrays host.
+ *   n_public        the public wires, the constant wire ONE included (>= 1)
+ *   n_commitments   k <= NLX_BN254_GROTH16_MAX_COMMITMENTS Bsb22 / Pedersen commitments
+ *   ic, n_ic        G1.K: n_public points for the public wires, then one per commitment wire; n_ic = n_public + k
+ *   n_hashed, hashed   PublicAndCommitmentCommitted: k counts, then the sets concatenated - ids into ic's index space (an id
+ *                   n_public + i names commitment i's wire and must have i < the commitment that hashes it)
+ *   pedersen_g, pedersen_g_root_sigma_neg   the Pedersen verifying key, e(C, GRootSigmaNeg) e(Pok, G) = 1 ([1]_2 and [-1 / sigma]_2 in gnark's setup); read only for k > 0
+ * Creation checks every point as nlx_bn254_pairing does, computes e(alpha, beta) once on the device (gnark's Precompute) and keeps
+ * it resident next to -gamma, -delta and ic.  NLX_E_RANGE: a point that fails its checks, n_public = 0, k out of range, n_ic that
+ * disagrees, an id out of range.  The key belongs to its context and must be destroyed before it. */
+typedef struct nlx_bn254_groth16_vk nlx_bn254_groth16_vk;
+typedef struct {
+    const uint64_t *g1_alpha, *g2_beta, *g2_gamma, *g2_delta;
+    const uint64_t* ic; uint64_t n_ic;
+    uint32_t n_public, n_commitments;
+    const uint32_t* n_hashed;
+    const uint32_t* hashed;
+    const uint64_t *pedersen_g, *pedersen_g_root_sigma_neg;
+} nlx_bn254_groth16_vk_desc;
+int32_t nlx_bn254_groth16_vk_create(nlx_ctx* ctx, const nlx_bn254_groth16_vk_desc* desc, nlx_bn254_groth16_vk** out);
+void nlx_bn254_groth16_vk_destroy(nlx_bn254_groth16_vk* vk);
+/* gnark's groth16.Verify on the bytes of Proof.WriteTo (164 + 32 k; what bn254_groth16.proof_bytes writes).  public_inputs:
+ * (n_public - 1) x 4 words per proof (wires 1 .. n_public - 1, Montgomery, host), the proofs' back to back in the batch call;
+ * proofs / lens: host.  The return value says whether the check RAN (conventions of nlx_verify): NLX_OK with the answer in the
+ * verdict (zero-filled first), and on a rejection nlx_last_error holds one line naming the first rejected proof; NLX_E_INVAL for
+ * NULL arguments, NLX_E_RANGE for a public input that is not below r.  A proof gets the first reason that applies, in gnark's
+ * order:
+ *   NLX_BN254_VERIFY_MALFORMED  a wrong length or commitment count, a bad flag byte, a coordinate >= q, an x with no y on the
+ *                               curve, Bs outside the subgroup; index = 0 Ar, 1 Bs, 2 Krs, 3 + j C_j, 3 + k Pok (0 for the length)
+ *   NLX_BN254_VERIFY_PEDERSEN   e(sum_j rho^j C_j, GRootSigmaNeg) e(Pok, G) != 1
+ *   NLX_BN254_VERIFY_PAIRING    e(Ar, Bs) e(IC_0 + sum w_i IC_i + sum C_j, -gamma) e(Krs, -delta) != e(alpha, beta)
+ * Host: decoding, the square roots, the commitment challenges and rho.  Device: the subgroup test of Bs, the public sum, 3 (+ 2)
+ * Miller loops per proof and the final exponentiations - the same five launches for one proof and for a batch (kernel-timing
+ * names "bn254_groth16_ksum", "bn254_pairing_points", "bn254_pairing_miller", "bn254_pairing_final_exp"). */
+#define NLX_BN254_VERIFY_ACCEPT 0u
+#define NLX_BN254_VERIFY_MALFORMED 1u
+#define NLX_BN254_VERIFY_PEDERSEN 2u
+#define NLX_BN254_VERIFY_PAIRING 3u
+typedef struct { uint32_t accepted, reason, index; } nlx_bn254_verdict;
+int32_t nlx_bn254_groth16_verify(const nlx_bn254_groth16_vk* vk, const uint8_t* proof, size_t len, const uint64_t* public_inputs,
+                                 nlx_bn254_verdict* verdict);
+int32_t nlx_bn254_groth16_verify_batch(const nlx_bn254_groth16_vk* vk, const uint8_t* const* proofs, const size_t* lens, size_t n_proofs,
+                                       const uint64_t* public_inputs, nlx_bn254_verdict* verdicts);
+
 /* ---- a3: plonky2::fri::oracle::PolynomialBatch::{from_values, from_coeffs} ----
  * values / coeffs: n_cols x 2^log_n column-major, natural order.  The coset shift is the
  * field's multiplicative generator (plonky2 F::coset_shift()).  blinding / salting is not

@@ -503,3 +503,63 @@ def poseidon_bn128_hash_rows(ctx, rows, as_ints=False):
     out = np.zeros((r.shape[0], 4), dtype=np.uint64)
     ctx.check(dll.nlx_poseidon_bn128_hash_rows(ctx.handle, ptr(r), r.shape[0], r.shape[1], ptr(out)))
     return bn254_unpack(out[None])[0] if as_ints else out
+
+
+# ---- row f.4: the optimal ate pairing (csrc/bn254_pairing.hip, nlx_bn254_pairing / nlx_bn254_pairing_check) ----
+def _point_rows(a, width):
+    if hasattr(a, "data_ptr"):
+        if a.dim() != 2 or a.shape[1] != width or not a.is_contiguous() or a.element_size() != 8:
+            raise ValueError("expected a contiguous (n, %d) tensor of 64-bit words" % width)
+        return a, a.data_ptr(), a.shape[0]
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError("expected shape (n, %d)" % width)
+    return a, a.ctypes.data, a.shape[0]
+
+
+def bn254_pairing(ctx, g1, g2, montgomery=True):
+    """The reduced optimal ate pairings e(g1[i], g2[i]).  g1: (n, 8) words (bn254_g1_pack), g2: (n, 16) words (bn254_g2_pack),
+    numpy or device tensors; a point at infinity gives 1.  Returns (n, 48) uint64: twelve Fq elements per pairing in
+    gnark-crypto's E12 order, Montgomery words (or canonical integers with montgomery=False) - bn254_gt_unpack reads them.
+    A coordinate >= q, a point off its curve or a G2 point outside the subgroup of order r raises NlxError (NLX_E_RANGE)."""
+    k1, p1, n = _point_rows(g1, 8)
+    k2, p2, n2 = _point_rows(g2, 16)
+    if n != n2:
+        raise ValueError("g1 and g2 differ in length")
+    out = np.zeros((n, 48), dtype=np.uint64)
+    ctx.check(dll.nlx_bn254_pairing(ctx.handle, p1 if n else None, p2 if n else None, n, 1 if montgomery else 0, out.ctypes.data if n else None))
+    return out
+
+
+def bn254_pairing_check(ctx, g1, g2, n_pairs):
+    """prod_i e(P_i, Q_i) == 1 for each check: g1 / g2 hold the pairs of all checks back to back, n_pairs[c] of them belong to
+    check c.  One Miller launch and one final exponentiation launch whatever the counts.  Returns a list of bools."""
+    counts = np.ascontiguousarray(n_pairs, dtype=np.uint32).reshape(-1)
+    k1, p1, n = _point_rows(g1, 8)
+    k2, p2, n2 = _point_rows(g2, 16)
+    if n != n2 or n != int(counts.sum()):
+        raise ValueError("g1 and g2 hold sum(n_pairs) points each")
+    ok = np.zeros(max(len(counts), 1), dtype=np.uint8)
+    ctx.check(dll.nlx_bn254_pairing_check(ctx.handle, p1 if n else None, p2 if n else None, counts.ctypes.data, len(counts), 0, ok.ctypes.data))
+    return [bool(v) for v in ok[:len(counts)]]
+
+
+def bn254_gt_unpack(words, montgomery=True):
+    """(48,) or (n, 48) words of nlx_bn254_pairing -> per element the tuple of twelve integers that tools/bn254_pairing_model.py
+    computes with: the coefficients of w^0 .. w^11 in Fq[w] / (w^12 - 18 w^6 + 82) (w^6 = 9 + u).  E12's C_c.B_b = a0 + a1 u is the
+    coefficient of w^(2 b + c): a0 - 9 a1 goes to w^(2 b + c), a1 to w^(2 b + c + 6)."""
+    a = np.asarray(words, dtype=np.uint64)
+    single = a.ndim == 1
+    a = a.reshape(-1, 48)
+    rinv = pow(_MONT_Q, BN254_Q - 2, BN254_Q) if montgomery else 1
+    out = []
+    for row in a:
+        v = [sum(int(row[4 * i + k]) << (64 * k) for k in range(4)) * rinv % BN254_Q for i in range(12)]
+        coeffs, i = [0] * 12, 0
+        for c in range(2):
+            for b in range(3):
+                k = 2 * b + c
+                coeffs[k], coeffs[k + 6] = (v[i] - 9 * v[i + 1]) % BN254_Q, v[i + 1]
+                i += 2
+        out.append(tuple(coeffs))
+    return out[0] if single else out

@@ -6,6 +6,8 @@ gnark-produced bytes unpinned: DESIGN.md section 19).
   r1cs_eval(pk, w)       nlx_bn254_r1cs_eval: A w, B w, C w
   prove(pk, w, r, s)     nlx_bn254_groth16_prove: the proof's three points (G1Affine / G2Affine / G1Affine words)
   proof_bytes(...)       gnark's Proof.WriteTo, 164 + 32 k bytes; g1_compress / g2_compress: gnark-crypto's Bytes()
+  VerifyingKey(ctx, ...) nlx_bn254_groth16_vk_create: gnark's VerifyingKey resident, e(alpha, beta) precomputed on the device;
+                         .verify(proof_bytes, public) / .verify_many(proofs, publics) -> Verdict
 Keys with k Bsb22 / Pedersen commitments (rules: tools/groth16_commit_model.py):
   ProvingKey(ctx, ..., commitments=[...])   nlx_bn254_groth16_key_create_committed: the Pedersen bases resident next to the key
   commit(pk, j, w)                          nlx_bn254_groth16_commit: C_j, the call a solver's hint makes
@@ -31,7 +33,7 @@ KEY_INFO_WORDS = 8
 MAX_COMMITMENTS = 8
 COMMITMENT_DST = b"bsb22-commitment"     # the hint's hash (gnark constraint/commitment.go)
 FOLD_DST = b"G16-BSB22"                  # pedersen.BatchProve's folding challenge (gnark backend/groth16/bn254/prove.go)
-NLX_E_INVAL = -1
+NLX_E_INVAL, NLX_E_RANGE = -1, -4
 
 
 class _KeyDesc(ctypes.Structure):
@@ -337,3 +339,125 @@ def prove_committed(pk, witness, r=None, s=None, abc=None):
             raise NlxError(NLX_E_INVAL, "commitment %d: wire %d does not hold the challenge of the witness's own commitment"
                            % (j, pk.commitments[j]["wire"]))
     return ar, bs, krs, [cs[j] for j in range(k)], pok
+
+
+# ---- the verifier (csrc/bn254_pairing.hip; the model with real pairings is tools/bn254_pairing_model.py) ----
+VERIFY_ACCEPT, VERIFY_MALFORMED, VERIFY_PEDERSEN, VERIFY_PAIRING = 0, 1, 2, 3
+_REASONS = {VERIFY_ACCEPT: "accepted", VERIFY_MALFORMED: "malformed", VERIFY_PEDERSEN: "the Pedersen proof of knowledge fails",
+            VERIFY_PAIRING: "the pairing equation fails"}
+
+
+class _VkDesc(ctypes.Structure):
+    """nlx_bn254_groth16_vk_desc (include/nlx.h)"""
+    _fields_ = [("g1_alpha", ctypes.c_void_p), ("g2_beta", ctypes.c_void_p), ("g2_gamma", ctypes.c_void_p), ("g2_delta", ctypes.c_void_p),
+                ("ic", ctypes.c_void_p), ("n_ic", ctypes.c_uint64), ("n_public", ctypes.c_uint32), ("n_commitments", ctypes.c_uint32),
+                ("n_hashed", ctypes.c_void_p), ("hashed", ctypes.c_void_p), ("pedersen_g", ctypes.c_void_p),
+                ("pedersen_g_root_sigma_neg", ctypes.c_void_p)]
+
+
+class Verdict(ctypes.Structure):
+    """nlx_bn254_verdict: accepted, and for a rejected proof the first reason in gnark's order and the point it names"""
+    _fields_ = [("accepted", ctypes.c_uint32), ("reason", ctypes.c_uint32), ("index", ctypes.c_uint32)]
+
+    k = None      # the key's commitment count, set by VerifyingKey.verify_many: what tells C_j from Pok
+
+    def point_name(self):
+        i, k = int(self.index), self.k
+        if i < 3:
+            return ("Ar", "Bs", "Krs")[i]
+        if k is None:
+            return "point %d (C_%d, or Pok after %d commitments)" % (i, i - 3, i - 3)
+        return "Pok" if i == 3 + k else "C_%d" % (i - 3)
+
+    def __bool__(self):
+        return bool(self.accepted)
+
+    def __str__(self):
+        if self.accepted:
+            return "accepted"
+        text = "rejected: " + _REASONS.get(int(self.reason), "reason %d" % self.reason)
+        return text + (" at " + self.point_name() if self.reason == VERIFY_MALFORMED else "")
+
+    def raise_if_rejected(self):
+        if not self.accepted:
+            raise NlxError(NLX_E_INVAL, "Groth16 proof " + str(self))
+        return self
+
+
+class VerifyingKey:
+    """nlx_bn254_groth16_vk: gnark's groth16.VerifyingKey resident on the device (owns the handle; close() or the context's
+    close() releases it).  g1_alpha: 8 words; g2_beta, g2_gamma, g2_delta: 16 words; ic: (n_public + k, 8) words - G1.K over the
+    public wires (the constant wire first), then one point per commitment wire.  commitments: one dict per Bsb22 commitment with
+    "public" = PublicAndCommitmentCommitted as positions in ic (a public wire's id, or n_public + i for commitment i's wire);
+    pedersen: the Pedersen verifying key's (G, GRootSigmaNeg), 16 words each - needed when there are commitments."""
+
+    def __init__(self, ctx, n_public, g1_alpha, g2_beta, g2_gamma, g2_delta, ic, commitments=(), pedersen=None, n_ic=None):
+        self.ctx, self.handle = ctx, None
+        self.n_public, self.k = int(n_public), len(commitments)
+        keep = {}
+        d = _VkDesc()
+        for name, arr, count in (("g1_alpha", g1_alpha, 8), ("g2_beta", g2_beta, 16), ("g2_gamma", g2_gamma, 16), ("g2_delta", g2_delta, 16)):
+            keep[name] = np.ascontiguousarray(arr, dtype=np.uint64).reshape(count)
+            setattr(d, name, keep[name].ctypes.data)
+        keep["ic"] = np.ascontiguousarray(ic, dtype=np.uint64).reshape(-1, 8)
+        d.ic, d.n_ic = keep["ic"].ctypes.data, len(keep["ic"]) if n_ic is None else int(n_ic)
+        d.n_public, d.n_commitments = self.n_public, self.k
+        if self.k:
+            if pedersen is None:
+                raise ValueError("a key with commitments needs the Pedersen verifying key")
+            keep["n_hashed"] = np.array([len(c["public"]) for c in commitments], dtype=np.uint32)
+            keep["hashed"] = np.array([i for c in commitments for i in c["public"]] + [0], dtype=np.uint32)
+            keep["ped"] = [np.ascontiguousarray(p, dtype=np.uint64).reshape(16) for p in pedersen]
+            d.n_hashed, d.hashed = keep["n_hashed"].ctypes.data, keep["hashed"].ctypes.data
+            d.pedersen_g, d.pedersen_g_root_sigma_neg = keep["ped"][0].ctypes.data, keep["ped"][1].ctypes.data
+        h = ctypes.c_void_p()
+        ctx.check(dll.nlx_bn254_groth16_vk_create(ctx.handle, ctypes.byref(d), ctypes.byref(h)))
+        self.handle = h
+        ctx._adopt(self)
+
+    def verify_many(self, proofs, publics):
+        """One Verdict per proof.  proofs: the bytes of Proof.WriteTo (proof_bytes); publics: per proof the n_public - 1 public
+        inputs (wires 1 .. n_public - 1) as integers.  The whole batch is the same five launches as one proof.  An integer not
+        below r raises NlxError (NLX_E_RANGE)."""
+        if not self.handle:
+            raise NlxError(NLX_E_INVAL, "the verifying key is closed")
+        n = len(proofs)
+        if len(publics) != n or any(len(p) != self.n_public - 1 for p in publics):
+            raise ValueError("one list of n_public - 1 public inputs per proof")
+        blobs = [bytes(p) for p in proofs]
+        ptrs = (ctypes.c_char_p * max(n, 1))(*blobs)
+        lens = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in blobs])
+        words = np.zeros((max(n * (self.n_public - 1), 1), 4), dtype=np.uint64)
+        row = 0
+        for p in publics:
+            for x in p:
+                x = int(x)
+                if not 0 <= x < (1 << 256):
+                    raise NlxError(NLX_E_RANGE, "proof %d: a public input does not fit four words" % (row // max(self.n_public - 1, 1)))
+                m = x * _MONT % R if x < R else x               # r <= x < 2^256 is no residue: its words go as they are and the library refuses them
+                for w in range(4):
+                    words[row, w] = (m >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
+                row += 1
+        verdicts = (Verdict * max(n, 1))()
+        self.ctx.check(dll.nlx_bn254_groth16_verify_batch(self.handle, ptrs, lens, n, words.ctypes.data, verdicts))
+        out = []
+        for i in range(n):
+            v = Verdict(verdicts[i].accepted, verdicts[i].reason, verdicts[i].index)
+            v.k = self.k
+            out.append(v)
+        return out
+
+    def verify(self, proof, public=()):
+        """nlx_bn254_groth16_verify: one proof's Verdict"""
+        return self.verify_many([proof], [list(public)])[0]
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            dll.nlx_bn254_groth16_vk_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

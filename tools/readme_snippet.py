@@ -34,5 +34,7 @@ one = np.array([1, 1], dtype=np.uint64)              # the circuit "w1 * w1 = w1
 r1cs = {m: (np.array([0, 1], dtype=np.uint64), np.array([1], dtype=np.uint32), np.array([0], dtype=np.uint32)) for m in "ABC"}
 r1cs["coeffs"] = G.fr_pack([1])
 key = G.ProvingKey(ctx, 1, 2, 1, 1, inf8[None][:0], inf8[None][:0], inf16[None][:0], inf8[None], inf8[None], one, one, inf8, inf8, inf8, inf16, inf16, r1cs=r1cs)
-print("groth16", len(G.proof_bytes(*G.prove(key, G.fr_pack([1, 1])))))
+groth16_proof = G.proof_bytes(*G.prove(key, G.fr_pack([1, 1])))
+print("groth16", len(groth16_proof))
+G.VerifyingKey(ctx, 1, inf8, inf16, inf16, inf16, inf8[None]).verify(groth16_proof).raise_if_rejected()   # the matching key of points at infinity: e(alpha, beta) = 1
 print("hash_to_field", hex(nlx.bn254_plonk.hash_to_field_native(b"abc")) == hex(nlx.bn254_plonk.hash_to_field(b"abc")))   # the PLONK prover's host hash (ResidentKey / prove_resident: DESIGN.md section 23)
