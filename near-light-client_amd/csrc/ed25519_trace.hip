@@ -7,6 +7,7 @@
 //   k_ed_rows  one lane per row recomputes its 16 units from that input point (results are canonical, so the
 //              recomputation is bit-identical) and writes its 1 488 cells; a wave's 64 lanes are 64 consecutive rows,
 //              so every column store is 512 contiguous bytes.
+#include "bind_round.hpp"
 #include "ctx.hpp"
 #include "ed25519_rows.hpp"
 #include "gl.hpp"
@@ -228,40 +229,9 @@ extern "C" int32_t nlx_ed25519_bind_round(nlx_ctx* ctx, const uint64_t* trace, u
     if (!ctx) return NLX_E_INVAL;
     if (!trace || !gamma || !acc_out || !total_out) return ctx->fail(NLX_E_INVAL, "NULL argument");
     if (log_slots > 16) return ctx->fail(NLX_E_RANGE, "log_slots must be <= 16");
-    (void)hipSetDevice(ctx->device);
-    const uint32_t n_slots = 1u << log_slots;
-    const size_t n = (size_t)n_slots * ed::ROWS;
-    Staged tr(ctx, trace, (size_t)ed::N_COLS0 * n * 8, true, false);
-    if (tr.status) return tr.status;
-    Staged so(ctx, acc_out, 2 * n * 8, false, true);
-    if (so.status) return so.status;
-    std::vector<gl::Ext> fp_h(n_slots), start(n_slots);   // `start` becomes the source of a queued copy: it outlives the scratch
-    Scratch scratch(ctx);
-    gl::Ext* d_fp = scratch.alloc_as<gl::Ext>((size_t)n_slots * sizeof(gl::Ext));
-    if (!d_fp) return NLX_E_NOMEM;
-    const gl::Ext g{gamma[0] % gl::P, gamma[1] % gl::P};
-    hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_ed_bind_slot, dim3((n_slots + 63) / 64), dim3(64), 0, st, tr.as<uint64_t>(), n_slots, g, d_fp);
-    int32_t rc = fetch(ctx, fp_h.data(), d_fp, (size_t)n_slots * sizeof(gl::Ext));
-    if (!rc) {
-        // the slots' start values: acc_(s+1) = acc_s gamma^96 + fp_s (a few thousand extension multiplications, on the host)
-        const gl::Ext g_slot = gl::pow(g, 16 * ED_BOUND);
-        gl::Ext acc{0, 0};
-        for (uint32_t k = 0; k < n_slots; k++) {
-            start[k] = acc;
-            acc = gl::add(gl::mul(acc, g_slot), fp_h[k]);
-        }
-        total_out[0] = acc.a;
-        total_out[1] = acc.b;
-        hipError_t e = hipMemcpyAsync(d_fp, start.data(), (size_t)n_slots * sizeof(gl::Ext), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) rc = ctx->hip_fail(e, "hipMemcpyAsync");
-    }
-    if (!rc) {
-        hipLaunchKernelGGL(k_ed_bind_rows, dim3((n_slots + 63) / 64), dim3(64), 0, st, tr.as<uint64_t>(), n_slots, g, d_fp,
-                           so.as<uint64_t>());
-        rc = so.finish();
-    }
-    return scratch.finish(rc);
+    // a slot absorbs 16 limbs of ED_BOUND values
+    return bind_round(ctx, trace, 1u << log_slots, ed::ROWS, ed::N_COLS0, 16 * ED_BOUND, gamma, acc_out, total_out, k_ed_bind_slot,
+                      k_ed_bind_rows);
 } NLX_CATCH(ctx)
 
 

@@ -42,7 +42,7 @@ import numpy as np
 
 from . import fp25519 as fp
 from . import logup
-from .stark import STEP_TAG_LEN, Air, Stark
+from .stark import STEP_TAG_LEN, Air, Stark, StatementProver
 
 P = fp.P25519
 D = (-121665 * pow(121666, P - 2, P)) % P
@@ -774,16 +774,13 @@ class Ed25519Stark:
         self.stark = Stark(self.air, log_slots + 8, config)
 
 
-class Ed25519Prover:
+class Ed25519Prover(StatementProver):
     """Proves 2^log_slots Ed25519 verifications on one GPU: trace generation (nlx_ed25519_trace), multiplicities and
     lookup columns (nlx_logup_*), two-round STARK (nlx_stark_prove_rounds) - nothing of the trace touches the host."""
 
     def __init__(self, ctx, log_slots, config=None, max_resident_leaves=None, segment_nodes=None, step_tag=None):
-        self.ctx = ctx
-        self.step_tag = None if step_tag is None else [int(v) for v in step_tag]   # see stark.step_tag: public inputs 0..3
-        self.es = Ed25519Stark(log_slots, config, max_resident_leaves, segment_nodes, tagged=self.step_tag is not None)
-        self.stark = self.es.stark
-        self.prover = self.stark.build(ctx)
+        self.es = Ed25519Stark(log_slots, config, max_resident_leaves, segment_nodes, tagged=step_tag is not None)
+        super().__init__(ctx, self.es.stark, step_tag)   # see stark.step_tag: public inputs 0..3
         self._t0 = self._t1 = None
 
     def generate_trace(self, slots):
@@ -823,19 +820,13 @@ class Ed25519Prover:
         return self._t1, [int(total[0]), int(total[1])]
 
     def prove(self, slots):
-        t0 = self.generate_trace(slots)
-        return self.prover.prove_rounds(lambda rnd, known: t0 if rnd == 0 else self.round1(known), self.step_tag or [])
+        return self._prove(self.generate_trace(slots))
 
     def check(self, slots, challenges=None):
         """A stark.TraceReport for the trace of these slots: the rounds prove() would run, checked against the AIR instead of
         proved (StarkProver.check_rounds)."""
-        t0 = self.generate_trace(slots)
-        return self.prover.check_rounds(lambda rnd, known: t0 if rnd == 0 else self.round1(known), self.step_tag or [], challenges)
-
-    def verify(self, proof, public_inputs=None):
-        """does the proof verify, and which check breaks if not (StarkProver.verify)"""
-        return self.prover.verify(proof, public_inputs)
+        return self._check(self.generate_trace(slots), challenges=challenges)
 
     def close(self):
-        self.prover.close()
+        super().close()
         self._t0 = self._t1 = None

@@ -968,6 +968,37 @@ class StarkProver:
             pass
 
 
+class StatementProver:
+    """What the provers of the statement AIRs (SHA-256, SHA-512, Ed25519) share: a two-round STARK whose round 0 is a trace
+    left on the device and whose round 1 is the subclass's round1(known), with the step tag (step_tag above) behind the
+    statement's own public inputs."""
+
+    def __init__(self, ctx, stark, step_tag=None):
+        self.ctx, self.stark = ctx, stark
+        self.step_tag = None if step_tag is None else [int(v) for v in step_tag]
+        self.prover = stark.build(ctx)
+        self.last_total = None
+
+    def _round_fn(self, t0):
+        return lambda rnd, known: t0 if rnd == 0 else self.round1(known)
+
+    def _pis(self, public_inputs):
+        return [int(v) for v in public_inputs] + (self.step_tag or [])
+
+    def _prove(self, t0, public_inputs=()):
+        return self.prover.prove_rounds(self._round_fn(t0), self._pis(public_inputs))
+
+    def _check(self, t0, public_inputs=(), challenges=None):
+        return self.prover.check_rounds(self._round_fn(t0), self._pis(public_inputs), challenges)
+
+    def verify(self, proof, public_inputs=None):
+        """does the proof verify, and which check breaks if not (StarkProver.verify)"""
+        return self.prover.verify(proof, public_inputs)
+
+    def close(self):
+        self.prover.close()
+
+
 # ---------------------------------------------------------------------------------------------
 # Example AIRs (starky's own FibonacciStark, and a wide synthetic AIR shaped like a hash-round table)
 # ---------------------------------------------------------------------------------------------
