@@ -1126,6 +1126,14 @@ int32_t nlx_ed25519_trace(nlx_ctx* ctx, const uint64_t* slots, uint32_t log_slot
  * the tuples it believes were verified (near-light-client_amd/ed25519_air.py::fingerprint). */
 int32_t nlx_ed25519_bind_round(nlx_ctx* ctx, const uint64_t* trace, uint32_t log_slots, const uint64_t gamma[2],
                                uint64_t* acc_out, uint64_t total_out[2]);
+/* Self-test entry for the arithmetic mod 2^255 - 19 of the trace generator's scan (csrc/fe25519_fast.hpp and the four-lane
+ * moves of k_ed_scan4), one lane per element.  a, b: n x 10 signed limbs of 26 bits (value = sum l_i 2^(26 i)), |l_i| < 2^28, NOT
+ * reduced first.  out: n x NLX_FE25519_OPS_WORDS u32 (host or device), per element: words 0-15 the canonical value of a as
+ * 16-bit limbs; 16-31 the canonical product a b; 32-41 the product's ten carried limbs as the device holds them (two's
+ * complement); 42-57 the canonical product of the NEXT lane of the element's quad (element 4 (i / 4) + (i + 1) % 4), fetched
+ * through the quad broadcasts and the lane select of the scan; lanes past n compute element n - 1. */
+#define NLX_FE25519_OPS_WORDS 58
+int32_t nlx_fe25519_ops(nlx_ctx* ctx, const int32_t* a, const int32_t* b, size_t n, uint32_t* out);
 /* f.1: trace generation on the GPU for the SHA-256 compression AIR (column layout and constraints:
  * near-light-client_amd/sha256_air.py; callers in the reference: curta_sha256 at nearx/src/merkle.rs:49,
  * nearx/src/variables.rs:71-72).  blocks: 2^log_blocks padded 512-bit blocks as 16 big-endian-decoded words

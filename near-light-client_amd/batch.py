@@ -42,6 +42,23 @@ def ext_ops(ctx, a, b):
     return out
 
 
+FE25519_OPS_WORDS = 58
+
+
+def fe25519_ops(ctx, a, b):
+    """the Ed25519 scan's arithmetic mod 2^255 - 19 on n pairs of UNREDUCED operands (a, b: (n, 10) int32, signed 26-bit limbs,
+    |l| < 2^28), one lane each: (n, 58) uint32 = the canonical a (16 limbs of 16 bits), the canonical a b (16), the product's ten
+    carried limbs as the device holds them (two's complement), the canonical product of the next lane of the element's quad (16),
+    fetched through the scan's quad moves; a lane past n stands for element n - 1"""
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    b = np.ascontiguousarray(b, dtype=np.int32)
+    if a.ndim != 2 or a.shape[1] != 10 or a.shape != b.shape:
+        raise ValueError("a and b must both have shape (n, 10)")
+    out = np.zeros((a.shape[0], FE25519_OPS_WORDS), dtype=np.uint32)
+    ctx.check(dll.nlx_fe25519_ops(ctx.handle, a.ctypes.data, b.ctypes.data, a.shape[0], out.ctypes.data))   # 32-bit arrays: no ptr()
+    return out
+
+
 def hash_rows(ctx, rows):
     """PoseidonHash::hash_or_noop of every row of a row-major (n_rows, row_len) matrix."""
     r = np.ascontiguousarray(rows, dtype=np.uint64)

@@ -1,8 +1,8 @@
 // Trace generation for the Ed25519 verification AIR (near-light-client_amd/ed25519_air.py; SURVEY.md §8a row a12 /
 // §8f.1: curta_eddsa_verify_sigs_conditional, nearx/src/builder.rs:152).  Two kernels over the row code of
 // ed25519_rows.hpp:
-//   k_ed_scan  one lane per slot walks its 256 rows (the point after each row depends on the one before) and
-//              records the input point of every row - the only sequential part, on values only (fe25519_fast.hpp:
+//   k_ed_scan4 four lanes per slot walk its 256 rows (the point after each row depends on the one before) and
+//              record the input point of every row - the only sequential part, on values only (fe25519_fast.hpp:
 //              26-bit limbs, no witness cells; canonical results, so identical to what the row emitter recomputes);
 //   k_ed_rows  one lane per row recomputes its 16 units from that input point (results are canonical, so the
 //              recomputation is bit-identical) and writes its 1 488 cells; a wave's 64 lanes are 64 consecutive rows,
@@ -18,45 +18,16 @@ namespace nlx {
 
 static_assert(ed::N_COLS0 == NLX_ED25519_COLS0, "column map");
 
-__global__ __launch_bounds__(64) void k_ed_scan(const uint64_t* __restrict__ words, uint32_t n_slots, ed::Slot* __restrict__ slots,
-                                                ed::Point* __restrict__ in, ed::Point* __restrict__ fin) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_slots) return;
-    ed::Slot s;
-    ed::slot_from_words(words + (size_t)k * ed::SLOT_WORDS, s);
-    slots[k] = s;
-    ed::FastSlot fs;
-    ed::fast_slot(s, fs);
-    ed::FastPoint fq;
-    {
-        uint32_t zero[16], one[16];
-        for (int i = 0; i < 16; i++) { zero[i] = 0; one[i] = i == 0; }
-        fq.x = fe::from_limbs16(zero);
-        fq.y = fe::from_limbs16(one);
-        fq.z = fe::from_limbs16(one);
-    }
-    ed::Point q;
-#pragma unroll 1
-    for (int r = 0; r < ed::ROWS; r++) {
-        ed::fast_store(fq, q);
-        in[(size_t)k * ed::ROWS + r] = q;
-        const int bit = ed::ROWS - 1 - r;
-        ed::fast_row(fq, ((s.sw[bit >> 4] >> (bit & 15)) & 1) != 0, ((s.hw[bit >> 4] >> (bit & 15)) & 1) != 0, fs);
-    }
-    ed::fast_store(fq, q);
-    fin[k] = q;
-}
-
 // ---- the scan on FOUR lanes per slot ------------------------------------------------------------------------------------
 // A row of the double-and-add chain is fifteen field products in four dependent levels (4 squares; 4 products of the
-// doubling; 4 products with the addend; 3 products of the addition): k_ed_scan walks them one after the other on one lane per
-// slot - 128 lanes for the Sync step's 128 slots, 3.7 ms of latency.  Here a quad of lanes owns a slot: lane j computes
+// doubling; 4 products with the addend; 3 products of the addition).  Walked one after the other on one lane per slot (ed::fast_row,
+// the form the host runs) that is 128 lanes for the Sync step's 128 slots and 3.7 ms of latency.  Here a quad of lanes owns a slot: lane j computes
 // product j of every level (operands picked by lane-index selects, no divergent control flow), the four results travel by
 // DPP quad broadcasts (ten 26-bit limbs each), and lanes 0..2 canonicalise and store one coordinate of the row's input point
-// each.  The state is replicated in the quad; values are the same residues as k_ed_scan's (canonical after freeze), so the
+// each.  The state is replicated in the quad; values are the same residues as ed::fast_row's (canonical after freeze), so the
 // trace is bit-identical.
 namespace quad {
-struct F10 { int32_t l[10]; };   // fe::Fe's limbs after a carry fit 32 bits (|l| <= 2^25 + small)
+struct F10 { int32_t l[10]; };   // fe::Fe's limbs after a carry fit 32 bits (|l_0| <= 2^25 + 608, |l_i| <= 2^25: fe::carry10)
 
 template <int SRC>
 __device__ __forceinline__ F10 bcast(const F10& v) {   // lane SRC of the quad's value, in every lane of the quad
@@ -83,9 +54,44 @@ __device__ __forceinline__ fe::Fe wide(const F10& a) { fe::Fe r;
 __device__ __forceinline__ F10 narrow(const fe::Fe& a) { F10 r;
 #pragma unroll
     for (int i = 0; i < 10; i++) r.l[i] = (int32_t)a.l[i]; return r; }
-// operands: sums of at most four carried values (|l| < 2^28, fe::mul's bound); result carried
+// operands: sums of at most four carried values (|l| <= 2^27 + 2432 < 2^28, fe::mul's bound); result carried
 __device__ __forceinline__ F10 mul(const F10& a, const F10& b) { return narrow(fe::mul(wide(a), wide(b))); }
 }  // namespace quad
+
+// ---- the scan's arithmetic at given values (self-test entry nlx_fe25519_ops): one lane per element, launched in whole quads - the
+// DPP moves need all four lanes, so no lane returns before them; lanes past n compute element n - 1 and store nothing, as
+// k_ed_scan4's spare quads do.  Per element: freeze(a) | freeze(a b) | a b's ten carried limbs | freeze of the NEXT lane's product,
+// fetched the way the scan moves values (quad::mul, the four broadcasts, quad::pick). ----
+constexpr uint32_t FE_OPS_WORDS = NLX_FE25519_OPS_WORDS;
+static_assert(FE_OPS_WORDS == 16 + 16 + 10 + 16, "output layout");
+__global__ __launch_bounds__(64) void k_fe25519_ops(const int32_t* __restrict__ a, const int32_t* __restrict__ b, size_t n,
+                                                    uint32_t* __restrict__ out) {
+    using quad::F10;
+    const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const bool live = t < n;
+    const size_t e = live ? t : n - 1;
+    const uint32_t j = threadIdx.x & 3;
+    F10 x, y;
+#pragma unroll
+    for (int i = 0; i < 10; i++) { x.l[i] = a[e * 10 + i]; y.l[i] = b[e * 10 + i]; }
+    const fe::Fe prod = fe::mul(quad::wide(x), quad::wide(y));
+    const F10 m = quad::mul(x, y);
+    const F10 next = quad::pick((j + 1) & 3, quad::bcast<0>(m), quad::bcast<1>(m), quad::bcast<2>(m), quad::bcast<3>(m));
+    if (!live) return;
+    uint32_t* o = out + e * FE_OPS_WORDS;
+    uint32_t c16[16];
+    fe::freeze(quad::wide(x), c16);
+#pragma unroll
+    for (int i = 0; i < 16; i++) o[i] = c16[i];
+    fe::freeze(prod, c16);
+#pragma unroll
+    for (int i = 0; i < 16; i++) o[16 + i] = c16[i];
+#pragma unroll
+    for (int i = 0; i < 10; i++) o[32 + i] = (uint32_t)(int32_t)prod.l[i];
+    fe::freeze(quad::wide(next), c16);
+#pragma unroll
+    for (int i = 0; i < 16; i++) o[42 + i] = c16[i];
+}
 
 constexpr uint32_t SCAN4_SLOTS_PER_BLOCK = 16;   // 64 lanes
 __global__ __launch_bounds__(64) void k_ed_scan4(const uint64_t* __restrict__ words, uint32_t n_slots, ed::Slot* __restrict__ slots,
@@ -235,6 +241,24 @@ extern "C" int32_t nlx_ed25519_bind_round(nlx_ctx* ctx, const uint64_t* trace, u
 } NLX_CATCH(ctx)
 
 
+extern "C" int32_t nlx_fe25519_ops(nlx_ctx* ctx, const int32_t* a, const int32_t* b, size_t n, uint32_t* out) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (!a || !b || !out) return ctx->fail(NLX_E_INVAL, "NULL buffer");
+    if (n == 0) return NLX_OK;
+    if (n > (size_t)1 << 24) return ctx->fail(NLX_E_RANGE, "n must be <= 2^24");
+    (void)hipSetDevice(ctx->device);
+    Staged sa(ctx, a, n * 10 * 4, true, false), sb(ctx, b, n * 10 * 4, true, false), so(ctx, out, n * FE_OPS_WORDS * 4, false, true);
+    if (sa.status) return sa.status;
+    if (sb.status) return sb.status;
+    if (so.status) return so.status;
+    hipLaunchKernelGGL(k_fe25519_ops, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, sa.as<int32_t>(), sb.as<int32_t>(), n,
+                       so.as<uint32_t>());
+    int32_t rc = so.finish();
+    if (rc) return rc;
+    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NLX_OK;
+} NLX_CATCH(ctx)
+
 extern "C" int32_t nlx_ed25519_trace(nlx_ctx* ctx, const uint64_t* slots, uint32_t log_slots, uint64_t* trace_out) NLX_TRY {
     if (!ctx) return NLX_E_INVAL;
     if (!slots || !trace_out) return ctx->fail(NLX_E_INVAL, "NULL argument");
@@ -257,8 +281,10 @@ extern "C" int32_t nlx_ed25519_trace(nlx_ctx* ctx, const uint64_t* slots, uint32
     uint32_t* d_bad = (uint32_t*)(d_fin + n_slots);
     hipError_t e0 = hipMemcpyAsync(d_bad, &bad, 4, hipMemcpyHostToDevice, ctx->stream);
     if (e0 != hipSuccess) return ctx->hip_fail(e0, "hipMemcpyAsync");
-    // four lanes per slot (k_ed_scan4); k_ed_scan, one lane per slot, is the same walk written sequentially (kept: the reference
-    // the quad version is checked against in tests/native and the form the row emitter's recomputation mirrors)
+    // four lanes per slot.  What checks k_ed_scan4 is tests/test_gpu_ed25519_aims.py: its trace against the Python reference, cell
+    // by cell, on slots aimed at the arithmetic's extremes, from one slot (fifteen spare quads) to two blocks; its arithmetic and
+    // lane moves at given values through nlx_fe25519_ops.  The same walk on one lane is ed::fast_row, which only the host runs
+    // (tests/native/ed25519_host_check.cpp, against the witness row and the reference): no device kernel launches it.
     hipLaunchKernelGGL(k_ed_scan4, dim3((n_slots + SCAN4_SLOTS_PER_BLOCK - 1) / SCAN4_SLOTS_PER_BLOCK), dim3(64), 0, ctx->stream,
                        sw.as<uint64_t>(), n_slots, d_slots, d_in, d_fin);
     hipLaunchKernelGGL(k_ed_rows, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, d_slots, d_in, d_fin, n_slots,

@@ -1,9 +1,10 @@
-// Fast arithmetic mod 2^255 - 19 for the sequential part of the Ed25519 trace generator (k_ed_scan): values only, no
+// Fast arithmetic mod 2^255 - 19 for the sequential part of the Ed25519 trace generator (k_ed_scan4): values only, no
 // witness cells.  Ten signed limbs of 26 bits (value = sum l_i 2^(26 i), 260 bits; 2^260 = 608 mod p).  A product is
 // a plain 19-column schoolbook in int64 (|column| < 10 * 2^54), carried to 26-bit limbs, the upper ten folded with
 // 608 and carried again - 100 multiply-adds against the 256 + quotient + carry chain of the witness unit.  Results
 // are only ever compared after freeze() (canonical), so they equal the witness code's canonical values bit for bit;
-// tests/native/ed25519_host_check.cpp runs both and compares.
+// tests/native/ed25519_host_check.cpp runs both and compares.  tests/native/fe25519_fast_check.cpp checks every function here on
+// the host against big integers at the edges of p and of the limb bounds; nlx_fe25519_ops does the same on the device.
 #pragma once
 #include "fp25519.hpp"
 
@@ -32,7 +33,13 @@ FP_HD inline Fe sub(const Fe& a, const Fe& b) { Fe r; FP_UNROLL for (int i = 0; 
 FP_HD inline Fe dbl(const Fe& a) { Fe r; FP_UNROLL for (int i = 0; i < 10; i++) r.l[i] = 2 * a.l[i]; return r; }
 FP_HD inline Fe neg(const Fe& a) { Fe r; FP_UNROLL for (int i = 0; i < 10; i++) r.l[i] = -a.l[i]; return r; }
 
-// carry a 10-limb value whose limbs fit int64 comfortably to |l_i| <= 2^25 + small (balanced), folding the top carry
+// Carry a 10-limb value with |l_i| < 2^41 to balanced limbs, folding the top carry (2^260 = 608):
+//     -2^25 - 608 <= l_0 <= 2^25 - 1 + 608     and     -2^25 <= l_i <= 2^25 - 1  for i >= 1.
+// A limb that has been rounded lies in [-2^25, 2^25).  Pass 1: every carry is at most 2^15 + 1 in magnitude, so limbs 1..9 are
+// rounded and limb 0 is a rounded value plus 608 c_9 with 608 |c_9| < 2^25, below 2^26 in magnitude.  Pass 2: limb 0's carry is
+// therefore -1, 0 or 1, and so is every later one (a rounded limb plus such a carry); limbs 1..9 end rounded, and limb 0, rounded,
+// receives 608 c_9 with |c_9| <= 1.  With one pass limb 0 would keep 608 c_9 of the first pass, up to 2^25.  fe::mul's operands in
+// the scan are sums of at most four such values, |l| <= 2^27 + 2432 < 2^28, and every limb fits quad::F10's 32 bits.
 FP_HD inline void carry10(int64_t* l) {
     FP_UNROLL
     for (int pass = 0; pass < 2; pass++) {
@@ -71,7 +78,7 @@ FP_HD inline Fe mul(const Fe& a, const Fe& b) {  // inputs |l_i| < 2^28
     }
     Fe r;
     FP_UNROLL
-    for (int i = 0; i < 10; i++) r.l[i] = t[i] + 608 * t[i + 10];
+    for (int i = 0; i < 10; i++) r.l[i] = t[i] + 608 * t[i + 10];   // |t_k| <= 2^25 for k < 19, |t_19| < 2^31: |r_i| < 2^41
     carry10(r.l);
     return r;
 }

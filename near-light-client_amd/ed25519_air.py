@@ -618,12 +618,13 @@ def reference_slot(ax, ay, rx, ry, s, d, active=1):
     return t, q
 
 
-def reference_trace(slots):
+def reference_trace(slots, slot_rows=None):
     """Round-0 trace of a list of slots (ax, ay, rx, ry, s, d[, active]): the Y comparison of slot k sits in row 0 of
-    slot k + 1 (cyclically)."""
+    slot k + 1 (cyclically).  slot_rows: a stand-in for reference_slot (a caller's cache); row 0 is written into the
+    arrays it returns, so it must hand out a fresh array per call."""
     parts, finals = [], []
     for sl in slots:
-        tr, q = reference_slot(*sl)
+        tr, q = (slot_rows or reference_slot)(*sl)
         parts.append(tr)
         finals.append(q)
     for k, sl in enumerate(slots):
