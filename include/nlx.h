@@ -196,6 +196,16 @@ int32_t nlx_bn254_msm_g2(nlx_ctx* ctx, const uint64_t* points, const uint64_t* s
  * points were split over several GPUs - one addition per rank. */
 int32_t nlx_bn254_g1_sum(const uint64_t* points, uint64_t n, uint64_t out[8]);
 int32_t nlx_bn254_g2_sum(const uint64_t* points, uint64_t n, uint64_t out[16]);   /* the same for G2Affine points */
+/* Segmented G1 linear combinations on the device: out[s] = sum of scalars[t] * points[t] over first[s] <= t < first[s + 1] -
+ * many short sums at once (a verifier's digests, one segment per proof and digest), one wave per segment.
+ * points: n_terms x 8 words (G1Affine, Montgomery), scalars: n_terms x 4 words, canonical integers below r - both host or
+ * device; first: HOST, n_segments + 1 ascending offsets from 0, n_terms = first[n_segments]; out: n_segments x 8 G1Affine words,
+ * host or device.  The all-zero words stand for the point at infinity on input and output; a scalar of 0 and an empty segment
+ * give it.  Points are checked as nlx_bn254_pairing checks its G1 points: a coordinate not below q, a point off the curve or a
+ * scalar not below r gives NLX_E_RANGE, the message names the term ("term t: ...") and nothing is written.  At most 2^20 segments
+ * and 2^24 terms.  Kernel-timing names "bn254_g1_lincomb_check", "bn254_g1_lincomb". */
+int32_t nlx_bn254_g1_lincomb(nlx_ctx* ctx, const uint64_t* points, const uint64_t* scalars, const uint32_t* first, size_t n_segments,
+                             uint64_t* out);
 /* Test / bench data on the device: out[i] = (i + 1) * base for i < n as G1Affine words - n distinct curve points (an SRS's
  * worth of gather targets for the MSM; a big-integer model makes a few thousand per second).  out: host or device, n x 8
  * words; n <= 2^27; base must not be the point at infinity. */
@@ -519,6 +529,58 @@ int32_t nlx_bn254_groth16_verify(const nlx_bn254_groth16_vk* vk, const uint8_t* 
                                  nlx_bn254_verdict* verdict);
 int32_t nlx_bn254_groth16_verify_batch(const nlx_bn254_groth16_vk* vk, const uint8_t* const* proofs, const size_t* lens, size_t n_proofs,
                                        const uint64_t* public_inputs, nlx_bn254_verdict* verdicts);
+
+/* gnark's plonk VerifyingKey resident on the device and gnark v0.9 plonk.Verify on the bytes of Proof.WriteTo (552 + 64 k; what
+ * nlx_bn254_plonk_prove writes) - csrc/bn254_plonk_verify.hip, DESIGN.md section 32.  The specification of every byte and formula
+ * is tools/gnark_bsb22_model.py; parity with gnark's own Verify is UNPINNED like the rest of f.4.  All arrays host.
+ *   log_n 3 .. 26, n_public <= n, n_commit = k <= NLX_BN254_PLONK_MAX_COMMIT
+ *   k1, k2          four Montgomery words each, below r (as in nlx_bn254_plonk_key_desc)
+ *   commitments     (8 + k) x 8 words in nlx_bn254_plonk_key_commitments' order: s1 s2 s3 ql qr qm qo qk qcp_0 ..
+ *   commit_rows     k rows i_j < n; read only for k > 0
+ *   g1              the SRS's first point (gnark vk.Kzg.G1); g2, g2_tau: [1]_2 and [tau]_2, 16 words each
+ * Creation checks every point as nlx_bn254_groth16_vk_create does (the two G2 points in the subgroup) and keeps the points
+ * resident.  NLX_E_RANGE: a point that fails (the message names it), log_n, k, a row not below n, n_public > n, k1 / k2 not below
+ * r; NLX_E_INVAL: a NULL pointer.  The key belongs to its context and must be destroyed before it. */
+typedef struct nlx_bn254_plonk_vk nlx_bn254_plonk_vk;
+typedef struct {
+    uint32_t log_n, n_public, n_commit;
+    const uint64_t *k1, *k2;
+    const uint64_t* commitments;
+    const uint32_t* commit_rows;
+    const uint64_t *g1;
+    const uint64_t *g2, *g2_tau;
+} nlx_bn254_plonk_vk_desc;
+int32_t nlx_bn254_plonk_vk_create(nlx_ctx* ctx, const nlx_bn254_plonk_vk_desc* desc, nlx_bn254_plonk_vk** out);
+void nlx_bn254_plonk_vk_destroy(nlx_bn254_plonk_vk* vk);
+/* The calling conventions are nlx_bn254_groth16_verify's: the return value says whether the check RAN, the verdict is zero-filled
+ * first, on a rejection nlx_last_error holds one line naming the first rejected proof; NLX_E_INVAL for NULL arguments, NLX_E_RANGE
+ * for a public input not below r (naming the proof and the input).  public_inputs: n_public x 4 Montgomery words per proof, the
+ * proofs' back to back.  A proof gets the first reason that applies:
+ *   NLX_BN254_VERIFY_MALFORMED  index 0: the length, or a count that does not fit (commitment count != k, claimed-value count
+ *                               != 7 + k); after the length the fields are judged in byte order.  Points (a bad flag byte, a
+ *                               coordinate >= q, an x with no y; a compressed point at infinity is a valid point): 0 L, 1 R, 2 O,
+ *                               3 Z, 4 .. 6 H1 .. H3, 7 + j PI2_j, 7 + k the batched opening's H, 8 + k the shifted opening's H.
+ *                               Values not below r: 9 + k + i claimed value i, 16 + 2 k the shifted value
+ *   NLX_BN254_VERIFY_ALGEBRAIC  gnark's "algebraic relation does not hold": lin(zeta) + PI(zeta) - alpha b (o + gamma) z_w -
+ *                               alpha^2 L_1(zeta) != folded_h(zeta) (zeta^n - 1), PI with the Bsb22 terms; an inverse of 0 is 0
+ *   NLX_BN254_VERIFY_PAIRING    the two openings folded into one check of two pairs fail:
+ *                               e(D_f + lambda Z - (v_f + lambda z_w) G + zeta H_b + lambda zeta w H_z, [1]_2)
+ *                               e(-(H_b + lambda H_z), [tau]_2) != 1
+ * The lambda rule.  gnark's kzg.BatchVerifyMultiPoints draws lambda from crypto/rand; this library draws no randomness: lambda =
+ * nlx_bn254_hash_to_field(zeta || gamma' || Z.Marshal() || H_b.Marshal() || H_z.Marshal() || v_f || z_w, dst
+ * "nlx-plonk-kzg-fold") with the scalars as 32 big-endian bytes, 1 in place of 0.  gamma' (FoldProof's challenge) stands in the
+ * message for the folded digest D_f = sum gamma'^i D_i: it is itself a hash over zeta, every D_i and every claimed value, and D_f is
+ * never computed on its own - it is spelled out inside the one combination of the left point.  Any nonzero lambda is a valid run of
+ * gnark's verifier, so acceptance equals gnark's up to a probability of 1 / r.
+ * Host: decoding, square roots, the transcript, the Bsb22 hashes, every scalar (one inversion per proof), the relation.  Device:
+ * two launches of the segmented combination (two segments a proof each), the Miller loops of two pairs a proof, one final
+ * exponentiation a proof - the same launches for one proof and for a batch of up to 2^17 (kernel-timing names
+ * "bn254_plonk_verify_lincomb_a", "bn254_plonk_verify_lincomb_b", "bn254_pairing_miller", "bn254_pairing_final_exp"). */
+#define NLX_BN254_VERIFY_ALGEBRAIC 4u
+int32_t nlx_bn254_plonk_verify(const nlx_bn254_plonk_vk* vk, const uint8_t* proof, size_t len, const uint64_t* public_inputs,
+                               nlx_bn254_verdict* verdict);
+int32_t nlx_bn254_plonk_verify_batch(const nlx_bn254_plonk_vk* vk, const uint8_t* const* proofs, const size_t* lens, size_t n_proofs,
+                                     const uint64_t* public_inputs, nlx_bn254_verdict* verdicts);
 
 /* ---- a3: plonky2::fri::oracle::PolynomialBatch::{from_values, from_coeffs} ----
  * values / coeffs: n_cols x 2^log_n column-major, natural order.  The coset shift is the

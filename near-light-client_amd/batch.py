@@ -431,6 +431,25 @@ def bn254_g1_sum(points):
     return out
 
 
+def bn254_g1_lincomb(ctx, points, scalars, first):
+    """Segmented G1 linear combinations on the GPU (nlx_bn254_g1_lincomb): out[s] = sum of scalars[t] * points[t] over
+    first[s] <= t < first[s + 1], one wave per segment.  points: (n_terms, 8) G1Affine words (bn254_g1_pack), scalars:
+    (n_terms, 4) words of canonical integers below r - numpy arrays or device tensors; first: n_segments + 1 ascending offsets
+    from 0.  Returns (n_segments, 8) uint64 words, all zero for the point at infinity.  A coordinate >= q, a point off the curve
+    or a scalar >= r raises NlxError (NLX_E_RANGE) naming the term."""
+    first = np.ascontiguousarray(first, dtype=np.uint32).reshape(-1)
+    if len(first) < 1:
+        raise ValueError("first holds n_segments + 1 offsets")
+    kp, pp, n = _point_rows(points, 8)
+    ks, sp, n2 = _point_rows(scalars, 4)
+    if n != n2 or n != int(first[-1]):
+        raise ValueError("points and scalars hold first[-1] rows each")
+    out = np.zeros((len(first) - 1, 8), dtype=np.uint64)
+    ctx.check(dll.nlx_bn254_g1_lincomb(ctx.handle, pp if n else None, sp if n else None, first.ctypes.data, len(first) - 1,
+                                       out.ctypes.data if len(out) else None))
+    return out
+
+
 def bn254_g1_multiples(ctx, base, n, device=None):
     """[(i + 1) * base for i < n] as G1Affine words, computed on the GPU: (n, 8) uint64 on the host, or an int64 device
     tensor with device="cuda:k" (test and bench data: n distinct curve points)."""

@@ -643,3 +643,154 @@ def hash_to_field_native(msg, dst=BSB22_DST):
     if rc:
         raise ValueError("nlx_bn254_hash_to_field: error %d" % rc)
     return _from_words_mont(out)
+
+
+# ---- the verifier (csrc/bn254_plonk_verify.hip; the model with real pairings is
+# tools/gnark_plonk_verify_model.py) ----
+VERIFY_ACCEPT, VERIFY_MALFORMED, VERIFY_PAIRING, VERIFY_ALGEBRAIC = 0, 1, 3, 4
+_REASONS = {VERIFY_ACCEPT: "accepted", VERIFY_MALFORMED: "malformed", VERIFY_ALGEBRAIC: "the algebraic relation fails",
+            VERIFY_PAIRING: "the pairing equation fails"}
+_NLX_E_INVAL, _NLX_E_RANGE = -1, -4
+
+
+class _PlonkVkDesc(ctypes.Structure):
+    """nlx_bn254_plonk_vk_desc (include/nlx.h)"""
+    _fields_ = [("log_n", ctypes.c_uint32), ("n_public", ctypes.c_uint32), ("n_commit", ctypes.c_uint32)] + [(name, ctypes.c_void_p) for name in (
+        "k1", "k2", "commitments", "commit_rows", "g1", "g2", "g2_tau")]
+
+
+class Verdict(ctypes.Structure):
+    """nlx_bn254_verdict of the PLONK verifier: accepted, and for a rejected proof the first reason that applies and the field
+    a malformed proof is named by"""
+    _fields_ = [("accepted", ctypes.c_uint32), ("reason", ctypes.c_uint32), ("index", ctypes.c_uint32)]
+
+    k = None      # the key's commitment count, set by VerifyingKey.verify_many: what the indices above 6 are counted from
+    counts_off = False   # set there too: the bytes' length or one of their two counts does not fit the key (index 0 is then not L)
+
+    def field_name(self):
+        i, k = int(self.index), self.k
+        if i == 0 and self.reason == VERIFY_MALFORMED and self.counts_off:
+            return "the length or a count"
+        if i < 7:
+            return ("L", "R", "O", "Z", "H1", "H2", "H3")[i]
+        if k is None:
+            return "field %d" % i
+        if i < 7 + k:
+            return "PI2_%d" % (i - 7)
+        if i < 9 + k:
+            return ("the batched opening's H", "the shifted opening's H")[i - 7 - k]
+        if i < 16 + 2 * k:
+            return "claimed value %d" % (i - 9 - k)
+        return "the shifted value"
+
+    def __bool__(self):
+        return bool(self.accepted)
+
+    def __str__(self):
+        if self.accepted:
+            return "accepted"
+        text = "rejected: " + _REASONS.get(int(self.reason), "reason %d" % self.reason)
+        return text + (" at " + self.field_name() if self.reason == VERIFY_MALFORMED else "")
+
+    def raise_if_rejected(self):
+        if not self.accepted:
+            from ._lib import NlxError
+            raise NlxError(_NLX_E_INVAL, "PLONK proof " + str(self))
+        return self
+
+
+_G1_WORDS = B.bn254_g1_pack([(1, 2)])[0]
+
+
+class VerifyingKey:
+    """nlx_bn254_plonk_vk: gnark's plonk.VerifyingKey resident on the device (owns the handle; close() or the context's close()
+    releases it).  k1, k2: integers; commitments: (8 + k, 8) G1Affine words in ResidentKey.key_commitments' order (s1 s2 s3 ql
+    qr qm qo qk qcp_0 ..); commit_rows: the k rows i_j; g1: the SRS's first point (8 words; the generator by default); g2,
+    g2_tau: [1]_2 and [tau]_2, 16 words each (batch.bn254_g2_pack)."""
+
+    def __init__(self, ctx, log_n, n_public, k1, k2, commitments, commit_rows=(), g1=None, g2=None, g2_tau=None):
+        from ._lib import NlxError, dll
+        self.ctx, self.handle = ctx, None
+        if g2 is None or g2_tau is None:
+            raise ValueError("the key needs [1]_2 and [tau]_2")
+        self.log_n, self.n_public = int(log_n), int(n_public)
+        keep = {"commitments": np.ascontiguousarray(commitments, dtype=np.uint64).reshape(-1, 8)}
+        self.k = len(keep["commitments"]) - 8
+        if self.k < 0 or len(commit_rows) != self.k:
+            raise ValueError("8 + k commitments and k commitment rows")
+        for name, x in (("k1", k1), ("k2", k2)):
+            x = int(x)
+            if not 0 <= x < (1 << 256):
+                raise NlxError(_NLX_E_RANGE, "%s does not fit four words" % name)
+            keep[name] = B._fr_words(_to_mont(x) if x < R else x)   # r <= x < 2^256 is no residue: the library refuses its words
+        rows = [int(i) for i in commit_rows]
+        if any(not 0 <= i < (1 << 32) for i in rows) or not 0 <= self.log_n < (1 << 32) or not 0 <= self.n_public < (1 << 32):
+            raise NlxError(_NLX_E_RANGE, "a row or a count does not fit 32 bits")
+        keep["commit_rows"] = np.array(rows + [0], dtype=np.uint32)
+        keep["g1"] = np.ascontiguousarray(_G1_WORDS if g1 is None else g1, dtype=np.uint64).reshape(8)
+        keep["g2"] = np.ascontiguousarray(g2, dtype=np.uint64).reshape(16)
+        keep["g2_tau"] = np.ascontiguousarray(g2_tau, dtype=np.uint64).reshape(16)
+        d = _PlonkVkDesc()
+        d.log_n, d.n_public, d.n_commit = self.log_n, self.n_public, self.k
+        for name in ("k1", "k2", "commitments", "commit_rows", "g1", "g2", "g2_tau"):
+            setattr(d, name, keep[name].ctypes.data)
+        h = ctypes.c_void_p()
+        ctx.check(dll.nlx_bn254_plonk_vk_create(ctx.handle, ctypes.byref(d), ctypes.byref(h)))
+        self.handle = h
+        ctx._adopt(self)
+
+    @classmethod
+    def from_resident(cls, key, g2, g2_tau, n_public, g1=None):
+        """the verifying key of a ResidentKey: its 8 + k commitments (nlx_bn254_plonk_key_commitments), k1, k2 and commitment rows"""
+        return cls(key.ctx, key.log_n, n_public, key.k1, key.k2, key.key_commitments(), [c["row"] for c in key.bsb22], g1=g1, g2=g2, g2_tau=g2_tau)
+
+    def verify_many(self, proofs, publics):
+        """One Verdict per proof.  proofs: the bytes of Proof.WriteTo; publics: per proof its n_public public inputs as integers.
+        The whole batch is the same four launches as one proof.  An integer not below r raises NlxError (NLX_E_RANGE)."""
+        from ._lib import NlxError, dll
+        if not self.handle:
+            raise NlxError(_NLX_E_INVAL, "the verifying key is closed")
+        n = len(proofs)
+        if len(publics) != n or any(len(p) != self.n_public for p in publics):
+            raise ValueError("one list of n_public public inputs per proof")
+        blobs = [bytes(p) for p in proofs]
+        ptrs = (ctypes.c_char_p * max(n, 1))(*blobs)
+        lens = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in blobs])
+        words = np.zeros((max(n * self.n_public, 1), 4), dtype=np.uint64)
+        row = 0
+        for p in publics:
+            for x in p:
+                x = int(x)
+                if not 0 <= x < (1 << 256):
+                    raise NlxError(_NLX_E_RANGE, "proof %d: a public input does not fit four words" % (row // max(self.n_public, 1)))
+                m = _to_mont(x) if x < R else x               # r <= x < 2^256 is no residue: its words go as they are and the library refuses them
+                for w in range(4):
+                    words[row, w] = (m >> (64 * w)) & 0xFFFFFFFFFFFFFFFF
+                row += 1
+        verdicts = (Verdict * max(n, 1))()
+        self.ctx.check(dll.nlx_bn254_plonk_verify_batch(self.handle, ptrs, lens, n, words.ctypes.data, verdicts))
+        out = []
+        for i in range(n):
+            v = Verdict(verdicts[i].accepted, verdicts[i].reason, verdicts[i].index)
+            v.k = self.k
+            b, at = blobs[i], 260 + 32 * self.k
+            v.counts_off = (len(b) != 552 + 64 * self.k or int.from_bytes(b[224:228], "big") != self.k
+                            or int.from_bytes(b[at:at + 4], "big") != 7 + self.k)
+            out.append(v)
+        return out
+
+    def verify(self, proof, public=()):
+        """nlx_bn254_plonk_verify: one proof's Verdict"""
+        return self.verify_many([proof], [list(public)])[0]
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            from ._lib import dll
+            dll.nlx_bn254_plonk_vk_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

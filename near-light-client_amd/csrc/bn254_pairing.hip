@@ -17,7 +17,9 @@
 #include <vector>
 #include "bn254_curve29.hpp"
 #include "bn254_msm.hpp"
+#include "bn254_gnark_bytes.hpp"
 #include "bn254_pairing.hpp"
+#include "bn254_pairing_launch.hpp"
 #include "ctx.hpp"
 #include "transcript.hpp"
 #include "../../include/nlx.h"
@@ -26,9 +28,6 @@ using namespace nlx;
 using namespace nlx::pairing;
 
 namespace {
-
-constexpr uint32_t WORD_UNSET = 0xFFFFFFFFu;
-constexpr size_t MAX_PAIRS = (size_t)1 << 20;
 
 // stride: words between one point and the next (the verifier tests only the first pair of each proof)
 __global__ __launch_bounds__(64) void k_bn254_pairing_points(const uint64_t* __restrict__ g1, const uint64_t* __restrict__ g2, uint32_t n,
@@ -115,6 +114,12 @@ const char* status_text(uint32_t st) {
     }
 }
 
+}  // namespace
+
+// declared in bn254_pairing_launch.hpp: the PLONK verifier (bn254_plonk_verify.hip) enqueues the same checks
+namespace nlx {
+namespace pairing {
+
 // The entry checks of n pairs (either side may be NULL): enqueues, reads the status words back, answers NLX_E_RANGE naming the
 // first offending pair.  `what`: how the message calls a pair.
 int32_t check_points(nlx_ctx* ctx, Scratch& scratch, const uint64_t* d_g1, const uint64_t* d_g2, size_t n, const char* what) {
@@ -160,6 +165,11 @@ int32_t read_results(nlx_ctx* ctx, const uint32_t* d_result, size_t n, std::vect
         if (out[i] > 1) return ctx->fail(NLX_E_HIP, "pairing: the final exponentiation wrote no result for check %zu", i);
     return NLX_OK;
 }
+
+}  // namespace pairing
+}  // namespace nlx
+
+namespace {
 
 int32_t pairing_body(nlx_ctx* ctx, Scratch& scratch, const uint64_t* g1, const uint64_t* g2, size_t n, uint32_t flags, uint64_t* gt_out) {
     Staged s1(ctx, g1, n * 64, true, false), s2(ctx, g2, n * 128, true, false);
@@ -251,6 +261,13 @@ using bnf::RP;
 typedef bnf::Fp<QP> Fq;
 typedef bnf::Fp<RP> Fr;
 typedef msm::H2 H2;
+using ppr::fq_from_be;
+using ppr::fq_sqrt;
+using ppr::fr_to_be;
+using ppr::g1_decode;
+using ppr::g1_marshal;
+using ppr::lex_largest;
+using ppr::rest_zero;
 
 void vk_free(nlx_bn254_groth16_vk* vk) {
     if (!vk) return;
@@ -261,29 +278,6 @@ void vk_free(nlx_bn254_groth16_vk* vk) {
     delete vk;
 }
 
-// ---- decoding gnark-crypto's compressed points on the host (eight-limb arithmetic, bn254_fp.hpp) ----
-template <class P>
-bnf::Fp<P> pow_limbs(const bnf::Fp<P>& a, const uint32_t e[8]) {
-    bnf::Fp<P> r = bnf::one<P>();
-    for (int bit = 255; bit >= 0; bit--) {
-        r = bnf::sqr(r);
-        if ((e[bit >> 5] >> (bit & 31)) & 1) r = bnf::mul(r, a);
-    }
-    return r;
-}
-// a square root in Fq (q = 3 mod 4: a^((q + 1) / 4)), false if there is none
-bool fq_sqrt(const Fq& a, Fq& out) {
-    uint32_t e[8];
-    uint64_t c = 1;
-    for (int i = 0; i < 8; i++) {   // q + 1
-        c += QP::mod(i);
-        e[i] = (uint32_t)c;
-        c >>= 32;
-    }
-    for (int i = 0; i < 8; i++) e[i] = (e[i] >> 2) | (i < 7 ? e[i + 1] << 30 : 0);
-    out = pow_limbs<QP>(a, e);
-    return bnf::equal(bnf::sqr(out), a);
-}
 // a square root in Fq2 by the complex method: the norm's root, then two roots in Fq
 bool f2_sqrt_host(const H2::T& a, H2::T& out) {
     Fq y;
@@ -306,53 +300,6 @@ bool f2_sqrt_host(const H2::T& a, H2::T& out) {
     const H2::T sq = H2::mul(out, out);
     return bnf::equal(sq.c0, a.c0) && bnf::equal(sq.c1, a.c1);
 }
-// 32 big-endian bytes (the top `mask_bits` bits dropped) -> an element; false if the integer is not below q
-bool fq_from_be(const uint8_t* b, bool mask, Fq& out) {
-    Fq x;
-    for (int i = 0; i < 8; i++) {
-        const uint8_t* p = b + 28 - 4 * i;
-        uint32_t w = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-        if (i == 7 && mask) w &= 0x3FFFFFFFu;
-        x.v[i] = w;
-    }
-    if (bnf::geq_mod(x)) return false;
-    out = bnf::to_mont(x);
-    return true;
-}
-void fq_to_be(const Fq& a, uint8_t* b) {
-    const Fq c = bnf::from_mont(a);
-    for (int i = 0; i < 8; i++) {
-        uint8_t* p = b + 28 - 4 * i;
-        p[0] = (uint8_t)(c.v[i] >> 24); p[1] = (uint8_t)(c.v[i] >> 16); p[2] = (uint8_t)(c.v[i] >> 8); p[3] = (uint8_t)c.v[i];
-    }
-}
-// gnark-crypto's "lexicographically largest": y > (q - 1) / 2, i.e. y > -y as integers
-bool lex_largest(const Fq& y) {
-    const Fq a = bnf::from_mont(y), b = bnf::from_mont(bnf::neg(y));
-    for (int i = 7; i >= 0; i--)
-        if (a.v[i] != b.v[i]) return a.v[i] > b.v[i];
-    return false;
-}
-bool rest_zero(const uint8_t* b, size_t n) {
-    uint8_t o = 0;
-    for (size_t i = 1; i < n; i++) o |= b[i];
-    return o == 0;
-}
-// G1Affine.SetBytes on 32 bytes: words (all zero for the point at infinity); false: malformed
-bool g1_decode(const uint8_t* b, uint64_t w[8]) {
-    memset(w, 0, 64);
-    const unsigned flag = b[0] >> 6;
-    if (flag == 1) return b[0] == 0x40 && rest_zero(b, 32);
-    if (flag == 0) return false;
-    Fq x, y;
-    if (!fq_from_be(b, true, x)) return false;
-    const Fq one = bnf::one<QP>(), three = bnf::add(one, bnf::add(one, one));
-    if (!fq_sqrt(bnf::add(bnf::mul(bnf::sqr(x), x), three), y)) return false;
-    if (lex_largest(y) != (flag == 3)) y = bnf::neg(y);
-    bnf::store_words(x, w);
-    bnf::store_words(y, w + 4);
-    return true;
-}
 // G2Affine.SetBytes on 64 bytes: X.A1 || X.A0
 bool g2_decode(const uint8_t* b, uint64_t w[16]) {
     memset(w, 0, 128);
@@ -370,24 +317,6 @@ bool g2_decode(const uint8_t* b, uint64_t w[16]) {
     H2::store(x, w);
     H2::store(y, w + 8);
     return true;
-}
-// G1Affine.Marshal(): x || y big-endian; the point at infinity is the flag byte 0x40 and zeros
-void g1_marshal(const uint64_t w[8], uint8_t out[64]) {
-    memset(out, 0, 64);
-    uint64_t o = 0;
-    for (int i = 0; i < 8; i++) o |= w[i];
-    if (!o) {
-        out[0] = 0x40;
-        return;
-    }
-    fq_to_be(bnf::load_words<QP>(w), out);
-    fq_to_be(bnf::load_words<QP>(w + 4), out + 32);
-}
-void fr_to_be(const Fr& canonical, uint8_t* b) {
-    for (int i = 0; i < 8; i++) {
-        uint8_t* p = b + 28 - 4 * i;
-        p[0] = (uint8_t)(canonical.v[i] >> 24); p[1] = (uint8_t)(canonical.v[i] >> 16); p[2] = (uint8_t)(canonical.v[i] >> 8); p[3] = (uint8_t)canonical.v[i];
-    }
 }
 void g2_negate(const uint64_t* in, uint64_t* out) {
     memcpy(out, in, 128);
