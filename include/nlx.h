@@ -140,11 +140,20 @@ int32_t nlx_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, size_t n_leaves, 
  * permute_batch: states n x 16 words (4 elements x 4 words), permuted in place; an element >= r -> NLX_E_RANGE.
  * hash_rows: hash_or_noop of every row (inputs taken mod p): <= 4 elements are the digest sum x_i 2^(64 i) itself (NLX_E_RANGE
  * if that is >= r), longer rows hash_no_pad (9 elements per permutation, three per slot 1..3, the slots overwritten).
- * merkle_build: nlx_merkle_build with these leaves and two_to_one(a, b) = permute([0, 0, a, b])[0] for the nodes. */
+ * merkle_build: nlx_merkle_build with these leaves and two_to_one(a, b) = permute([0, 0, a, b])[0] for the nodes.
+ * merkle_verify_batch: plonky2's verify_merkle_proof_to_cap for n (leaf, index, path) triples against one cap, one byte each
+ * (ok_out[i] = 1: the path reaches cap[indices[i] >> path_len]).  Host arrays in merkle_build's layouts: leaves n x leaf_len
+ * (taken mod p; leaf_len <= 4: hash_rows' no-op rule, NLX_E_RANGE if a packed leaf is >= r), indices n u64 (NLX_E_RANGE unless
+ * below 2^(path_len + cap_height)), siblings n x path_len x 4 bottom-up, cap 2^cap_height x 4.  A sibling or cap entry is a
+ * digest: one integer below r, whatever its words are against p (NLX_E_RANGE otherwise).  One quad of lanes per triple, the
+ * device code of the proof verifier's path kernel. */
 int32_t nlx_poseidon_bn128_permute_batch(nlx_ctx* ctx, uint64_t* states, size_t n);
 int32_t nlx_poseidon_bn128_hash_rows(nlx_ctx* ctx, const uint64_t* rows, size_t n_rows, size_t row_len, uint64_t* digests_out);
 int32_t nlx_poseidon_bn128_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, size_t n_leaves, size_t leaf_len, uint32_t cap_height,
                                         uint64_t* digests_out, uint64_t* cap_out);
+int32_t nlx_poseidon_bn128_merkle_verify_batch(nlx_ctx* ctx, const uint64_t* leaves, size_t n, size_t leaf_len, const uint64_t* indices,
+                                               const uint64_t* siblings, uint32_t path_len, const uint64_t* cap, uint32_t cap_height,
+                                               uint8_t* ok_out);
 
 /* ---- a2: plonky2_field::fft::{fft, ifft}, PolynomialCoeffs::coset_fft, PolynomialValues::coset_ifft ----
  * cols: n_cols x 2^log_n, column-major, transformed in place, natural order in and out.
@@ -1117,7 +1126,8 @@ size_t nlx_stark_proof_bytes(const nlx_stark* s);
  * constants_sigmas, wires, zs_partial, quotient), per FRI layer the fold before the path, and the final polynomial.
  * One deliberate difference from the test oracle's verifier (oracle/plonk.c), which does not look at it: a field word of the
  * proof that is not below p is NLX_VERIFY_MALFORMED here, as for STARK proofs.
- * Only the Goldilocks Poseidon config: a NLX_HASHER_POSEIDON_BN128 circuit gives NLX_E_UNSUPPORTED. */
+ * nlx_verifier_from_circuit and nlx_verifier_create are the Goldilocks Poseidon config's: a NLX_HASHER_POSEIDON_BN128 circuit
+ * gives NLX_E_UNSUPPORTED there.  The *_hasher entries below take either config. */
 typedef nlx_stark_verdict nlx_proof_verdict;
 typedef struct nlx_verifier nlx_verifier;
 /* the cap and the digest of a built circuit; the verifier lives on the circuit's context and does not need the circuit later */
@@ -1127,6 +1137,21 @@ int32_t nlx_verifier_from_circuit(const nlx_circuit* c, nlx_verifier** out);
  * (NLX_E_INVAL otherwise). */
 int32_t nlx_verifier_create(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants_sigmas_cap,
                             const uint64_t digest[4], nlx_verifier** out);
+/* The same with the config's Hasher named (NLX_HASHER_*).  NLX_HASHER_POSEIDON_GOLDILOCKS is exactly the
+ * two entries above.  NLX_HASHER_POSEIDON_BN128 verifies the proofs of a nlx_circuit_build_hasher circuit under plonky2x's
+ * PoseidonBN128GoldilocksConfig (rules recalled, not pinned against plonky2x's own verifier): every Merkle path over BN254 Fr, the
+ * circuit digest and the caps entering the transcript as five limbs a digest, everything else as above.  A digest of the proof -
+ * the caps, the FRI caps, every sibling - is four little-endian words of ONE integer that must be below r (its words need not be
+ * below p); a digest that is not is NLX_VERIFY_MALFORMED, as a field word that is not below p.
+ * create_hasher: the descriptor is checked as nlx_circuit_build_hasher checks it (NLX_E_UNSUPPORTED under BN128 for lookup tables
+ * and for an oracle of <= 4 columns), cap and digest as digests of that hasher (NLX_E_RANGE).
+ * from_circuit_hasher: the config the caller expects; NLX_E_INVAL when the circuit was built under the other one, NLX_E_RANGE
+ * for an unknown hasher. */
+int32_t nlx_verifier_create_hasher(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants_sigmas_cap,
+                                   const uint64_t digest[4], uint32_t hasher, nlx_verifier** out);
+int32_t nlx_verifier_from_circuit_hasher(const nlx_circuit* c, uint32_t hasher, nlx_verifier** out);
+/* the verifier's NLX_HASHER_* (NLX_E_INVAL for NULL) */
+int32_t nlx_verifier_hasher(const nlx_verifier* v);
 void nlx_verifier_destroy(nlx_verifier* v);
 /* the exact length of a proof of this circuit (0 for NULL) */
 size_t nlx_verifier_proof_bytes(const nlx_verifier* v);

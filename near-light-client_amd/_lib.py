@@ -74,6 +74,9 @@ SIGNATURES = {
                                                       ctypes.c_void_p]),
     "nlx_poseidon_bn128_merkle_build": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
                                                          ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_poseidon_bn128_merkle_verify_batch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                                ctypes.c_uint32, ctypes.c_void_p]),
     "nlx_ntt_batch": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32,
                                        ctypes.c_int, ctypes.c_uint64]),
     "nlx_ntt_split_level": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
@@ -198,6 +201,10 @@ SIGNATURES = {
     "nlx_stark_proof_bytes": (ctypes.c_size_t, [ctypes.c_void_p]),
     "nlx_verifier_from_circuit": (ctypes.c_int32, [ctypes.c_void_p, c_void_pp]),
     "nlx_verifier_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
+    "nlx_verifier_create_hasher": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                                    c_void_pp]),
+    "nlx_verifier_from_circuit_hasher": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, c_void_pp]),
+    "nlx_verifier_hasher": (ctypes.c_int32, [ctypes.c_void_p]),
     "nlx_verifier_destroy": (None, [ctypes.c_void_p]),
     "nlx_verifier_proof_bytes": (ctypes.c_size_t, [ctypes.c_void_p]),
     "nlx_verify": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),

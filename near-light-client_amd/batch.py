@@ -541,6 +541,29 @@ def poseidon_bn128_hash_rows(ctx, rows, as_ints=False):
     return bn254_unpack(out[None])[0] if as_ints else out
 
 
+def poseidon_bn128_merkle_verify(ctx, leaves, indices, siblings, cap):
+    """plonky2's verify_merkle_proof_to_cap under PoseidonBN128 for n (leaf, index, path) triples against one cap
+    (nlx_poseidon_bn128_merkle_verify_batch): leaves (n, leaf_len) Goldilocks words, indices n, siblings (n, path_len, 4) bottom-up
+    as MerkleTree.prove returns them, cap (2^cap_height, 4) - a bool array, True where the path reaches the cap.  NlxError
+    NLX_E_RANGE for a sibling or cap entry that is not below r, or an index past the tree."""
+    lv = np.ascontiguousarray(leaves, dtype=np.uint64)
+    if lv.ndim != 2:
+        raise ValueError("leaves must be a 2-D matrix")
+    n = lv.shape[0]
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    sib = np.ascontiguousarray(siblings, dtype=np.uint64)
+    sib = sib.reshape(n, -1, 4) if sib.size else np.zeros((n, 0, 4), np.uint64)   # path_len = 0: the leaf's digest is a cap entry
+    cp = np.ascontiguousarray(cap, dtype=np.uint64).reshape(-1, 4)
+    n_cap = cp.shape[0]
+    if idx.size != n or n_cap == 0 or n_cap & (n_cap - 1):
+        raise ValueError("one index per leaf and a cap of 2^cap_height digests")
+    ok = np.zeros(n, dtype=np.uint8)
+    ctx.check(dll.nlx_poseidon_bn128_merkle_verify_batch(ctx.handle, ptr(lv) if lv.size else None, n, lv.shape[1], ptr(idx) if n else None,
+                                                         ptr(sib) if sib.size else None, sib.shape[1], ptr(cp), n_cap.bit_length() - 1,
+                                                         ok.ctypes.data if n else None))
+    return ok.astype(bool)
+
+
 # ---- row f.4: the optimal ate pairing (csrc/bn254_pairing.hip, nlx_bn254_pairing / nlx_bn254_pairing_check) ----
 def _point_rows(a, width):
     if hasattr(a, "data_ptr"):

@@ -10,11 +10,16 @@
 // and the one parser that checks a proof's structure against that.  The path-length bytes leave every later 64-bit word
 // unaligned.  parse() checks those bytes and copies the words into an aligned staging buffer - the proof without its path-length
 // bytes, so a word's place there follows from the descriptor too.  The device reads only that buffer.
-// Host only: no HIP include, so that a stand-alone program can run it under a sanitizer (tests/tools/layout_check.cpp).
+// A proof made under the PoseidonBN128 config (Layout::hasher = HASHER_BN128) has the same bytes, but a digest there is four
+// little-endian words of ONE integer below BN254's r, and its words need not be below p: the layout knows which staging words are
+// digests - the head's caps, the FRI caps, every path sibling - and parse() checks those four at a time against r.
+// Host only: no HIP include, so that a stand-alone program can run it under a sanitizer (tests/tools/layout_check.cpp,
+// tests/tools/digest_words_check.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
+#include "bn254_fp.hpp"
 
 namespace nlx {
 namespace fpl {
@@ -22,6 +27,7 @@ namespace fpl {
 constexpr uint64_t FIELD_P = 0xFFFFFFFF00000001ULL;
 constexpr uint32_t MAX_TREES = 32;    // initial trees of one proof
 constexpr uint32_t MAX_LAYERS = 16;
+enum : uint32_t { HASHER_GOLDILOCKS = 0, HASHER_BN128 = 1 };   // NLX_HASHER_* (include/nlx.h)
 
 // FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits)
 inline uint32_t num_layers(uint32_t degree_bits, uint32_t rate_bits, uint32_t cap_height, uint32_t arity_bits, uint32_t final_poly_bits) {
@@ -35,6 +41,8 @@ inline uint32_t num_layers(uint32_t degree_bits, uint32_t rate_bits, uint32_t ca
 }
 
 struct Layout {
+    uint32_t hasher;                       // of the proof's Merkle trees; fill() leaves HASHER_GOLDILOCKS
+    size_t w_head_caps, n_head_cap_words;  // the caps in the format's head (staging words); the format sets them after fill()
     uint32_t n_queries, n_pis, n_trees, tree_cols[MAX_TREES];
     uint32_t log_L, n_layers, arity, final_len;
     uint32_t tree_plen, layer_plen[MAX_LAYERS];
@@ -54,6 +62,8 @@ struct Layout {
 // false: a shape no proof has (more trees or layers than the format allows)
 inline bool fill(Layout& l, uint32_t degree_bits, uint32_t rate_bits, uint32_t cap_height, uint32_t arity_bits, uint32_t final_poly_bits,
                  uint32_t n_queries, uint32_t n_pis, uint32_t n_trees, const uint32_t* tree_cols, size_t head_words, size_t tail_words) {
+    l.hasher = HASHER_GOLDILOCKS;
+    l.w_head_caps = l.n_head_cap_words = 0;
     l.log_L = degree_bits + rate_bits;
     l.n_layers = num_layers(degree_bits, rate_bits, cap_height, arity_bits, final_poly_bits);
     if (n_trees > MAX_TREES || l.n_layers > MAX_LAYERS || cap_height > l.log_L || arity_bits > 6) return false;
@@ -122,6 +132,43 @@ struct Finding {
     size_t word = 0;                           // BAD_WORD: its index in the staging buffer
 };
 
+// The first word in staging[a, b) that is not below p, or b
+inline size_t first_word_not_below_p(const uint64_t* staging, size_t a, size_t b) {
+    for (size_t i = a; i < b; i++)
+        if (staging[i] >= FIELD_P) return i;
+    return b;
+}
+// The first word of the first digest in staging[a, b) (whole digests of four words) that is not below r, or b
+inline size_t first_digest_not_below_r(const uint64_t* staging, size_t a, size_t b) {
+    for (size_t i = a; i + 4 <= b; i += 4)
+        if (!bnf::below_mod<bnf::RP>(staging + i)) return i;
+    return b;
+}
+
+// The word check under HASHER_BN128, in staging order: a digest (the head's caps, the FRI caps, every sibling) must be below r as
+// one integer, every other word below p.  The index of the first offender (a digest's first word), or l.w_total.
+inline size_t first_bad_word_bn128(const Layout& l, const uint64_t* staging) {
+    size_t at = 0, bad;
+    // [at, to): field words, then [to, to + n): digests
+    auto span = [&](size_t to, size_t n) {
+        if ((bad = first_word_not_below_p(staging, at, to)) != to) return false;
+        if ((bad = first_digest_not_below_r(staging, to, to + n)) != to + n) return false;
+        at = to + n;
+        return true;
+    };
+    if (!span(l.w_head_caps, l.n_head_cap_words)) return bad;
+    if (!span(l.w_fri_caps, l.n_layers * l.cap_words)) return bad;
+    for (uint32_t q = 0; q < l.n_queries; q++) {
+        const size_t q0 = l.w_queries + (size_t)q * l.w_query_words;
+        for (uint32_t o = 0; o < l.n_trees; o++)
+            if (!span(q0 + l.w_path[o], 4 * (size_t)l.tree_plen)) return bad;
+        for (uint32_t k = 0; k < l.n_layers; k++)
+            if (!span(q0 + l.w_layer_path[k], 4 * (size_t)l.layer_plen[k])) return bad;
+    }
+    if (!span(l.w_total, 0)) return bad;
+    return l.w_total;
+}
+
 // Checks `proof` against the layout and fills `staging` (l.w_total words).  Reads proof[0 .. len) only, and nothing at all unless
 // len == l.total; no offset depends on a byte of the proof.  The first finding wins, in the order of the enum.
 inline uint32_t parse(const Layout& l, const uint8_t* proof, size_t len, uint64_t* staging, Finding* f) {
@@ -154,6 +201,15 @@ inline uint32_t parse(const Layout& l, const uint8_t* proof, size_t len, uint64_
     }
     memcpy(staging + l.w_final_poly, proof + l.final_poly, l.total - l.final_poly);
     if (f->what != SOUND) return f->what;
+    if (l.hasher == HASHER_BN128) {
+        const size_t bad = first_bad_word_bn128(l, staging);
+        if (bad != l.w_total) {
+            f->what = BAD_WORD;
+            f->word = bad;
+            return f->what;
+        }
+        return SOUND;
+    }
     for (size_t i = 0; i < l.w_total; i++)
         if (staging[i] >= FIELD_P) {   // the proof-of-work witness is a field element too; the count word was compared above
             f->what = BAD_WORD;

@@ -4,6 +4,7 @@
 // transcript output reduced mod the LDE size, none from a byte of the proof.
 #include <algorithm>
 #include "fri_verify.hpp"
+#include "poseidon_bn128_path.hpp"
 #include "poseidon_quad.hpp"
 
 namespace nlx {
@@ -95,6 +96,31 @@ __global__ __launch_bounds__(64) void k_fri_paths(PathParams p) {
     const unsigned long long m = __ballot(ok);
     const bool quad_ok = ((m >> (threadIdx.x & 60u)) & 0xFull) == 0xFull;
     if (live && q == 0) p.fail[(size_t)item * p.n_trees + blockIdx.y] = quad_ok ? 0 : 1;
+}
+
+// The same grid and items for trees hashed with PoseidonBN128 (Verifier::hasher): one quad per (proof, query, tree) on the
+// lane-split permutation, lane q holding element q of the state as nine 29-bit limbs in Montgomery form; the work of the quad is
+// pbn::quad_merkle_path (poseidon_bn128_path.hpp).  A digest is one integer below r, four words: lane 0 brings the last one out
+// of Montgomery form and compares the four words with the cap's.  The siblings were checked below r by the parser
+// (fpl::first_bad_word_bn128).  There is no hash_or_noop branch: validate_circuit_desc (prover.hip) refuses a BN128 circuit
+// with an oracle of <= 4 columns, and a commit-phase leaf has 2 arity >= 8 words - every row here is hashed.
+__global__ __launch_bounds__(64) void k_fri_paths_bn128(PathParams p) {
+    const VTree t = p.trees[blockIdx.y];
+    const uint32_t q = threadIdx.x & 3;
+    const uint32_t raw = blockIdx.x * 16 + (threadIdx.x >> 2);
+    const bool live = raw < p.n_items;
+    const uint32_t item = live ? raw : p.n_items - 1;   // spare quads redo the last item and store nothing: a quad stays whole
+    const uint32_t proof = item / p.n_queries, query = item - proof * p.n_queries;
+    const uint64_t* base = p.stage + (size_t)proof * p.w_total;
+    const uint64_t* qs = base + p.w_queries + (size_t)query * p.w_query_words;
+    const uint32_t idx = p.qidx[item] >> t.shift;
+    const pbn::QuadRow qrow = pbn::quad_row(q);
+    const pbn::Fe s = pbn::quad_merkle_path(f29::zero(), qs + t.w_row, t.width, idx, qs + t.w_path, t.path_len, q, qrow);
+    uint64_t d[4];
+    pbn::to_words(s, d);
+    const uint64_t* cap = (t.ext_cap ? p.ext_cap : base) + t.w_cap + (size_t)(idx >> t.path_len) * 4;   // idx < 2^(path_len + cap_height)
+    const bool ok = d[0] == cap[0] && d[1] == cap[1] && d[2] == cap[2] && d[3] == cap[3];
+    if (live && q == 0) p.fail[(size_t)item * p.n_trees + blockIdx.y] = ok ? 0 : 1;
 }
 
 struct FriParams {
@@ -226,10 +252,12 @@ const char* reason_name(uint32_t r) {
     return r <= NLX_VERIFY_FINAL_POLY ? names[r] : "?";
 }
 
-// the transcript from the FRI commit caps to the query indices; returns whether the proof of work fails
-bool transcript_tail(Challenger& ch, const fpl::Layout& l, uint32_t pow_bits, const uint64_t* w, uint64_t* pp, uint32_t* qidx) {
+// the transcript from the FRI commit caps to the query indices; returns whether the proof of work fails.  A cap enters through
+// observe_hash: under BN128 five limbs a digest, which the parser has found below r; the sponge, the proof of work and the
+// reduction of the query indices are Goldilocks under both configs
+bool transcript_tail(Challenger& ch, const fpl::Layout& l, uint32_t hasher, uint32_t pow_bits, const uint64_t* w, uint64_t* pp, uint32_t* qidx) {
     for (uint32_t k = 0; k < l.n_layers; k++) {
-        ch.observe(w + l.w_fri_caps + k * l.cap_words, l.cap_words);
+        (void)observe_hash(hasher, ch, w + l.w_fri_caps + k * l.cap_words, l.cap_words / 4);
         ch.ext_challenge(pp + PP_FRI_BETAS + 2 * k);
     }
     ch.observe(w + l.w_final_poly, 2 * (size_t)l.final_len);
@@ -291,11 +319,14 @@ int32_t verify_live(Verifier& v, VerifyCall& vc, const std::vector<size_t>& live
         for (uint32_t k = 0; k < R; k++)
             pa.trees[NT + k] = VTree{(uint32_t)l.w_layer_evals[k], 2 * l.arity, (uint32_t)l.w_layer_path[k], l.layer_plen[k],
                                      (uint32_t)(l.w_fri_caps + k * capw), (k + 1) * v.arity_bits, 0, 0};
+        const bool bn128 = v.hasher == NLX_HASHER_POSEIDON_BN128;
+        const uint32_t chunk = bn128 ? pbn::CHUNK : 8;   // words a permutation absorbs
         size_t perms = 0;
-        for (uint32_t t = 0; t < n_trees; t++) perms += (pa.trees[t].width + 7) / 8 + pa.trees[t].path_len;
+        for (uint32_t t = 0; t < n_trees; t++) perms += (pa.trees[t].width + chunk - 1) / chunk + pa.trees[t].path_len;
         ctx->begin_kernel(v.name_paths, 8.0 * np * l.w_total, (double)perms * n_items);
-        hipLaunchKernelGGL(v.grouped_leaves ? k_fri_paths<true> : k_fri_paths<false>, dim3((unsigned)((n_items + 15) / 16), n_trees), dim3(64), 0,
-                           st, pa);
+        const dim3 grid((unsigned)((n_items + 15) / 16), n_trees);
+        if (bn128) hipLaunchKernelGGL(k_fri_paths_bn128, grid, dim3(64), 0, st, pa);
+        else hipLaunchKernelGGL(v.grouped_leaves ? k_fri_paths<true> : k_fri_paths<false>, grid, dim3(64), 0, st, pa);
         ctx->end_kernel();
     }
     {
@@ -414,7 +445,7 @@ int32_t verify_staged(Verifier& v, VerifyCall& vc, const uint8_t* const* proofs,
         uint64_t* pp = vc.pp.data() + at * v.pp_stride;
         Challenger ch;
         v.head(w, pp, ch);
-        pow_bad.push_back(transcript_tail(ch, l, v.pow_bits, w, pp, vc.qidx.data() + at * nQ));
+        pow_bad.push_back(transcript_tail(ch, l, v.hasher, v.pow_bits, w, pp, vc.qidx.data() + at * nQ));
         live.push_back(i);
     }
     if (!live.empty()) NLX_RC(verify_live(v, vc, live, pow_bad, verdicts));

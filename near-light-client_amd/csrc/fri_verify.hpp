@@ -3,6 +3,7 @@
 // of opened columns that enter the two FRI batches - and plugs in what is its own: the head of the transcript, the constraint
 // launch and the judgement of what that launch leaves.  fri_verify.hip has the two kernels every verifier runs
 //   k_fri_paths    one quad of lanes per (proof, query, tree): leaf digest of the opened row, the sibling path, the cap
+//                  (k_fri_paths_bn128 for a verifier whose trees are PoseidonBN128's: DESIGN.md section 33)
 //   k_fri_queries  one wave per (proof, query): fri_combine_initial, the fold chain, the final polynomial; and one wave per
 //                  (proof, periodic column) of a verifier that has such columns
 // and the host driver from parsing to the verdicts.
@@ -51,7 +52,10 @@ struct Verifier {
     nlx_ctx* ctx = nullptr;
     const fpl::Layout* lay = nullptr;
     uint32_t log_n = 0, arity_bits = 0, pow_bits = 0, pp_stride = 0;
-    size_t w_caps = 0;                      // the first cap the proof carries; one per initial tree follows
+    // of the proof's Merkle trees: which path kernel runs and how a cap enters the transcript (observe_hash); lay->hasher, which
+    // tells the parser which words are digests, is the same value
+    uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS;
+    size_t w_caps = 0;                     // the first cap the proof carries; one per initial tree follows
     const uint64_t* ext_cap = nullptr;      // device: tree 0's cap where the proof does not carry it
     bool grouped_leaves = false;            // the format has leaf_group_cols, and leaf_group is this verifier's value (0: none)
     uint32_t leaf_group = 0;

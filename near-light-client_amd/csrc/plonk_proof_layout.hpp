@@ -44,8 +44,8 @@ struct Layout : fpl::Layout {
     size_t w_caps, w_openings[N_OPENINGS];   // word offsets in the staging buffer
 };
 
-// false: a shape no proof has
-inline bool make_layout(const Shape& s, Layout* out) {
+// false: a shape no proof has.  hasher: of the proof's trees (fpl::HASHER_*) - which words the parser checks as digests
+inline bool make_layout(const Shape& s, Layout* out, uint32_t hasher = fpl::HASHER_GOLDILOCKS) {
     Layout& l = *out;
     memset(&l, 0, sizeof l);
     l.sh = s;
@@ -59,8 +59,13 @@ inline bool make_layout(const Shape& s, Layout* out) {
         l.openings[c] = 8 * w;
         w += 2 * (size_t)counts[c];
     }
-    return fpl::fill(l, s.degree_bits, s.rate_bits, s.cap_height, s.arity_bits, s.final_poly_bits, s.n_queries, s.n_pis, N_TREES, tree_cols,
-                     w, 0);
+    if (!fpl::fill(l, s.degree_bits, s.rate_bits, s.cap_height, s.arity_bits, s.final_poly_bits, s.n_queries, s.n_pis, N_TREES, tree_cols,
+                   w, 0))
+        return false;
+    l.w_head_caps = l.w_caps;   // 0: the three caps open the proof
+    l.n_head_cap_words = 3 * l.cap_words;
+    l.hasher = hasher;
+    return true;
 }
 
 }  // namespace ppl

@@ -9,6 +9,10 @@
 //   k_plonk_constraints  one lane per proof, one block row per gate (then per challenge: the permutation argument, the lookup
 //                        argument): the constraints at zeta over F_p[X]/(X^2 - 7) (gate_eval_ext.hpp), on the openings
 //                        transposed to [word][proof]
+// A verifier carries its config's Hasher (nlx_verifier_create_hasher, nlx_verifier_from_circuit_hasher):
+// under NLX_HASHER_POSEIDON_BN128 the circuit digest and the caps enter the transcript through observe_hash, the parser checks
+// digests against r, and the path launch is fri_verify.hip's k_fri_paths_bn128.  The constraint launch, the FRI launch and the
+// judgement do not know of it.
 #include <algorithm>
 #include <memory>
 #include <vector>
@@ -135,6 +139,7 @@ struct nlx_verifier {
     // verifier-only data
     std::vector<uint64_t> cs_cap;
     uint64_t digest[4] = {0, 0, 0, 0};
+    uint32_t hasher = NLX_HASHER_POSEIDON_GOLDILOCKS;   // the config's Hasher: of every tree, the cap and the digest
     ppl::Layout lay{};
     // device: gates | k_is | cap, one block
     void* d_block = nullptr;
@@ -148,8 +153,9 @@ using namespace nlx::pv;
 
 // the host half of a verifier: the copies, the derived counts, the layout; gd: the gates as the kernels read them
 int32_t verifier_fill(nlx_ctx* ctx, nlx_verifier* v, const nlx_circuit_desc& d, const uint64_t* cap, const uint64_t digest[4],
-                      std::vector<GateDev>& gd) {
+                      uint32_t hasher, std::vector<GateDev>& gd) {
     v->ctx = ctx;
+    v->hasher = hasher;
     v->d = d;
     v->gates.assign(d.gates, d.gates + d.num_gates);
     v->k_is.assign(d.k_is, d.k_is + d.num_routed_wires);
@@ -189,8 +195,15 @@ int32_t verifier_fill(nlx_ctx* ctx, nlx_verifier* v, const nlx_circuit_desc& d, 
     }
     const size_t capw = (size_t)4 << d.cap_height;
     v->cs_cap.assign(cap, cap + capw);
-    for (uint64_t w : v->cs_cap)
-        if (w >= gl::P) return ctx->fail(NLX_E_RANGE, "a word of constants_sigmas_cap is not canonical");
+    if (hasher == NLX_HASHER_POSEIDON_BN128) {
+        // digests of this hasher: one integer below r each, whatever its words are against p
+        if (fpl::first_digest_not_below_r(v->cs_cap.data(), 0, capw) != capw)
+            return ctx->fail(NLX_E_RANGE, "a digest of constants_sigmas_cap is not below r");
+        if (!pbn::lt_r(digest[0], digest[1], digest[2], digest[3])) return ctx->fail(NLX_E_RANGE, "circuit_digest is not below r");
+    } else {
+        for (uint64_t w : v->cs_cap)
+            if (w >= gl::P) return ctx->fail(NLX_E_RANGE, "a word of constants_sigmas_cap is not canonical");
+    }
     memcpy(v->digest, digest, 32);
     memcpy(v->d.circuit_digest, digest, 32);
     ppl::Shape sh{};
@@ -198,17 +211,18 @@ int32_t verifier_fill(nlx_ctx* ctx, nlx_verifier* v, const nlx_circuit_desc& d, 
     sh.final_poly_bits = d.fri_final_poly_bits; sh.n_queries = d.fri_num_queries; sh.n_pis = d.num_public_inputs;
     sh.n_constants = v->n_consts_all; sh.n_sigmas = d.num_routed_wires; sh.n_wires = d.num_wires; sh.n_challenges = d.num_challenges;
     sh.n_partial = d.num_challenges * d.num_partial_products; sh.n_lookup_polys = v->n_lk_polys; sh.n_quotient = v->n_q;
-    if (!ppl::make_layout(sh, &v->lay) || v->lay.n_layers != v->n_fri_rounds)
+    if (!ppl::make_layout(sh, &v->lay, hasher) || v->lay.n_layers != v->n_fri_rounds)
         return ctx->fail(NLX_E_UNSUPPORTED, "the circuit's proofs have a shape the verifier does not take");
     if (d.num_gates + 2 * d.num_challenges > 65535) return ctx->fail(NLX_E_RANGE, "too many gate kinds");
     if (d.fri_num_queries == 0) return ctx->fail(NLX_E_RANGE, "a proof without FRI queries is not verified");
     return NLX_OK;
 }
 
-int32_t verifier_build(nlx_ctx* ctx, const nlx_circuit_desc& d, const uint64_t* cap, const uint64_t digest[4], nlx_verifier** out) {
+int32_t verifier_build(nlx_ctx* ctx, const nlx_circuit_desc& d, const uint64_t* cap, const uint64_t digest[4], uint32_t hasher,
+                       nlx_verifier** out) {
     std::unique_ptr<nlx_verifier> v(new nlx_verifier());
     std::vector<GateDev> gd;
-    NLX_RC(verifier_fill(ctx, v.get(), d, cap, digest, gd));
+    NLX_RC(verifier_fill(ctx, v.get(), d, cap, digest, hasher, gd));
     const size_t capw = (size_t)4 << d.cap_height;
     // device copies of what the kernels index by descriptor values
     (void)hipSetDevice(ctx->device);
@@ -233,7 +247,9 @@ int32_t verifier_build(nlx_ctx* ctx, const nlx_circuit_desc& d, const uint64_t* 
 }
 
 // the head of one proof's chain: the transcript up to the FRI alpha, the reduced openings, get_lut_poly, L_0(zeta).  w: the
-// staging copy; pp: PP_STRIDE words, zeroed
+// staging copy; pp: PP_STRIDE words, zeroed.  Rules 1 - 5 of DESIGN.md section 17: the circuit digest and every cap enter through
+// observe_hash - under BN128 five limbs a digest, each found below r by verifier_fill or the parser -, while the public-inputs
+// hash and the sponge stay Goldilocks under both configs.
 void transcript_head(const nlx_verifier* v, const uint64_t* w, uint64_t* pp, Challenger& ch) {
     const nlx_circuit_desc& d = v->d;
     const ppl::Layout& l = v->lay;
@@ -241,9 +257,9 @@ void transcript_head(const nlx_verifier* v, const uint64_t* w, uint64_t* pp, Cha
     const size_t capw = l.cap_words;
     const uint64_t* pis = w + l.w_public_inputs;
     hash_no_pad_host(pis, d.num_public_inputs, pp + PP_PIH);
-    ch.observe(v->digest, 4);
+    (void)observe_hash(v->hasher, ch, v->digest, 1);
     ch.observe(pp + PP_PIH, 4);
-    ch.observe(w + l.w_caps, capw);                                   // wires cap
+    (void)observe_hash(v->hasher, ch, w + l.w_caps, capw / 4);        // wires cap
     for (uint32_t i = 0; i < nc; i++) pp[PP_BETAS + i] = ch.challenge();
     for (uint32_t i = 0; i < nc; i++) pp[PP_GAMMAS + i] = ch.challenge();
     if (d.num_luts) {
@@ -264,9 +280,9 @@ void transcript_head(const nlx_verifier* v, const uint64_t* w, uint64_t* pp, Cha
                 pp[PP_LUT + ci * d.num_luts + t] = gl::mul(acc, gl::pow(dl, degree - len));
             }
     }
-    ch.observe(w + l.w_caps + capw, capw);                            // Zs / partial products cap
+    (void)observe_hash(v->hasher, ch, w + l.w_caps + capw, capw / 4);   // Zs / partial products cap
     for (uint32_t i = 0; i < nc; i++) pp[PP_ALPHAS + i] = ch.challenge();
-    ch.observe(w + l.w_caps + 2 * capw, capw);                        // quotient cap
+    (void)observe_hash(v->hasher, ch, w + l.w_caps + 2 * capw, capw / 4);   // quotient cap
     const gl::Ext zeta = draw_zeta(ch, pp, d.degree_bits);
     // the openings as the prover observed them: the zeta batch (constants .. zs, then partial products and quotient, then the
     // lookup polynomials), then the g zeta batch.  constants, sigmas, wires, zs are contiguous.
@@ -320,7 +336,7 @@ int32_t verify_batch(nlx_verifier* v, const uint8_t* const* proofs, const size_t
     ConsParams cp{};
     fill_cons_params(v, cp);
     Verifier fvv;
-    fvv.ctx = ctx; fvv.lay = &l;
+    fvv.ctx = ctx; fvv.lay = &l; fvv.hasher = v->hasher;
     fvv.log_n = d.degree_bits; fvv.arity_bits = d.fri_arity_bits; fvv.pow_bits = d.fri_pow_bits; fvv.pp_stride = PP_STRIDE;
     fvv.w_caps = l.w_caps; fvv.ext_cap = v->d_cs_cap;   // tree 0 is the circuit's own constants_sigmas
     // the zeta batch walks constants_sigmas, wires, the Zs and partial products, the quotient, then the lookup columns of the Zs
@@ -339,7 +355,7 @@ int32_t verify_batch(nlx_verifier* v, const uint8_t* const* proofs, const size_t
     run(2, v->n_zpp, nlk, 2, pow1);
     fvv.batch_shift = pow1;
     fvv.part_words = (size_t)cp.n_items * nc * 2;
-    fvv.name_paths = "plonk_verify_paths"; fvv.name_fri = "plonk_verify_fri";
+    fvv.name_paths = v->hasher == NLX_HASHER_POSEIDON_BN128 ? "plonk_verify_paths_bn128" : "plonk_verify_paths"; fvv.name_fri = "plonk_verify_fri";
     fvv.part_unwritten = "the constraint kernel left an item unwritten";
     fvv.head = [&](const uint64_t* w, uint64_t* pp, Challenger& ch) { transcript_head(v, w, pp, ch); };
     fvv.constraints = [&](const Device& dev) {
@@ -380,21 +396,32 @@ int32_t verify_batch(nlx_verifier* v, const uint8_t* const* proofs, const size_t
     return fv::verify_batch(fvv, call.base, proofs, lens, n_proofs, public_inputs, verdicts);
 }
 
+// nlx_verifier_create and nlx_verifier_create_hasher
+int32_t verifier_create(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants_sigmas_cap, const uint64_t digest[4],
+                        uint32_t hasher, nlx_verifier** out) {
+    if (!ctx) return NLX_E_INVAL;
+    if (!desc || !constants_sigmas_cap || !digest || !out || !desc->gates || !desc->k_is) return ctx->fail(NLX_E_INVAL, "NULL argument");
+    *out = nullptr;
+    NLX_RC(validate_circuit_desc(ctx, *desc, hasher));
+    bool zero = true;
+    for (int i = 0; i < 4; i++) zero = zero && desc->circuit_digest[i] == 0;
+    if (!zero && memcmp(desc->circuit_digest, digest, 32) != 0)
+        return ctx->fail(NLX_E_INVAL, "the descriptor's circuit_digest differs from the verifier-only data's");
+    return verifier_build(ctx, *desc, constants_sigmas_cap, digest, hasher, out);
+}
+
 }  // namespace
 
 extern "C" {
 
 int32_t nlx_verifier_create(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants_sigmas_cap,
                             const uint64_t digest[4], nlx_verifier** out) NLX_TRY {
-    if (!ctx) return NLX_E_INVAL;
-    if (!desc || !constants_sigmas_cap || !digest || !out || !desc->gates || !desc->k_is) return ctx->fail(NLX_E_INVAL, "NULL argument");
-    *out = nullptr;
-    NLX_RC(validate_circuit_desc(ctx, *desc, NLX_HASHER_POSEIDON_GOLDILOCKS));
-    bool zero = true;
-    for (int i = 0; i < 4; i++) zero = zero && desc->circuit_digest[i] == 0;
-    if (!zero && memcmp(desc->circuit_digest, digest, 32) != 0)
-        return ctx->fail(NLX_E_INVAL, "the descriptor's circuit_digest differs from the verifier-only data's");
-    return verifier_build(ctx, *desc, constants_sigmas_cap, digest, out);
+    return verifier_create(ctx, desc, constants_sigmas_cap, digest, NLX_HASHER_POSEIDON_GOLDILOCKS, out);
+} NLX_CATCH(ctx)
+
+int32_t nlx_verifier_create_hasher(nlx_ctx* ctx, const nlx_circuit_desc* desc, const uint64_t* constants_sigmas_cap,
+                                   const uint64_t digest[4], uint32_t hasher, nlx_verifier** out) NLX_TRY {
+    return verifier_create(ctx, desc, constants_sigmas_cap, digest, hasher, out);
 } NLX_CATCH(ctx)
 
 int32_t nlx_verifier_from_circuit(const nlx_circuit* c, nlx_verifier** out) NLX_TRY {
@@ -406,8 +433,25 @@ int32_t nlx_verifier_from_circuit(const nlx_circuit* c, nlx_verifier** out) NLX_
     const nlx_circuit_desc& d = circuit_desc(c);
     std::vector<uint64_t> cap((size_t)4 << d.cap_height);
     NLX_RC(nlx_circuit_constants_sigmas_cap(c, cap.data()));
-    return verifier_build(ctx, d, cap.data(), d.circuit_digest, out);
+    return verifier_build(ctx, d, cap.data(), d.circuit_digest, NLX_HASHER_POSEIDON_GOLDILOCKS, out);
 } NLX_CATCH(c ? circuit_ctx(c) : nullptr)
+
+int32_t nlx_verifier_from_circuit_hasher(const nlx_circuit* c, uint32_t hasher, nlx_verifier** out) NLX_TRY {
+    if (!c || !out) return NLX_E_INVAL;
+    *out = nullptr;
+    nlx_ctx* ctx = circuit_ctx(c);
+    if (hasher != NLX_HASHER_POSEIDON_GOLDILOCKS && hasher != NLX_HASHER_POSEIDON_BN128) return ctx->fail(NLX_E_RANGE, "unknown hasher %u", hasher);
+    if ((uint32_t)nlx_circuit_hasher(c) != hasher)
+        return ctx->fail(NLX_E_INVAL, "the circuit was built under hasher %d, not %u", nlx_circuit_hasher(c), hasher);
+    const nlx_circuit_desc& d = circuit_desc(c);
+    std::vector<uint64_t> cap((size_t)4 << d.cap_height);
+    NLX_RC(nlx_circuit_constants_sigmas_cap(c, cap.data()));
+    return verifier_build(ctx, d, cap.data(), d.circuit_digest, hasher, out);
+} NLX_CATCH(c ? circuit_ctx(c) : nullptr)
+
+int32_t nlx_verifier_hasher(const nlx_verifier* v) NLX_TRY {
+    return v ? (int32_t)v->hasher : NLX_E_INVAL;
+} NLX_CATCH_VALUE(nullptr, NLX_E_INVAL)
 
 void nlx_verifier_destroy(nlx_verifier* v) NLX_TRY {
     if (!v) return;

@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include "commit.hpp"
 #include "gl.hpp"
-#include "poseidon_bn128.hpp"
+#include "poseidon_bn128_path.hpp"
 
 namespace nlx {
 
@@ -232,6 +232,41 @@ __global__ __launch_bounds__(256) void k_pbn_fri_leaves_quad(const uint64_t* __r
     if (live && q == 0) pbn_store(digests, leaf, s);
 }
 
+// verify_merkle_proof_to_cap of n (leaf, index, path) triples against one cap: one quad of lanes each, the quad's work being
+// pbn::quad_merkle_path - the code the proof verifier's path kernel runs (fri_verify.hip).  leaves [n][leaf_len] (taken mod p),
+// indices [n] (below 2^(path_len + cap_height): the host has checked), siblings [n][path_len][4] and cap [2^cap_height][4]
+// (digests below r: the host has checked).  A leaf of <= 4 words is its own digest (hash_or_noop's no-op branch, its value below
+// r by the host's check): it starts on lane 0 and nothing is absorbed.  ok[i] = 1: the path reaches the cap.  Spare quads redo
+// the last item and store nothing.
+__global__ __launch_bounds__(64) void k_pbn_merkle_verify(const uint64_t* __restrict__ leaves, uint32_t n, uint32_t leaf_len,
+                                                          const uint64_t* __restrict__ indices, const uint64_t* __restrict__ siblings,
+                                                          uint32_t path_len, const uint64_t* __restrict__ cap, uint8_t* __restrict__ ok) {
+    const uint32_t q = threadIdx.x & 3;
+    const uint32_t raw = blockIdx.x * 16 + (threadIdx.x >> 2);
+    const bool live = raw < n;
+    const uint32_t item = live ? raw : n - 1;
+    const uint64_t* row = leaves + (size_t)item * leaf_len;
+    const uint64_t index = indices[item];
+    Fe s = f29::zero();
+    if (leaf_len <= 4) {   // kernel-uniform
+        uint64_t e[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 4; c++)
+            if ((uint32_t)c < leaf_len) e[c] = gl::canon(row[c]);
+        const Fe d = pbn::from_words(e[0], e[1], e[2], e[3]);
+#pragma unroll
+        for (int l = 0; l < pbn::NL; l++) s.v[l] = q == 0 ? d.v[l] : 0u;
+    }
+    const pbn::QuadRow qrow = pbn::quad_row(q);
+    // only the low path_len bits of the index steer the path (path_len <= 31)
+    s = pbn::quad_merkle_path(s, row, leaf_len <= 4 ? 0 : leaf_len, (uint32_t)index, siblings + (size_t)item * path_len * 4, path_len, q, qrow);
+    uint64_t d[4];
+    pbn::to_words(s, d);
+    const uint64_t* c = cap + (size_t)(index >> path_len) * 4;
+    const bool good = d[0] == c[0] && d[1] == c[1] && d[2] == c[2] && d[3] == c[3];
+    if (live && q == 0) ok[item] = good ? 1 : 0;
+}
+
 // ---- host launchers (stream-ordered, no synchronisation); `bad`: a device word the caller zeroed ----
 static unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -360,6 +395,52 @@ int32_t nlx_poseidon_bn128_merkle_build(nlx_ctx* ctx, const uint64_t* leaves, si
         if (!rc && e != hipSuccess) rc = ctx->hip_fail(e, "hipStreamSynchronize");
     }
     return rc;
+} NLX_CATCH(ctx)
+
+int32_t nlx_poseidon_bn128_merkle_verify_batch(nlx_ctx* ctx, const uint64_t* leaves, size_t n, size_t leaf_len, const uint64_t* indices,
+                                               const uint64_t* siblings, uint32_t path_len, const uint64_t* cap, uint32_t cap_height,
+                                               uint8_t* ok_out) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (n == 0) return NLX_OK;
+    if (!indices || !cap || !ok_out || (!leaves && leaf_len) || (!siblings && path_len)) return ctx->fail(NLX_E_INVAL, "NULL buffer");
+    if (is_device_ptr(leaves) || is_device_ptr(indices) || is_device_ptr(siblings) || is_device_ptr(cap) || is_device_ptr(ok_out))
+        return ctx->fail(NLX_E_INVAL, "nlx_poseidon_bn128_merkle_verify_batch takes host arrays");
+    if (leaf_len > 0xFFFFFFFFull) return ctx->fail(NLX_E_RANGE, "leaf_len too large");
+    if (n > 0x0FFFFFFFull) return ctx->fail(NLX_E_RANGE, "too many paths in one call");
+    if (path_len > 31 || cap_height > 31 || path_len + cap_height > 32) return ctx->fail(NLX_E_RANGE, "a tree of more than 2^32 leaves");
+    // the range rules, on the host: what the device indexes with, and every value that must be a digest
+    for (size_t i = 0; i < n; i++)
+        if (indices[i] >> (path_len + cap_height)) return ctx->fail(NLX_E_RANGE, "index %llu is not below 2^(path_len + cap_height)", (unsigned long long)i);
+    const size_t n_cap = (size_t)1 << cap_height;
+    for (size_t i = 0; i < n_cap; i++)
+        if (!bnf::below_mod<bnf::RP>(cap + 4 * i)) return ctx->fail(NLX_E_RANGE, "cap entry %llu is not below r", (unsigned long long)i);
+    for (size_t i = 0; i < n * path_len; i++)
+        if (!bnf::below_mod<bnf::RP>(siblings + 4 * i))
+            return ctx->fail(NLX_E_RANGE, "sibling %llu of path %llu is not below r", (unsigned long long)(i % path_len), (unsigned long long)(i / path_len));
+    if (leaf_len <= 4)   // hash_or_noop's no-op branch, as nlx_poseidon_bn128_hash_rows: the packed row is the digest
+        for (size_t i = 0; i < n; i++) {
+            uint64_t e[4] = {0, 0, 0, 0};
+            for (size_t c = 0; c < leaf_len; c++) e[c] = gl::canon(leaves[i * leaf_len + c]);
+            if (!bnf::below_mod<bnf::RP>(e)) return ctx->fail(NLX_E_RANGE, "leaf %llu packs to a value that is not below r", (unsigned long long)i);
+        }
+    (void)hipSetDevice(ctx->device);
+    Staged d_leaves(ctx, leaves, n * leaf_len * 8, true, false);
+    Staged d_idx(ctx, indices, n * 8, true, false);
+    Staged d_sib(ctx, siblings, n * path_len * 32, true, false);
+    Staged d_cap(ctx, cap, n_cap * 32, true, false);
+    Staged d_ok(ctx, ok_out, n, false, true);
+    for (const Staged* st : {&d_leaves, &d_idx, &d_sib, &d_cap, &d_ok})
+        if (st->status) return st->status;
+    const size_t chunks = leaf_len <= 4 ? 0 : (leaf_len + pbn::CHUNK - 1) / pbn::CHUNK;
+    ctx->begin_kernel("merkle_verify_bn128", 8.0 * n * (leaf_len + 4.0 * path_len), (double)n * (double)(chunks + path_len));
+    hipLaunchKernelGGL(k_pbn_merkle_verify, dim3((unsigned)((n + 15) / 16)), dim3(64), 0, ctx->stream, d_leaves.as<uint64_t>(), (uint32_t)n,
+                       (uint32_t)leaf_len, d_idx.as<uint64_t>(), d_sib.as<uint64_t>(), path_len, d_cap.as<uint64_t>(), d_ok.as<uint8_t>());
+    ctx->end_kernel();
+    NLX_HIP(ctx, hipGetLastError());
+    const int32_t rc = d_ok.finish();
+    if (rc) return rc;
+    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NLX_OK;
 } NLX_CATCH(ctx)
 
 }  // extern "C"

@@ -179,7 +179,9 @@ def proof_layout(circuit):
     "lookup_zs_next", "partial_products", "quotient", "fri_caps" ("fri_cap"[k]), "query"[q] = {"row"[t], "path_len"[t], "path"[t]
     for the trees t = constants_sigmas, wires, zs_partial, quotient, "layer"[k] = {"evals", "path_len", "path"}}, "final_poly",
     "pow_witness", "num_public_inputs", "public_inputs" - and "total", the length of the proof; "tree_cols", "n_layers" and
-    "arity" describe the shape (csrc/plonk_proof_layout.hpp)."""
+    "arity" describe the shape (csrc/plonk_proof_layout.hpp).  "digests" lists the spans that hold Merkle digests, in proof
+    order - the three caps, the FRI caps, every path's siblings: under the PoseidonBN128 config those are checked 32 bytes at a
+    time against r, every other word against p."""
     from .stark import _Span, _Taker, _layout_queries_and_tail
     d = circuit
     if hasattr(d, "_desc"):
@@ -201,6 +203,10 @@ def proof_layout(circuit):
     out["openings"] = _Span((out["constants"][0], take.at - out["constants"][0]))
     _layout_queries_and_tail(out, take, d, tree_cols)
     out["total"] = take.at
+    dg = list(out["cap"]) + list(out["fri_cap"])
+    for q in out["query"]:
+        dg += list(q["path"]) + [ly["path"] for ly in q["layer"]]
+    out["digests"] = [sp for sp in dg if sp[1]]
     return out
 
 
@@ -209,12 +215,19 @@ class VerifierData:
     constants_sigmas_cap and circuit_digest.  Needs none of the prover's tables.  verify / verify_many return Verdicts
     (stark.Verdict: .ok, .reason_name, .message, .raise_if_rejected())."""
 
-    def __init__(self, ctx, desc, constants_sigmas_cap, circuit_digest, _from_circuit=None):
+    def __init__(self, ctx, desc, constants_sigmas_cap, circuit_digest, hasher="poseidon_goldilocks", _from_circuit=None):
+        """hasher="poseidon_bn128": the verifying key of a circuit under plonky2x's PoseidonBN128GoldilocksConfig
+        (nlx_verifier_create_hasher) - cap and digest are digests over BN254 Fr, four little-endian words each"""
+        from .batch import _hasher_id
         self.ctx = ctx
         self._desc = desc   # keeps gates / k_is / tables alive while the library copies them
         h = ctypes.c_void_p()
+        hid = _hasher_id(hasher)
         if _from_circuit is not None:
-            ctx.check(dll.nlx_verifier_from_circuit(_from_circuit, ctypes.byref(h)))
+            if hid == 0:   # today's entry, exactly
+                ctx.check(dll.nlx_verifier_from_circuit(_from_circuit, ctypes.byref(h)))
+            else:
+                ctx.check(dll.nlx_verifier_from_circuit_hasher(_from_circuit, hid, ctypes.byref(h)))
         else:
             cap = np.ascontiguousarray(constants_sigmas_cap, dtype=np.uint64).reshape(-1)
             if cap.size != 4 << desc.cap_height:
@@ -222,10 +235,21 @@ class VerifierData:
             dig = np.ascontiguousarray(circuit_digest, dtype=np.uint64).reshape(-1)
             if dig.size != 4:
                 raise ValueError("circuit_digest must hold 4 words")
-            ctx.check(dll.nlx_verifier_create(ctx.handle, ctypes.byref(desc), ptr(cap), ptr(dig), ctypes.byref(h)))
+            if hid == 0:
+                ctx.check(dll.nlx_verifier_create(ctx.handle, ctypes.byref(desc), ptr(cap), ptr(dig), ctypes.byref(h)))
+            else:
+                ctx.check(dll.nlx_verifier_create_hasher(ctx.handle, ctypes.byref(desc), ptr(cap), ptr(dig), hid, ctypes.byref(h)))
         self.handle = h
         self.num_public_inputs = desc.num_public_inputs
         ctx._adopt(self)
+
+    @property
+    def hasher(self):
+        """"poseidon_goldilocks" or "poseidon_bn128" (nlx_verifier_hasher)"""
+        from .batch import HASHERS
+        hid = dll.nlx_verifier_hasher(self.handle)
+        self.ctx.check(min(hid, 0))
+        return {v: k for k, v in HASHERS.items()}[hid]
 
     @property
     def proof_bytes(self):
@@ -324,21 +348,24 @@ class CircuitData:
             rep.message = dll.nlx_last_error(self.ctx.handle).decode()
         return rep
 
-    def verifier_data(self):
-        """the circuit's VerifierData (nlx_verifier_from_circuit), made on first use and kept; NlxError NLX_E_UNSUPPORTED for a
-        circuit under the PoseidonBN128 config"""
-        if getattr(self, "_verifier", None) is None or not self._verifier.handle:
-            self._verifier = VerifierData(self.ctx, self._desc, None, None, _from_circuit=self.handle)
-        return self._verifier
+    def verifier_data(self, hasher="poseidon_goldilocks"):
+        """the circuit's VerifierData under the config the caller expects, made on first use and kept.  Without an argument it
+        is nlx_verifier_from_circuit: NlxError NLX_E_UNSUPPORTED for a circuit under the PoseidonBN128 config.  With the
+        circuit's own hasher (cd.verifier_data(cd.hasher)) it is nlx_verifier_from_circuit_hasher; NLX_E_INVAL for the other."""
+        kept = self.__dict__.setdefault("_verifiers", {})
+        if kept.get(hasher) is None or not kept[hasher].handle:
+            kept[hasher] = VerifierData(self.ctx, self._desc, None, None, hasher=hasher, _from_circuit=self.handle)
+        return kept[hasher]
 
     def verify(self, proof, public_inputs=None):
-        """does `proof` verify on the device, and which check breaks if not: cd.verify(proof).raise_if_rejected()"""
-        return self.verifier_data().verify(proof, public_inputs)
+        """does `proof` verify on the device, and which check breaks if not: cd.verify(proof).raise_if_rejected().  The
+        verifier is the one of the circuit's own hasher."""
+        return self.verifier_data(self._hasher).verify(proof, public_inputs)
 
     def verify_many(self, proofs, public_inputs=None):
         """a list of proofs of this circuit in one pass over the GPU; a Verdict per proof"""
         proofs = list(proofs)
-        return self.verifier_data().verify_many(proofs, public_inputs) if proofs else []
+        return self.verifier_data(self._hasher).verify_many(proofs, public_inputs) if proofs else []
 
     # ---- stage-level calls (the fine seam) ----
     def constants_sigmas_batch(self):
@@ -386,9 +413,8 @@ class CircuitData:
         return [(names[i].decode(), ms[i]) for i in range(n.value)]
 
     def close(self):
-        if getattr(self, "_verifier", None) is not None:
-            self._verifier.close()
-            self._verifier = None
+        for v in self.__dict__.pop("_verifiers", {}).values():
+            v.close()
         if self.handle and self.ctx.handle:
             dll.nlx_circuit_destroy(self.handle)
         self.handle = None

@@ -6,6 +6,7 @@ cd = nlx.CircuitData.from_synthetic(ctx, syn)
 proof = cd.prove(syn.wires, syn.public_inputs)
 cd.check_witness(syn.wires, syn.public_inputs).raise_if_unsatisfied()
 cd.verify(proof).raise_if_rejected()
+bn = nlx.CircuitData.from_synthetic(ctx, syn, hasher="poseidon_bn128"); bn.verify(bn.prove(syn.wires, syn.public_inputs)).raise_if_rejected()   # the same under plonky2x's PoseidonBN128GoldilocksConfig
 print("plonky2 proof", len(proof))
 S = nlx.stark
 air = S.Air(2, 3)
