@@ -275,7 +275,10 @@ int32_t nlx_bn254_plonk_quotient(nlx_ctx* ctx, const nlx_bn254_plonk_quotient_ar
  * z(w^(i+1)) = z(w^i) prod_j (w_j(i) + beta id_j(i) + gamma) / (w_j(i) + beta s_j(i) + gamma), id = (w^i, k1 w^i, k2 w^i).
  * One inversion per 64 rows (batch inversion), the running product as a multi-level scan.  All inputs n x 4 words on H in
  * natural order, host or device; beta, gamma, k1, k2 host; z_out: n x 4 words, host or device.  *closes (may be NULL): 1 if
- * the product returns to 1 after the last row - it does exactly when the wires respect the permutation. */
+ * the product returns to 1 after the last row - it does exactly when the wires respect the permutation.
+ * 1 / 0 := 0, as gnark's BatchInvert has it: a row whose denominator vanishes contributes the ratio 0 and nothing else, so z is
+ * exact up to and including that row, 0 after it, and *closes is 0.  beta, gamma, k1, k2 are fr.Element words: one that is not
+ * below r -> NLX_E_RANGE, as for nlx_bn254_plonk_quotient. */
 int32_t nlx_bn254_plonk_grand_product(nlx_ctx* ctx, uint32_t log_n, const uint64_t* l, const uint64_t* r, const uint64_t* o,
                                       const uint64_t* s1, const uint64_t* s2, const uint64_t* s3, const uint64_t beta[4],
                                       const uint64_t gamma[4], const uint64_t k1[4], const uint64_t k2[4], uint64_t* z_out,
@@ -297,6 +300,17 @@ int32_t nlx_bn254_groth16_quotient(nlx_ctx* ctx, uint32_t log_n, const uint64_t*
  * m - 1 points of the SRS (G1Affine words as for nlx_bn254_msm_g1; host or device).  2 <= m <= 2^28. */
 int32_t nlx_bn254_kzg_open(nlx_ctx* ctx, const uint64_t* coeffs, uint64_t m, const uint64_t zeta[4], const uint64_t* srs,
                            uint64_t y_out[4], uint64_t* quotient_out, uint64_t proof_out[8]);
+/* Self-test entry for the nine-limb loose field every BN254 kernel computes on (csrc/bn254_f29.hpp), one lane per case.
+ * modulus: the base field q or the scalar field r.  a, b: n x 9 u32 raw limbs of 29 bits (value = sum l_i 2^(29 i)), host or
+ * device; limbs 0 .. 7 below 2^29, limb 8 takes what is left of a value below 2^261 - NOT reduced first, so the operand limits
+ * the header states can be reached.  out: n x NLX_BN254_F29_OPS_WORDS u32 (host or device), per case eleven results of nine
+ * limbs each, in this order: mul(a, b), add(a, b), sub<4>(a, b), sub<8>(a, b), tighten(a), canonical(a), is_zero_mod(a) (0 or 1
+ * in limb 0), from_mont256(to_words256(a)), from_words256(to_words256(a)), to_canonical256(a) (its words re-sliced), x32(a).
+ * A result is meaningful where the case's operands lie inside that function's bounds. */
+#define NLX_BN254_MODULUS_Q 0u
+#define NLX_BN254_MODULUS_R 1u
+#define NLX_BN254_F29_OPS_WORDS 99
+int32_t nlx_bn254_f29_ops(nlx_ctx* ctx, uint32_t modulus, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
 
 /* ---- f.4, the Groth16 half: whole proofs from a proving key resident in HBM (gnark backend/groth16/bn254 ProvingKey and Prove;
  * Go, not in the reference: the layout and the rules are recalled from gnark v0.9, parity with gnark-produced bytes unpinned -

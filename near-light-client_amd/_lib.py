@@ -98,6 +98,7 @@ SIGNATURES = {
     "nlx_bn254_groth16_quotient": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 5),
     "nlx_bn254_kzg_open": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_bn254_f29_ops": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "nlx_bn254_groth16_key_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
     "nlx_bn254_groth16_key_destroy": (None, [ctypes.c_void_p]),
     "nlx_bn254_groth16_key_info": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),

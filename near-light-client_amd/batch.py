@@ -422,6 +422,26 @@ def bn254_kzg_open(ctx, coeffs, zeta, srs=None, want_quotient=True):
     return y, q, proof
 
 
+BN254_F29_OPS = ("mul", "add", "sub4", "sub8", "tighten", "canonical", "iszero", "frommont", "words", "tocanon", "x32")
+
+
+def bn254_f29_ops(ctx, modulus, a, b):
+    """csrc/bn254_f29.hpp on the device at given limbs (nlx_bn254_f29_ops), one lane per case.  modulus: "q" or "r"; a, b: (n, 9)
+    uint32 raw 29-bit limbs, limbs 0 .. 7 below 2^29, NOT reduced first.  Returns (n, 11, 9) uint32: per case the nine limbs of
+    each BN254_F29_OPS result (the header lists what each one is and on which operands it is meaningful)."""
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    if a.ndim != 2 or a.shape[1] != 9 or a.shape != b.shape:
+        raise ValueError("a and b must both have shape (n, 9)")
+    if modulus not in ("q", "r"):
+        raise ValueError("modulus must be 'q' or 'r'")
+    if a.size and max(int(a[:, :8].max()), int(b[:, :8].max())) >> 29:
+        raise ValueError("limbs 0 .. 7 must be below 2^29")
+    out = np.zeros((a.shape[0], len(BN254_F29_OPS), 9), dtype=np.uint32)
+    ctx.check(dll.nlx_bn254_f29_ops(ctx.handle, 0 if modulus == "q" else 1, a.ctypes.data, b.ctypes.data, a.shape[0], out.ctypes.data))
+    return out
+
+
 def bn254_g1_sum(points):
     """The sum of G1Affine points, (n, 8) uint64 words each (host): joins the partial MSMs of several GPUs."""
     a = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)

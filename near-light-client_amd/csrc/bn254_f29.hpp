@@ -14,6 +14,7 @@
 //   add            any two values whose sum is < 2^258                      -> the plain sum, limbs normalised
 //   sub<K>(a, b)   a + K q - b for K q >= the bound of b (K = 4: b < 2^255, K = 8: b < 3 * 2^255)
 //   tighten        any value < 2^258                                        -> the same residue, < 1.1 q
+//   x32            any value < 2^258                                        -> 32 times the residue, < 1.1 q
 // The point formulas in bn254_msm.hip state the bound of every intermediate.
 #pragma once
 #include <cstdint>
@@ -175,6 +176,24 @@ F29_HD Fe tighten(const Fe& a) {
     }
     r.v[NL - 1] = (uint32_t)((int64_t)a.v[NL - 1] - (int64_t)((uint64_t)t * M::p(NL - 1)) + c);
     return r;
+}
+
+// a 2^K as an integer, limbs normalised (the caller keeps it below 2^258)
+template <int K>
+F29_HD Fe shl(const Fe& a) {
+    Fe r;
+    r.v[0] = (a.v[0] << K) & MASK;
+#pragma unroll
+    for (int i = 1; i < NL - 1; i++) r.v[i] = ((a.v[i] << K) | (a.v[i - 1] >> (LB - K))) & MASK;
+    r.v[NL - 1] = (a.v[NL - 1] << K) | (a.v[NL - 2] >> (LB - K));
+    return r;
+}
+// x 2^5 for any value < 2^258: what puts a product of two 2^256-Montgomery values (x y 2^251) back into that form.  A value
+// below 1.1 p times 4 (< 2^256.2), tightened, times 8 (< 2^257.2), tightened: both shifts stay below tighten's 2^258
+template <class M = QMod>
+F29_HD Fe x32(const Fe& a) {
+    const Fe t = tighten<M>(shl<2>(tighten<M>(a)));
+    return tighten<M>(shl<3>(t));
 }
 
 // a = 0 mod p, for any value < 2^258

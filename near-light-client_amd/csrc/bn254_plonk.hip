@@ -43,20 +43,8 @@ __device__ __forceinline__ void st(uint64_t* p, size_t i, const Fe& v) { f29::st
 __device__ __forceinline__ Fe mul(const Fe& a, const Fe& b) { return f29::mul<RM>(a, b); }
 __device__ __forceinline__ Fe add(const Fe& a, const Fe& b) { return f29::tighten<RM>(f29::add(a, b)); }
 __device__ __forceinline__ Fe sub(const Fe& a, const Fe& b) { return f29::tighten<RM>(f29::sub<4, RM>(a, b)); }
-template <int K>
-__device__ __forceinline__ Fe shl(const Fe& a) {   // a 2^K as an integer (the caller keeps it below 2^258)
-    Fe r;
-    r.v[0] = (a.v[0] << K) & f29::MASK;
-#pragma unroll
-    for (int i = 1; i < f29::NL - 1; i++) r.v[i] = ((a.v[i] << K) | (a.v[i - 1] >> (f29::LB - K))) & f29::MASK;
-    r.v[f29::NL - 1] = (a.v[f29::NL - 1] << K) | (a.v[f29::NL - 2] >> (f29::LB - K));
-    return r;
-}
-// x 2^5: D x D products come out as x y 2^251; a value below 1.1 r times 4, tightened, times 8, tightened
-__device__ __forceinline__ Fe x32(const Fe& a) {
-    const Fe t = f29::tighten<RM>(shl<2>(f29::tighten<RM>(a)));
-    return f29::tighten<RM>(shl<3>(t));
-}
+// x 2^5: D x D products come out as x y 2^251 (f29::x32: times 4, tightened, times 8, tightened)
+__device__ __forceinline__ Fe x32(const Fe& a) { return f29::x32<RM>(a); }
 __device__ __forceinline__ Fe mul_dd(const Fe& a, const Fe& b) { return x32(mul(a, b)); }   // D x D -> D
 __device__ __forceinline__ Fe one_i() { return f29::one<RM>(); }
 __device__ __forceinline__ Fe one_d() {   // 2^256 mod r
@@ -314,10 +302,13 @@ __global__ __launch_bounds__(64) void k_gp_ratios(GrandProductParams p) {
         Fe d = mul_dd(add(add(ld(p.l, i), mul(ld(p.s1, i), beta_i)), gamma), add(add(ld(p.r, i), mul(ld(p.s2, i), beta_i)), gamma));
         return x32(mul_dd(d, add(add(ld(p.o, i), mul(ld(p.s3, i), beta_i)), gamma)));
     };
+    // 1 / 0 := 0 (gnark's BatchInvert): a zero denominator stands as 1 in the run's product, so that the other rows' inverses
+    // stay exact, and its own ratio is 0
     Fe acc = one_i();
 #pragma unroll 1
     for (size_t i = i0; i < i1; i++) {
-        acc = mul(acc, den_of(i));
+        const Fe d = den_of(i);
+        acc = mul(acc, f29::is_zero_mod<RM>(d) ? one_i() : d);
         if (i + 1 < i1) st(p.z, i + 1, acc);   // prefix product up to row i, parked where row i's ratio will go
     }
     Fe inv = inv_i(acc);
@@ -326,8 +317,10 @@ __global__ __launch_bounds__(64) void k_gp_ratios(GrandProductParams p) {
 #pragma unroll 1
     for (size_t i = i1; i-- > i0;) {
         const Fe prev = i > i0 ? ld(p.z, i) : one_i();   // prefix product up to row i - 1
-        const Fe dinv = mul(inv, prev);
-        inv = mul(inv, den_of(i));
+        const Fe d = den_of(i);
+        const bool zero = f29::is_zero_mod<RM>(d);
+        const Fe dinv = zero ? f29::zero() : mul(inv, prev);
+        inv = mul(inv, zero ? one_i() : d);
         Fe num = mul_dd(add(add(ld(p.l, i), mul(beta, x)), gamma), add(add(ld(p.r, i), mul(bk1, x)), gamma));
         num = mul_dd(num, add(add(ld(p.o, i), mul(bk2, x)), gamma));
         const Fe ratio = mul(num, dinv);       // D x I -> D; the scan wants I-form
@@ -402,6 +395,33 @@ __global__ __launch_bounds__(256) void k_lincomb(LincombParams p) {
     Fe acc = f29::zero();
     for (uint32_t t = 0; t < p.n_terms; t++) acc = add(acc, mul(ld(p.polys[t], i), ld(p.sc_i, t)));
     st(p.out, i, acc);
+}
+
+// ---- bn254_f29.hpp at given limbs (self-test entry nlx_bn254_f29_ops): one lane per case, every function on the case's
+// operands, each result as nine limbs.  The operands are raw limbs, so the loose values the kernels above never meet through the
+// public entries (those reduce first) can be passed. ----
+constexpr uint32_t F29_OPS_WORDS = NLX_BN254_F29_OPS_WORDS;
+static_assert(F29_OPS_WORDS == 11 * f29::NL, "output layout");
+template <class M>
+__global__ __launch_bounds__(64) void k_f29_ops(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, size_t n, uint32_t* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    Fe x, y;
+#pragma unroll
+    for (int i = 0; i < f29::NL; i++) { x.v[i] = a[t * f29::NL + i]; y.v[i] = b[t * f29::NL + i]; }
+    uint32_t w[8], c[8];
+    f29::to_words256(x, w);
+    f29::to_canonical256<M>(x, c);
+    Fe zf = f29::zero();
+    zf.v[0] = f29::is_zero_mod<M>(x) ? 1u : 0u;
+    const Fe res[11] = {f29::mul<M>(x, y), f29::add(x, y), f29::sub<4, M>(x, y), f29::sub<8, M>(x, y), f29::tighten<M>(x), f29::canonical<M>(x), zf,
+                        f29::from_mont256<M>(w), f29::from_words256(w), f29::from_words256(c), f29::x32<M>(x)};
+    uint32_t* o = out + t * F29_OPS_WORDS;
+#pragma unroll
+    for (int k = 0; k < 11; k++) {
+#pragma unroll
+        for (int i = 0; i < f29::NL; i++) o[k * f29::NL + i] = res[k].v[i];
+    }
 }
 
 }  // namespace bnp
@@ -565,6 +585,26 @@ int32_t quotient_chain(nlx_ctx* ctx, const QuotientIn& q, uint64_t* t_out, size_
 
 extern "C" {
 
+int32_t nlx_bn254_f29_ops(nlx_ctx* ctx, uint32_t modulus, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out) NLX_TRY {
+    if (!ctx) return NLX_E_INVAL;
+    if (!a || !b || !out) return ctx->fail(NLX_E_INVAL, "NULL buffer");
+    if (modulus != NLX_BN254_MODULUS_Q && modulus != NLX_BN254_MODULUS_R) return ctx->fail(NLX_E_RANGE, "modulus is NLX_BN254_MODULUS_Q or NLX_BN254_MODULUS_R");
+    if (n == 0) return NLX_OK;
+    if (n > (size_t)1 << 24) return ctx->fail(NLX_E_RANGE, "n must be <= 2^24");
+    (void)hipSetDevice(ctx->device);
+    Staged sa(ctx, a, n * f29::NL * 4, true, false), sb(ctx, b, n * f29::NL * 4, true, false), so(ctx, out, n * bnp::F29_OPS_WORDS * 4, false, true);
+    if (sa.status) return sa.status;
+    if (sb.status) return sb.status;
+    if (so.status) return so.status;
+    const dim3 grid((unsigned)((n + 63) / 64));
+    if (modulus == NLX_BN254_MODULUS_Q) hipLaunchKernelGGL(bnp::k_f29_ops<f29::QMod>, grid, dim3(64), 0, ctx->stream, sa.as<uint32_t>(), sb.as<uint32_t>(), n, so.as<uint32_t>());
+    else hipLaunchKernelGGL(bnp::k_f29_ops<f29::RMod>, grid, dim3(64), 0, ctx->stream, sa.as<uint32_t>(), sb.as<uint32_t>(), n, so.as<uint32_t>());
+    int32_t rc = so.finish();
+    if (rc) return rc;
+    NLX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return NLX_OK;
+} NLX_CATCH(ctx)
+
 int32_t nlx_bn254_plonk_grand_product(nlx_ctx* ctx, uint32_t log_n, const uint64_t* l, const uint64_t* r, const uint64_t* o,
                                       const uint64_t* s1, const uint64_t* s2, const uint64_t* s3, const uint64_t beta[4],
                                       const uint64_t gamma[4], const uint64_t k1[4], const uint64_t k2[4], uint64_t* z_out,
@@ -573,6 +613,8 @@ int32_t nlx_bn254_plonk_grand_product(nlx_ctx* ctx, uint32_t log_n, const uint64
     if (!l || !r || !o || !s1 || !s2 || !s3 || !beta || !gamma || !k1 || !k2 || !z_out) return ctx->fail(NLX_E_INVAL, "NULL argument");
     if (log_n < 1 || log_n > 28) return ctx->fail(NLX_E_RANGE, "log_n must be in [1, 28]");
     if (is_device_ptr(beta) || is_device_ptr(gamma) || is_device_ptr(k1) || is_device_ptr(k2)) return ctx->fail(NLX_E_INVAL, "the challenges and shifts are host values");
+    for (const uint64_t* sc : {beta, gamma, k1, k2})
+        if (!bnf::below_mod<bnf::RP>(sc)) return ctx->fail(NLX_E_RANGE, "a challenge or shift is not below r (fr.Element words are residues)");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     const size_t n = (size_t)1 << log_n;

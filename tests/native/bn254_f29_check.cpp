@@ -53,6 +53,7 @@ static int run(const char* op, const Fe& x, const Fe& y) {
     else if (!strcmp(op, "sub8")) print(sub<8, M>(x, y));
     else if (!strcmp(op, "tighten")) print(tighten<M>(x));
     else if (!strcmp(op, "canonical")) print(canonical<M>(x));
+    else if (!strcmp(op, "x32")) print(x32<M>(x));
     else if (!strcmp(op, "iszero")) printf("%d 1\n", is_zero_mod<M>(x) ? 1 : 0);
     else if (!strcmp(op, "frommont") || !strcmp(op, "words")) {
         uint32_t w[8];
