@@ -485,6 +485,50 @@ int32_t nlx_bn254_plonk_commit(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, uin
 int32_t nlx_bn254_plonk_prove(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, const uint64_t* l, const uint64_t* r, const uint64_t* o,
                               const uint64_t* public_inputs, uint64_t n_public, const uint64_t* blinding, const uint64_t* commit_blinding,
                               uint8_t* proof_out, size_t proof_cap, size_t* proof_len);
+/* The witness checker of the resident prover: which row, which copy or which commitment a witness breaks (DESIGN.md section 35;
+ * the counterpart of nlx_circuit_check_witness over BN254 Fr).  Exact on the rows of H - no challenge, no random combination:
+ *   GATES    row i is bad iff ql l + qr r + qm l r + qo o + qk + PI_i + m_i l != 0 with the selectors at w^i, PI_i =
+ *            public_inputs[i] for i < n_public, c_j on commitment row i_j, 0 elsewhere, m_i = the number of commitment sets whose
+ *            committed rows contain i.  The c_j are known only when COMMITS runs in the same call: without it the k commitment
+ *            rows are left out and counted in gate_rows_skipped.  "First" = the lowest row.
+ *   COPIES   cell (wire, row) is bad iff its value differs from the value at sigma(wire, row); both ends of a broken copy are
+ *            bad cells.  "First" = the lowest row, then the lowest wire (0 = L, 1 = R, 2 = O); copy_to_* is the decoded partner.
+ *   COMMITS  per commitment j, as the prover's round 0: pi2_j from l and commit_blinding, [PI2_j] by the key's MSM, c_j =
+ *            hash_to_field([PI2_j].Marshal(), "BSB22-Plonk"), compared with l[i_j].  Dropped from `checked` on a key with k = 0.
+ * NLX_BN254_PLONK_CHECK_ALL reports satisfied exactly when nlx_bn254_plonk_prove accepts the same arguments; where the prover
+ * refuses, the first finding of the corresponding kind exists (grand product <-> copies, quotient degree <-> gates, commitment
+ * message <-> commits).  Field elements of the report are four CANONICAL words (not Montgomery). */
+#define NLX_BN254_PLONK_CHECK_GATES   1u
+#define NLX_BN254_PLONK_CHECK_COPIES  2u
+#define NLX_BN254_PLONK_CHECK_COMMITS 4u   /* keys with k > 0 */
+#define NLX_BN254_PLONK_CHECK_ALL     7u
+typedef struct {
+    uint32_t checked;      /* the NLX_BN254_PLONK_CHECK_* bits that ran */
+    uint32_t satisfied;    /* 1: nothing found by any check that ran */
+    uint64_t gate_rows_bad;
+    uint32_t gate_rows_skipped, gate_row;
+    uint64_t gate_value[4];            /* the constraint's value on gate_row */
+    uint64_t copy_cells_bad;
+    uint32_t copy_row, copy_wire, copy_to_row, copy_to_wire;
+    uint64_t copy_value[4], copy_to_value[4];
+    uint32_t commits_bad, commit_index, commit_row, commit_pad_;
+    uint64_t commit_have[4] /* l[i_j] */, commit_want[4] /* c_j */;
+    uint64_t cache_bytes;              /* what the key now keeps for later checks */
+} nlx_bn254_plonk_witness_report;
+/* l, r, o, public_inputs, commit_blinding: as nlx_bn254_plonk_prove takes them; never written.  The wires' words must be
+ * reduced Montgomery values (below r), as every fr.Element is: they are not range-checked, here or in the prover, and the copy
+ * pass compares words, so x and x + r would count as different values.  what: a non-empty set of
+ * NLX_BN254_PLONK_CHECK_* bits.  Returns NLX_OK whenever the check ran - the verdict is in *report, which is zero-filled before
+ * anything else happens; when report->satisfied == 0, nlx_last_error holds one line naming the row and value, the two cells of
+ * the copy and their values, or the commitment.  NLX_E_INVAL: a NULL argument, `what` outside 1 .. 7, COMMITS on a key with
+ * k > 0 without commit_blinding, a sigma value that lies in no coset {1, k1, k2} H (its position is in the message, nothing is
+ * cached), 1, k1^n, k2^n not pairwise distinct.  NLX_E_RANGE: a scalar not below r, more public inputs than rows.
+ * The selectors' values on H are made per check in the call's scratch (five forward transforms of size n) and not kept; the
+ * first COPIES check of a key decodes s1 s2 s3 into one 32-bit word per cell (12 n bytes), which the key keeps until
+ * nlx_bn254_plonk_key_destroy - hence the non-const key. */
+int32_t nlx_bn254_plonk_check_witness(nlx_ctx* ctx, nlx_bn254_plonk_key* key, const uint64_t* l, const uint64_t* r, const uint64_t* o,
+                                      const uint64_t* public_inputs, uint64_t n_public, const uint64_t* commit_blinding, uint32_t what,
+                                      nlx_bn254_plonk_witness_report* report);
 /* n_polys <= 16 polynomials at ONE point in one pass: polys = host array of pointers to lens[i] x 4 words (coefficients, natural
  * order, host or device; 1 <= lens[i] <= 2^28, the lengths may differ), point: host; out: host, n_polys x 4 words.  Kernel-timing
  * name "bn254_fr_eval_many". */

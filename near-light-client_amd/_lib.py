@@ -116,6 +116,7 @@ SIGNATURES = {
                                                  ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_bn254_plonk_prove": (ctypes.c_int32, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                                        ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+    "nlx_bn254_plonk_check_witness": (ctypes.c_int32, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "nlx_bn254_fr_eval_many": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
     "nlx_bn254_hash_to_field": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

@@ -620,6 +620,79 @@ def prove_resident(key, l=None, r=None, o=None, public_inputs=(), blinding=None,
     return out[:got.value].tobytes()
 
 
+# ---- the witness checker of the resident prover (csrc/bn254_plonk_check.hip) ----
+CHECK_GATES, CHECK_COPIES, CHECK_COMMITS, CHECK_ALL = 1, 2, 4, 7
+
+
+class WitnessReport(ctypes.Structure):
+    """nlx_bn254_plonk_witness_report (include/nlx.h): what nlx_bn254_plonk_check_witness found; `message` is the library's
+    line.  Field elements are four canonical words: value("gate_value") gives the integer."""
+    _fields_ = [("checked", ctypes.c_uint32), ("satisfied", ctypes.c_uint32),
+                ("gate_rows_bad", ctypes.c_uint64), ("gate_rows_skipped", ctypes.c_uint32), ("gate_row", ctypes.c_uint32),
+                ("gate_value", ctypes.c_uint64 * 4),
+                ("copy_cells_bad", ctypes.c_uint64), ("copy_row", ctypes.c_uint32), ("copy_wire", ctypes.c_uint32),
+                ("copy_to_row", ctypes.c_uint32), ("copy_to_wire", ctypes.c_uint32), ("copy_value", ctypes.c_uint64 * 4),
+                ("copy_to_value", ctypes.c_uint64 * 4),
+                ("commits_bad", ctypes.c_uint32), ("commit_index", ctypes.c_uint32), ("commit_row", ctypes.c_uint32),
+                ("commit_pad_", ctypes.c_uint32), ("commit_have", ctypes.c_uint64 * 4), ("commit_want", ctypes.c_uint64 * 4),
+                ("cache_bytes", ctypes.c_uint64)]
+    message = ""
+
+    def value(self, name):
+        return sum(int(w) << (64 * i) for i, w in enumerate(getattr(self, name)))
+
+    def as_dict(self):
+        """every field but the padding, field elements as integers"""
+        return {name: (self.value(name) if name.endswith(("_value", "_have", "_want")) else int(getattr(self, name)))
+                for name, _ in self._fields_ if name != "commit_pad_"}
+
+    def __bool__(self):
+        return self.satisfied == 1
+
+    def __str__(self):
+        return self.message if not self else "the witness satisfies the circuit (checked = %d)" % self.checked
+
+    def raise_if_unsatisfied(self):
+        if not self:
+            raise ValueError(self.message)
+        return self
+
+
+def check_resident(key, l=None, r=None, o=None, public_inputs=(), commit_blinding=None, what=CHECK_ALL, witness=None):
+    """nlx_bn254_plonk_check_witness on a ResidentKey: which row, which copy or which Bsb22 commitment the wires break.  The
+    wires as prove_resident takes them: integer lists, (n, 4) device tensors of fr.Element words, or witness = a callable that
+    receives [c_0 .. c_{j-1}] and returns (l, r, o), driven through commit_resident as prove_resident drives it (that form
+    needs commit_blinding).  commit_blinding: the 2 k scalars the proof will use - required when `what` holds CHECK_COMMITS
+    and the key carries commitments.  CHECK_ALL is satisfied exactly when prove_resident accepts the same arguments.
+    Returns a WitnessReport (truthy when satisfied); bad arguments raise as prove_resident's do."""
+    from ._lib import dll
+    k = key.k
+    if (witness is None) == (l is None) or (witness is None and (r is None or o is None)):
+        raise ValueError("pass the wires l, r, o or a callable witness(cs) -> (l, r, o)")
+    cb = None if commit_blinding is None else [int(x) % R for x in commit_blinding]
+    if cb is not None and len(cb) != 2 * k:
+        raise ValueError("two blinding scalars per Bsb22 commitment")
+    if witness is not None:
+        if k and cb is None:
+            raise ValueError("a callable witness is completed through the commitments' hints: pass commit_blinding")
+        cs = []
+        for j in range(k):
+            cs.append(commit_resident(key, j, witness(list(cs))[0], cb[2 * j:2 * j + 2])[1])
+        l, r, o = witness(list(cs))
+    wires = [_wire_words(c) for c in (l, r, o)]
+    pubs = np.stack([B._fr_words(_to_mont(int(x) % R)) for x in public_inputs]) if len(public_inputs) else None
+    cbw = np.stack([B._fr_words(_to_mont(x)) for x in cb]) if k and cb is not None else None
+    rep = WitnessReport()
+    rc = dll.nlx_bn254_plonk_check_witness(key.ctx.handle, key.handle, _ptr(wires[0]), _ptr(wires[1]), _ptr(wires[2]),
+                                           pubs.ctypes.data if pubs is not None else None, len(public_inputs),
+                                           cbw.ctypes.data if cbw is not None else None, int(what), ctypes.byref(rep))
+    if rc:
+        _raise(key.ctx, rc)
+    if not rep:
+        rep.message = dll.nlx_last_error(key.ctx.handle).decode()
+    return rep
+
+
 def eval_many(ctx, polys, point):
     """nlx_bn254_fr_eval_many: up to 16 polynomials ((m_i, 4) uint64 arrays / device tensors of fr.Element words, coefficients in
     natural order, lengths may differ) at one point (a canonical integer) -> their values as canonical integers"""

@@ -18,6 +18,7 @@
 #include "bn254_gnark_bytes.hpp"
 #include "bn254_msm.hpp"
 #include "bn254_plonk.hpp"
+#include "bn254_plonk_key.hpp"
 #include "ctx.hpp"
 #include "transcript.hpp"
 #include "../../include/nlx.h"
@@ -136,29 +137,72 @@ __global__ __launch_bounds__(256) void k_qcp_count(const uint64_t* __restrict__ 
 using namespace nlx;
 using ppr::Fr;
 
-struct nlx_bn254_plonk_key {
-    nlx_ctx* ctx = nullptr;
-    uint32_t log_n = 0, n_commit = 0;
-    bool coset = false;
-    uint64_t* coeffs = nullptr;   // [8 + k][n + 3] natural order, zero above n: ql qr qm qo qk s1 s2 s3 qcp_0 ..
-    uint64_t* sigma = nullptr;    // [3][n] s1 s2 s3 by values on H
-    uint64_t* coset_ev = nullptr; // [8 + k][4 n] with NLX_BN254_PLONK_KEY_COSET
-    void* srs = nullptr;          // n + 3 points, the bucket kernels' form
-    uint32_t* rows = nullptr;     // the committed rows, concatenated
-    uint32_t seg[NLX_BN254_PLONK_MAX_COMMIT + 1] = {};
-    uint32_t commit_rows[NLX_BN254_PLONK_MAX_COMMIT] = {};
-    uint32_t last_row = 0;
-    uint64_t k1[4], k2[4], shift[4];
-    uint64_t commitments[(8 + NLX_BN254_PLONK_MAX_COMMIT) * 8];   // s1 s2 s3 ql qr qm qo qk qcp_0 ..
-    std::vector<void*> blocks;
-    uint64_t info[NLX_BN254_PLONK_KEY_INFO_WORDS] = {};
-};
+// struct nlx_bn254_plonk_key: bn254_plonk_key.hpp
+using namespace nlx::ppk;
 
-namespace {
+// ---- the host helpers the witness checker shares (bn254_plonk_key.hpp) ----
+namespace nlx {
+namespace ppk {
 
 const uint8_t BSB22_DST[] = "BSB22-Plonk";
-// position of ql qr qm qo qk s1 s2 s3 in the key's arrays
-enum { QL = 0, QR, QM, QO, QK, S1, S2, S3 };
+
+int32_t commit(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, const MsmScratch& ms, const uint64_t* d_scalars, size_t count, uint64_t out[8]) {
+    using namespace nlx::msm;
+    SortedDigits sd;
+    int32_t rc = sort_digits(ctx, d_scalars, count, 1, &sd);
+    if (rc) return rc;
+    bucket_reduce(ctx, sd, key->srs, 0, ms.buckets, ms.wsum);
+    std::vector<unsigned char> words(window_sum_bytes(0));
+    rc = fetch(ctx, words.data(), ms.wsum, words.size());
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    release_digits(ctx, &sd);
+    if (!rc) {
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = ctx->hip_fail(e, "kernel launch");
+    }
+    if (rc) return rc;
+    hstore_affine<H1>(window_tail_g1(words.data()), out);
+    return NLX_OK;
+}
+int32_t msm_scratch(nlx_ctx* ctx, Scratch& scratch, MsmScratch* ms) {
+    ms->buckets = scratch.alloc(msm::bucket_bytes(0));
+    ms->wsum = scratch.alloc(msm::window_sum_bytes(0));
+    return ms->buckets && ms->wsum ? NLX_OK : ctx->fail(NLX_E_NOMEM, "PLONK: device memory for the MSM's buckets");
+}
+
+// pi2_j on H from the L wire into d_col (n elements), its coefficients in place
+int32_t build_pi2(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, uint32_t j, const uint64_t* d_l, const uint64_t* d_b2, uint64_t* d_col) {
+    const size_t n = (size_t)1 << key->log_n;
+    const uint32_t count = key->seg[j + 1] - key->seg[j];
+    NLX_HIP(ctx, hipMemsetAsync(d_col, 0, n * 32, ctx->stream));
+    if (count) hipLaunchKernelGGL(ppr::k_pi2_gather, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, d_l, key->rows + key->seg[j], count, d_col);
+    hipLaunchKernelGGL(ppr::k_pi2_blind, dim3(1), dim3(1), 0, ctx->stream, d_col, key->commit_rows[j], key->last_row, d_b2);
+    return NLX_OK;
+}
+
+int32_t check_scalars(nlx_ctx* ctx, const uint64_t* w, size_t count, const char* what) {
+    if (is_device_ptr(w)) return ctx->fail(NLX_E_INVAL, "%s are host values", what);
+    for (size_t i = 0; i < count; i++)
+        if (!bnf::below_mod<bnf::RP>(w + 4 * i)) return ctx->fail(NLX_E_RANGE, "%s: element %llu is not below r", what, (unsigned long long)i);
+    return NLX_OK;
+}
+
+// round 0 for one commitment, as the prover, the solver's hint and the witness checker all take it
+int32_t commit_pi2(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, const MsmScratch& ms, uint32_t j, const uint64_t* d_l, const uint64_t* d_b2,
+                   uint64_t* d_col, uint64_t point_out[8], uint64_t c_out[4]) {
+    NLX_RC(build_pi2(ctx, key, j, d_l, d_b2, d_col));
+    NLX_RC(nlx_bn254_ntt_batch(ctx, d_col, 1, key->log_n, 1, NLX_BN254_MONTGOMERY));
+    NLX_RC(commit(ctx, key, ms, d_col, (size_t)1 << key->log_n, point_out));
+    uint8_t bytes[64];
+    ppr::g1_marshal(point_out, bytes);
+    bnf::store_words(ppr::hash_to_field(bytes, 64, BSB22_DST, sizeof BSB22_DST - 1), c_out);
+    return NLX_OK;
+}
+
+}  // namespace ppk
+}  // namespace nlx
+
+namespace {
 
 // a round's device time under the library's kernel timing: the rounds are made of calls that take samples of their own, so the
 // round's sample is pushed when it ends
@@ -184,6 +228,7 @@ void key_free(nlx_bn254_plonk_key* key) {
     if (key->ctx) {
         (void)hipStreamSynchronize(key->ctx->stream);
         for (void* p : key->blocks) key->ctx->release(p);
+        if (key->sigma_cells) key->ctx->release(key->sigma_cells);
     }
     delete key;
 }
@@ -194,35 +239,6 @@ void* key_alloc(nlx_bn254_plonk_key* key, size_t bytes) {
         key->info[0] += bytes;
     }
     return d;
-}
-
-// The MSM over the resident SRS: sum_i scalars[i] srs[i], i < count <= n + 3.  buckets / wsum: the call's scratch.
-struct MsmScratch {
-    void* buckets = nullptr;
-    void* wsum = nullptr;
-};
-int32_t commit(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, const MsmScratch& ms, const uint64_t* d_scalars, size_t count, uint64_t out[8]) {
-    using namespace nlx::msm;
-    SortedDigits sd;
-    int32_t rc = sort_digits(ctx, d_scalars, count, 1, &sd);
-    if (rc) return rc;
-    bucket_reduce(ctx, sd, key->srs, 0, ms.buckets, ms.wsum);
-    std::vector<unsigned char> words(window_sum_bytes(0));
-    rc = fetch(ctx, words.data(), ms.wsum, words.size());
-    if (rc) (void)hipStreamSynchronize(ctx->stream);
-    release_digits(ctx, &sd);
-    if (!rc) {
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = ctx->hip_fail(e, "kernel launch");
-    }
-    if (rc) return rc;
-    hstore_affine<H1>(window_tail_g1(words.data()), out);
-    return NLX_OK;
-}
-int32_t msm_scratch(nlx_ctx* ctx, Scratch& scratch, MsmScratch* ms) {
-    ms->buckets = scratch.alloc(msm::bucket_bytes(0));
-    ms->wsum = scratch.alloc(msm::window_sum_bytes(0));
-    return ms->buckets && ms->wsum ? NLX_OK : ctx->fail(NLX_E_NOMEM, "PLONK: device memory for the MSM's buckets");
 }
 
 // values of up to EVAL_MAX device polynomials at one host point -> out (host, Montgomery words)
@@ -358,23 +374,6 @@ int32_t key_build(nlx_ctx* ctx, const nlx_bn254_plonk_key_desc* d, nlx_bn254_plo
     return scratch.finish(NLX_OK);
 }
 
-// pi2_j on H from the L wire into d_col (n elements), its coefficients in place
-int32_t build_pi2(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, uint32_t j, const uint64_t* d_l, const uint64_t* d_b2, uint64_t* d_col) {
-    const size_t n = (size_t)1 << key->log_n;
-    const uint32_t count = key->seg[j + 1] - key->seg[j];
-    NLX_HIP(ctx, hipMemsetAsync(d_col, 0, n * 32, ctx->stream));
-    if (count) hipLaunchKernelGGL(ppr::k_pi2_gather, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, d_l, key->rows + key->seg[j], count, d_col);
-    hipLaunchKernelGGL(ppr::k_pi2_blind, dim3(1), dim3(1), 0, ctx->stream, d_col, key->commit_rows[j], key->last_row, d_b2);
-    return NLX_OK;
-}
-
-int32_t check_scalars(nlx_ctx* ctx, const uint64_t* w, size_t count, const char* what) {
-    if (is_device_ptr(w)) return ctx->fail(NLX_E_INVAL, "%s are host values", what);
-    for (size_t i = 0; i < count; i++)
-        if (!bnf::below_mod<bnf::RP>(w + 4 * i)) return ctx->fail(NLX_E_RANGE, "%s: element %llu is not below r", what, (unsigned long long)i);
-    return NLX_OK;
-}
-
 int32_t prove_body(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, const uint64_t* l, const uint64_t* r, const uint64_t* o, const uint64_t* pubs,
                    uint64_t n_public, const uint64_t* blinding, const uint64_t* commit_blinding, uint8_t* proof_out, size_t* proof_len) {
     using namespace nlx::ppr;
@@ -413,15 +412,10 @@ int32_t prove_body(nlx_ctx* ctx, const nlx_bn254_plonk_key* key, const uint64_t*
         NLX_HIP(ctx, hipMemsetAsync(d_pi, 0, (size_t)(1 + k) * m * 32, st));
         for (uint32_t j = 0; j < k; j++) {
             uint64_t* col = d_pi2 + (size_t)j * m * 4;
-            NLX_RC(build_pi2(ctx, key, j, d_wire[0], d_cb + 8 * j, col));
-            NLX_RC(nlx_bn254_ntt_batch(ctx, col, 1, log_n, 1, NLX_BN254_MONTGOMERY));
-            NLX_RC(commit(ctx, key, ms, col, n, pi2c[j]));
-            uint8_t bytes[64];
-            g1_marshal(pi2c[j], bytes);
-            cs[j] = hash_to_field(bytes, 64, BSB22_DST, sizeof BSB22_DST - 1);
-            uint64_t have[4], want[4];
+            uint64_t want[4], have[4];
+            NLX_RC(commit_pi2(ctx, key, ms, j, d_wire[0], d_cb + 8 * j, col, pi2c[j], want));
+            cs[j] = fr_words(want);
             NLX_RC(fetch(ctx, have, d_wire[0] + 4 * (size_t)key->commit_rows[j], 32));
-            store_words(cs[j], want);
             if (memcmp(have, want, 32))
                 return ctx->fail(NLX_E_INVAL, "Bsb22 commitment %u: the L wire of its commitment row is not the hash of the commitment (or a committed value changed after the hint)", j);
         }
@@ -658,15 +652,11 @@ extern "C" int32_t nlx_bn254_plonk_commit(nlx_ctx* ctx, const nlx_bn254_plonk_ke
     if (!d_col || !d_b2) return NLX_E_NOMEM;
     NLX_HIP(ctx, hipMemcpyAsync(d_b2, blinding, 64, hipMemcpyHostToDevice, ctx->stream));
     RoundTimer timer(ctx, "bn254_plonk_prove_commit");
-    NLX_RC(build_pi2(ctx, key, j, sl.as<uint64_t>(), d_b2, d_col));
-    NLX_RC(nlx_bn254_ntt_batch(ctx, d_col, 1, key->log_n, 1, NLX_BN254_MONTGOMERY));
-    uint64_t pt[8];
-    NLX_RC(commit(ctx, key, ms, d_col, n, pt));
+    uint64_t pt[8], c[4];
+    NLX_RC(commit_pi2(ctx, key, ms, j, sl.as<uint64_t>(), d_b2, d_col, pt, c));
     NLX_RC(scratch.finish(NLX_OK));
-    uint8_t bytes[64];
-    ppr::g1_marshal(pt, bytes);
     memcpy(point_out, pt, 64);
-    bnf::store_words(ppr::hash_to_field(bytes, 64, BSB22_DST, sizeof BSB22_DST - 1), c_out);
+    memcpy(c_out, c, 32);
     return NLX_OK;
 } NLX_CATCH(ctx)
 
