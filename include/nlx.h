@@ -219,6 +219,17 @@ int32_t nlx_bn254_g1_lincomb(nlx_ctx* ctx, const uint64_t* points, const uint64_
  * worth of gather targets for the MSM; a big-integer model makes a few thousand per second).  out: host or device, n x 8
  * words; n <= 2^27; base must not be the point at infinity. */
 int32_t nlx_bn254_g1_multiples(nlx_ctx* ctx, const uint64_t base[8], uint64_t n, uint64_t* out);
+/* Fixed-base batch scalar multiplication (csrc/bn254_fixed_base.hip): out[i] = scalars[i] * base for
+ * i < n - what an SRS [tau^i]_1, a Groth16 setup and every honest test key are made of.  base: HOST, 8 (G1Affine) or 16
+ * (G2Affine) Montgomery words; scalars: n x 4 words, fr.Element in Montgomery form with flags = NLX_BN254_MONTGOMERY, canonical
+ * integers with flags = 0, host or device; out: n x 8 (G1) or n x 16 (G2) words, Montgomery, host or device; the all-zero words
+ * stand for the point at infinity (a scalar of 0).  n <= 2^27.  NLX_E_RANGE: a scalar not below r (the message names its
+ * index), a base with a coordinate not below q, off its curve or (G2) outside the subgroup of order r - the checks
+ * nlx_bn254_g1_lincomb and nlx_bn254_pairing apply; NLX_E_INVAL: the base is the point at infinity.  Nothing is written on a
+ * refusal.  A table of d * 2^(8 j) * base (d < 256, j < 32) is built per call in HBM; then 32 mixed additions per scalar and
+ * one inversion per lane.  Kernel-timing names "bn254_fixed_base_table", "bn254_fixed_base_g1", "bn254_fixed_base_g2". */
+int32_t nlx_bn254_g1_scalar_muls(nlx_ctx* ctx, const uint64_t base[8], const uint64_t* scalars, uint64_t n, uint32_t flags, uint64_t* out);
+int32_t nlx_bn254_g2_scalar_muls(nlx_ctx* ctx, const uint64_t base[16], const uint64_t* scalars, uint64_t n, uint32_t flags, uint64_t* out);
 
 /* ---- f.4 (third piece): the PLONK prover's quotient chain and a KZG opening on those kernels.  What the wrap's prover
  * (gnark backend/plonk/bn254 Prove; Go, not in /root/reference - succinct.json:7-8 names the entry point that runs it) does
@@ -422,6 +433,61 @@ int32_t nlx_bn254_groth16_prove_committed(nlx_ctx* ctx, const nlx_bn254_groth16_
                                           const uint64_t* b, const uint64_t* c, const uint64_t r[4], const uint64_t s[4],
                                           const uint64_t rho[4], uint64_t ar_out[8], uint64_t bs_out[16], uint64_t krs_out[8],
                                           uint64_t* commitments_out, uint64_t pok_out[8]);
+
+/* gnark's groth16.Setup(r1cs) from a trapdoor, on the device (csrc/bn254_groth16_setup.hip).  The rules are
+ * rule 3 of tools/groth16_model.py and rule 1 of tools/groth16_commit_model.py - recalled from gnark v0.9, UNPINNED like the
+ * rest of the Groth16 half.  The descriptor:
+ *   log_n, n_wires, n_public, n_constraints, the R1CS (required) and n_commitments / n_private / private_wires /
+ *                       commitment_wires: as in nlx_bn254_groth16_key_desc and nlx_bn254_groth16_commit_desc (host or device)
+ *   tau, alpha, beta, gamma, delta    the trapdoor: HOST, four Montgomery words each
+ *   sigma               the Pedersen trapdoor: HOST, four Montgomery words; read only for n_commitments > 0
+ * On the device: L_j(tau) for j < 2^log_n with one batched inversion; A_i(tau), B_i(tau), C_i(tau) as the transposed products
+ * of the three matrices (terms sorted by wire id; a lane per wire, a wave per wire above 64 terms); the scalars of every key
+ * array; ONE fixed-base launch over G1 and one over G2.  InfinityA[i] / InfinityB[i] are set exactly when A_i(tau) / B_i(tau) is
+ * zero, whether the wire is absent from the matrix or its terms cancel.
+ * NLX_E_RANGE, the message naming the cause: flags other than NLX_BN254_MONTGOMERY, a trapdoor value that is zero or not
+ * below r, tau^(2^log_n) = 1, and everything nlx_bn254_groth16_key_create[_committed] refuses about sizes, ids and sets.
+ * Nothing is left allocated on a refusal.  The result belongs to its context and must be destroyed before it.
+ * The Pedersen verifying key is ([1]_2, [-sigma]_2): the model's rule takes BasisExpSigma = sigma Basis, under which
+ * e(C, [-sigma]_2) e(Pok, [1]_2) = 1 (a setup that takes BasisExpSigma = (1 / sigma') Basis writes the same key as [-1 / sigma']_2).
+ * (The type is known by its struct tag only: the name is the entry point's.) */
+struct nlx_bn254_groth16_setup;
+typedef struct {
+    uint32_t log_n;
+    uint32_t flags;                     /* NLX_BN254_MONTGOMERY */
+    uint64_t n_wires, n_public, n_constraints;
+    const uint64_t *a_row_ptr, *b_row_ptr, *c_row_ptr;
+    const uint32_t *a_wire, *b_wire, *c_wire;
+    const uint32_t *a_coeff_id, *b_coeff_id, *c_coeff_id;
+    const uint64_t* coeffs; uint64_t n_coeffs;
+    const uint64_t *tau, *alpha, *beta, *gamma, *delta;
+    uint32_t n_commitments;
+    const uint64_t* n_private;
+    const uint32_t* private_wires;
+    const uint32_t* commitment_wires;
+    const uint64_t* sigma;
+} nlx_bn254_groth16_setup_desc;
+int32_t nlx_bn254_groth16_setup(nlx_ctx* ctx, const nlx_bn254_groth16_setup_desc* desc, struct nlx_bn254_groth16_setup** out);
+void nlx_bn254_groth16_setup_destroy(struct nlx_bn254_groth16_setup* setup);
+/* out[0..3] = the points of G1.A, G1.B (= G2.B), G1.K, G1.Z; out[4] = M, the committed wires; out[5] = k; out[6] = the points of
+ * ic (n_public + k); out[7] = the wires whose sums ran one per wave (over the three matrices). */
+#define NLX_BN254_GROTH16_SETUP_INFO_WORDS 8
+int32_t nlx_bn254_groth16_setup_info(const struct nlx_bn254_groth16_setup* setup, uint64_t out[NLX_BN254_GROTH16_SETUP_INFO_WORDS]);
+/* One array of the result copied to `out` (host or device), in gnark-crypto's layout: G1Affine 8 words, G2Affine 16 words,
+ * Montgomery; the masks one byte per wire.  The counts are nlx_bn254_groth16_setup_info's; basis and basis_exp_sigma hold the k
+ * Pedersen keys' points concatenated (M each).  An array of no points writes nothing.  NLX_E_RANGE: an unknown `which`; the
+ * two Pedersen G2 points on a result without commitments. */
+enum {
+    NLX_G16_SETUP_G1_A = 0, NLX_G16_SETUP_G1_B = 1, NLX_G16_SETUP_G2_B = 2, NLX_G16_SETUP_G1_K = 3, NLX_G16_SETUP_G1_Z = 4,
+    NLX_G16_SETUP_INFINITY_A = 5, NLX_G16_SETUP_INFINITY_B = 6,
+    NLX_G16_SETUP_G1_ALPHA = 7, NLX_G16_SETUP_G1_BETA = 8, NLX_G16_SETUP_G1_DELTA = 9, NLX_G16_SETUP_G2_BETA = 10, NLX_G16_SETUP_G2_DELTA = 11,
+    NLX_G16_SETUP_BASIS = 12, NLX_G16_SETUP_BASIS_EXP_SIGMA = 13,
+    NLX_G16_SETUP_G2_GAMMA = 14, NLX_G16_SETUP_IC = 15, NLX_G16_SETUP_PEDERSEN_G = 16, NLX_G16_SETUP_PEDERSEN_G_ROOT_SIGMA_NEG = 17
+};
+int32_t nlx_bn254_groth16_setup_read(const struct nlx_bn254_groth16_setup* setup, uint32_t which, void* out);
+/* The resident proving key of this setup (with its R1CS, and its Pedersen bases for k > 0), built from the device arrays by
+ * nlx_bn254_groth16_key_create[_committed]: the points never visit the host.  The key is the caller's, independent of `setup`. */
+int32_t nlx_bn254_groth16_setup_key(const struct nlx_bn254_groth16_setup* setup, nlx_bn254_groth16_key** out);
 
 /* ---- f.4, the PLONK half: whole gnark-shaped proofs from a proving key resident in HBM (gnark backend/plonk/bn254 ProvingKey and
  * Prove; Go, not in the reference: the protocol is restated from its published structure, parity with gnark-produced bytes

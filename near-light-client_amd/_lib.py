@@ -92,6 +92,8 @@ SIGNATURES = {
     "nlx_bn254_msm_g2": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
                                            ctypes.c_void_p]),
     "nlx_bn254_g1_multiples": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]),
+    "nlx_bn254_g1_scalar_muls": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]),
+    "nlx_bn254_g2_scalar_muls": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]),
     "nlx_bn254_plonk_quotient": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "nlx_bn254_plonk_grand_product": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 11 + [ctypes.POINTER(ctypes.c_int32)]),
     "nlx_bn254_fr_lincomb": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -107,6 +109,11 @@ SIGNATURES = {
     "nlx_bn254_groth16_key_create_committed": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
     "nlx_bn254_groth16_commit": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_bn254_groth16_prove_committed": (ctypes.c_int32, [ctypes.c_void_p] * 14),
+    "nlx_bn254_groth16_setup": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
+    "nlx_bn254_groth16_setup_destroy": (None, [ctypes.c_void_p]),
+    "nlx_bn254_groth16_setup_info": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_bn254_groth16_setup_read": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "nlx_bn254_groth16_setup_key": (ctypes.c_int32, [ctypes.c_void_p, c_void_pp]),
     "nlx_bn254_plonk_key_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
     "nlx_bn254_plonk_key_destroy": (None, [ctypes.c_void_p]),
     "nlx_bn254_plonk_key_info": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),

@@ -484,6 +484,35 @@ def bn254_g1_multiples(ctx, base, n, device=None):
     return out
 
 
+def _scalar_muls(ctx, entry, base_words, width, scalars, montgomery, device):
+    ks, sp, n = _point_rows(scalars, 4)
+    if device is not None:
+        import torch
+        out = torch.empty((n, width), dtype=torch.int64, device=device)
+        ctx.check(entry(ctx.handle, base_words.ctypes.data, sp if n else None, n, 1 if montgomery else 0, out.data_ptr() if n else None))
+        return out
+    out = np.zeros((n, width), dtype=np.uint64)
+    ctx.check(entry(ctx.handle, base_words.ctypes.data, sp if n else None, n, 1 if montgomery else 0, out.ctypes.data if n else None))
+    return out
+
+
+def bn254_g1_scalar_muls(ctx, base, scalars, montgomery=False, device=None):
+    """Fixed-base batch scalar multiplication on the GPU (nlx_bn254_g1_scalar_muls): [k * base for k in scalars] as G1Affine
+    words.  base: (x, y) integers, or 8 words (bn254_g1_pack); scalars: (n, 4) uint64 words - canonical integers below r, or
+    fr.Element words with montgomery=True - numpy or a device tensor.  Returns (n, 8) uint64 on the host, or an int64 device
+    tensor with device="cuda:k"; all-zero words for the point at infinity.  A scalar >= r (its index is named), a base off
+    the curve or with a coordinate >= q raises NlxError (NLX_E_RANGE); the base at infinity NLX_E_INVAL."""
+    b = bn254_g1_pack([base])[0] if isinstance(base, tuple) else np.ascontiguousarray(base, dtype=np.uint64).reshape(8)
+    return _scalar_muls(ctx, dll.nlx_bn254_g1_scalar_muls, b, 8, scalars, montgomery, device)
+
+
+def bn254_g2_scalar_muls(ctx, base, scalars, montgomery=False, device=None):
+    """The same over G2 (nlx_bn254_g2_scalar_muls).  base: ((x0, x1), (y0, y1)) integers, or 16 words (bn254_g2_pack); returns
+    (n, 16) words.  The base must lie in the subgroup of order r (NLX_E_RANGE otherwise)."""
+    b = bn254_g2_pack([base])[0] if isinstance(base, tuple) else np.ascontiguousarray(base, dtype=np.uint64).reshape(16)
+    return _scalar_muls(ctx, dll.nlx_bn254_g2_scalar_muls, b, 16, scalars, montgomery, device)
+
+
 # ---- G2 (Groth16's B query): coordinates in Fq2 = Fq[u] / (u^2 + 1), gnark-crypto's G2Affine{X, Y E2{A0, A1}} ----
 def bn254_g2_pack(points):
     """[((x0, x1), (y0, y1)) | None] -> (n, 16) uint64: X.A0, X.A1, Y.A0, Y.A1, each a Montgomery fp.Element"""

@@ -8,6 +8,8 @@ gnark-produced bytes unpinned: DESIGN.md section 19).
   proof_bytes(...)       gnark's Proof.WriteTo, 164 + 32 k bytes; g1_compress / g2_compress: gnark-crypto's Bytes()
   VerifyingKey(ctx, ...) nlx_bn254_groth16_vk_create: gnark's VerifyingKey resident, e(alpha, beta) precomputed on the device;
                          .verify(proof_bytes, public) / .verify_many(proofs, publics) -> Verdict
+  setup(ctx, ..., r1cs)  nlx_bn254_groth16_setup: gnark's groth16.Setup from a trapdoor on the device -> (ProvingKey,
+                         VerifyingKey, SetupArrays); Setup is the resident result itself
 Keys with k Bsb22 / Pedersen commitments (rules: tools/groth16_commit_model.py):
   ProvingKey(ctx, ..., commitments=[...])   nlx_bn254_groth16_key_create_committed: the Pedersen bases resident next to the key
   commit(pk, j, w)                          nlx_bn254_groth16_commit: C_j, the call a solver's hint makes
@@ -179,6 +181,18 @@ class ProvingKey:
         self.handle = h
         self.has_r1cs = r1cs is not None
         ctx._adopt(self)
+
+    @classmethod
+    def _from_handle(cls, ctx, handle, log_n, n_wires, n_public, n_constraints, commitments=()):
+        """a key the library built itself (Setup.key): the handle is adopted as it is"""
+        self = cls.__new__(cls)
+        self.ctx, self.handle = ctx, handle
+        self.commitments = [{"private": [int(i) for i in c["private"]], "public": [int(i) for i in c["public"]], "wire": int(c["wire"])}
+                            for c in commitments]
+        self.log_n, self.n_wires, self.n_public, self.n_constraints = int(log_n), int(n_wires), int(n_public), int(n_constraints)
+        self.has_r1cs = True
+        ctx._adopt(self)
+        return self
 
     def info(self):
         """what the key reports: resident bytes, and the SpMV's row split"""
@@ -461,3 +475,178 @@ class VerifyingKey:
             self.close()
         except Exception:
             pass
+
+
+# ---- setup from a trapdoor (csrc/bn254_groth16_setup.hip; rules: tools/groth16_model.py rule 3, tools/groth16_commit_model.py rule 1) ----
+SETUP_INFO_WORDS = 8
+(SETUP_G1_A, SETUP_G1_B, SETUP_G2_B, SETUP_G1_K, SETUP_G1_Z, SETUP_INFINITY_A, SETUP_INFINITY_B, SETUP_G1_ALPHA, SETUP_G1_BETA,
+ SETUP_G1_DELTA, SETUP_G2_BETA, SETUP_G2_DELTA, SETUP_BASIS, SETUP_BASIS_EXP_SIGMA, SETUP_G2_GAMMA, SETUP_IC, SETUP_PEDERSEN_G,
+ SETUP_PEDERSEN_G_ROOT_SIGMA_NEG) = range(18)
+
+
+class _SetupDesc(ctypes.Structure):
+    """nlx_bn254_groth16_setup_desc (include/nlx.h)"""
+    _fields_ = ([("log_n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_wires", ctypes.c_uint64), ("n_public", ctypes.c_uint64),
+                 ("n_constraints", ctypes.c_uint64)]
+                + [(k, ctypes.c_void_p) for k in ("a_row_ptr", "b_row_ptr", "c_row_ptr", "a_wire", "b_wire", "c_wire",
+                                                  "a_coeff_id", "b_coeff_id", "c_coeff_id", "coeffs")]
+                + [("n_coeffs", ctypes.c_uint64)]
+                + [(k, ctypes.c_void_p) for k in ("tau", "alpha", "beta", "gamma", "delta")]
+                + [("n_commitments", ctypes.c_uint32), ("n_private", ctypes.c_void_p), ("private_wires", ctypes.c_void_p),
+                   ("commitment_wires", ctypes.c_void_p), ("sigma", ctypes.c_void_p)])
+
+
+class Trapdoor:
+    """The setup's toxic waste: tau, alpha, beta, gamma, delta and, for keys with commitments, the Pedersen sigma - integers in
+    1 .. r - 1 (the library refuses anything else, and a tau inside the domain).  Whoever keeps it can forge proofs."""
+
+    def __init__(self, tau, alpha, beta, gamma, delta, sigma=None):
+        self.tau, self.alpha, self.beta, self.gamma, self.delta = int(tau), int(alpha), int(beta), int(gamma), int(delta)
+        self.sigma = None if sigma is None else int(sigma)
+
+    @classmethod
+    def random(cls):
+        return cls(*(1 + secrets.randbelow(R - 1) for _ in range(6)))
+
+
+def _trapdoor_words(x):
+    x = int(x)
+    if not 0 <= x < (1 << 256):
+        raise NlxError(NLX_E_RANGE, "a trapdoor value does not fit four words")
+    m = x * _MONT % R if x < R else x              # r <= x < 2^256 is no residue: its words go as they are and the library refuses them
+    return np.array([(m >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(4)], dtype=np.uint64)
+
+
+class SetupArrays:
+    """gnark's ProvingKey and VerifyingKey arrays of one setup as numpy words (G1Affine 8, G2Affine 16, Montgomery): g1_a, g1_b,
+    g2_b, g1_k, g1_z, infinity_a, infinity_b, g1_alpha, g1_beta, g1_delta, g2_beta, g2_delta, commitments (per commitment
+    {"basis", "basis_exp_sigma"}), and g2_gamma, ic, pedersen_g, pedersen_g_root_sigma_neg (None without commitments)."""
+
+    def __init__(self, **arrays):
+        self.__dict__.update(arrays)
+
+
+class Setup:
+    """struct nlx_bn254_groth16_setup: the result of gnark's groth16.Setup from a trapdoor, resident on the device (owns the
+    handle).  r1cs as for ProvingKey (required); commitments: one dict per Bsb22 commitment - "private", "public", "wire" as for
+    ProvingKey, optionally "hashed" (the verifier's PublicAndCommitmentCommitted as positions in ic; by default "public" with
+    commitment i's wire as n_public + i)."""
+
+    def __init__(self, ctx, log_n, n_wires, n_public, n_constraints, r1cs, trapdoor, commitments=None, flags=NLX_BN254_MONTGOMERY):
+        self.ctx, self.handle = ctx, None
+        self.log_n, self.n_wires, self.n_public, self.n_constraints = int(log_n), int(n_wires), int(n_public), int(n_constraints)
+        self.commitments = [] if commitments is None else [dict(c) for c in commitments]
+        d = _SetupDesc()
+        d.log_n, d.flags, d.n_wires, d.n_public, d.n_constraints = self.log_n, int(flags), self.n_wires, self.n_public, self.n_constraints
+        keep = []
+        for m in "ABC":
+            rows = {}
+            for field, arr, dt in zip(("row_ptr", "wire", "coeff_id"), r1cs[m], (np.uint64, np.uint32, np.uint32)):
+                k, p, rows[field] = _buf(arr, dt, 0)
+                keep.append(k)
+                setattr(d, "%s_%s" % (m.lower(), field), p)
+            if rows["row_ptr"] != self.n_constraints + 1 or rows["wire"] != rows["coeff_id"]:
+                raise ValueError("matrix %s: row_ptr holds n_constraints + 1 offsets, wire and coeff_id one entry per term" % m)
+            last = int(r1cs[m][0][-1]) if rows["row_ptr"] else 0
+            if last > rows["wire"]:
+                raise ValueError("matrix %s: row_ptr ends at %d, the matrix holds %d terms" % (m, last, rows["wire"]))
+        k, p, rows = _buf(r1cs["coeffs"], np.uint64, 4)
+        keep.append(k)
+        d.coeffs, d.n_coeffs = p, rows
+        for name in ("tau", "alpha", "beta", "gamma", "delta"):
+            w = _trapdoor_words(getattr(trapdoor, name))
+            keep.append(w)
+            setattr(d, name, w.ctypes.data)
+        d.n_commitments = len(self.commitments)
+        if self.commitments:
+            if trapdoor.sigma is None:
+                raise ValueError("a setup with commitments needs the trapdoor's sigma")
+            counts = np.array([len(c["private"]) for c in self.commitments], dtype=np.uint64)
+            ids = np.array([i for c in self.commitments for i in c["private"]] + [0], dtype=np.uint32)
+            wires = np.array([c["wire"] for c in self.commitments], dtype=np.uint32)
+            sigma = _trapdoor_words(trapdoor.sigma)
+            keep += [counts, ids, wires, sigma]
+            d.n_private, d.private_wires, d.commitment_wires, d.sigma = counts.ctypes.data, ids.ctypes.data, wires.ctypes.data, sigma.ctypes.data
+        h = ctypes.c_void_p()
+        ctx.check(dll.nlx_bn254_groth16_setup(ctx.handle, ctypes.byref(d), ctypes.byref(h)))
+        self.handle = h
+        ctx._adopt(self)
+
+    def info(self):
+        out = np.zeros(SETUP_INFO_WORDS, dtype=np.uint64)
+        self.ctx.check(dll.nlx_bn254_groth16_setup_info(self.handle, out.ctypes.data))
+        names = ("g1_a", "g1_b", "g1_k", "g1_z", "committed_wires", "commitments", "ic", "wave_wires")
+        return {k: int(out[i]) for i, k in enumerate(names)}
+
+    def read(self, which, device=None):
+        """one array (SETUP_*): numpy words, or an int64 device tensor with device="cuda:k" (the masks: uint8)"""
+        info = self.info()
+        rows = {SETUP_G1_A: info["g1_a"], SETUP_G1_B: info["g1_b"], SETUP_G2_B: info["g1_b"], SETUP_G1_K: info["g1_k"], SETUP_G1_Z: info["g1_z"],
+                SETUP_INFINITY_A: self.n_wires, SETUP_INFINITY_B: self.n_wires, SETUP_BASIS: info["committed_wires"],
+                SETUP_BASIS_EXP_SIGMA: info["committed_wires"], SETUP_IC: info["ic"]}.get(which, 1)
+        mask = which in (SETUP_INFINITY_A, SETUP_INFINITY_B)
+        width = 16 if which in (SETUP_G2_B, SETUP_G2_BETA, SETUP_G2_DELTA, SETUP_G2_GAMMA, SETUP_PEDERSEN_G, SETUP_PEDERSEN_G_ROOT_SIGMA_NEG) else 8
+        if device is not None:
+            import torch
+            out = torch.zeros((rows,) if mask else (rows, width), dtype=torch.uint8 if mask else torch.int64, device=device)
+            self.ctx.check(dll.nlx_bn254_groth16_setup_read(self.handle, which, out.data_ptr() if rows else None))
+            return out
+        out = np.zeros((rows,) if mask else (rows, width), dtype=np.uint8 if mask else np.uint64)
+        self.ctx.check(dll.nlx_bn254_groth16_setup_read(self.handle, which, out.ctypes.data if rows else None))
+        return out
+
+    def arrays(self):
+        k = len(self.commitments)
+        a = {name: self.read(which) for name, which in (
+            ("g1_a", SETUP_G1_A), ("g1_b", SETUP_G1_B), ("g2_b", SETUP_G2_B), ("g1_k", SETUP_G1_K), ("g1_z", SETUP_G1_Z),
+            ("infinity_a", SETUP_INFINITY_A), ("infinity_b", SETUP_INFINITY_B), ("ic", SETUP_IC))}
+        for name, which in (("g1_alpha", SETUP_G1_ALPHA), ("g1_beta", SETUP_G1_BETA), ("g1_delta", SETUP_G1_DELTA), ("g2_beta", SETUP_G2_BETA),
+                            ("g2_delta", SETUP_G2_DELTA), ("g2_gamma", SETUP_G2_GAMMA)):
+            a[name] = self.read(which)[0]
+        basis, sigma = self.read(SETUP_BASIS), self.read(SETUP_BASIS_EXP_SIGMA)
+        a["commitments"], at = [], 0
+        for c in self.commitments:
+            a["commitments"].append({"basis": basis[at:at + len(c["private"])], "basis_exp_sigma": sigma[at:at + len(c["private"])]})
+            at += len(c["private"])
+        a["pedersen_g"] = self.read(SETUP_PEDERSEN_G)[0] if k else None
+        a["pedersen_g_root_sigma_neg"] = self.read(SETUP_PEDERSEN_G_ROOT_SIGMA_NEG)[0] if k else None
+        return SetupArrays(**a)
+
+    def key(self):
+        """nlx_bn254_groth16_setup_key: the resident ProvingKey, built from the device arrays"""
+        h = ctypes.c_void_p()
+        self.ctx.check(dll.nlx_bn254_groth16_setup_key(self.handle, ctypes.byref(h)))
+        return ProvingKey._from_handle(self.ctx, h, self.log_n, self.n_wires, self.n_public, self.n_constraints, self.commitments)
+
+    def verifying_key(self):
+        """the VerifyingKey of this setup (the verifying side is a few points: read to the host and handed to its creation)"""
+        k = len(self.commitments)
+        one = lambda which: self.read(which)[0]
+        wire_at = {int(c["wire"]): self.n_public + i for i, c in enumerate(self.commitments)}
+        hashed = [{"public": [int(i) for i in c["hashed"]] if "hashed" in c else [wire_at.get(int(i), int(i)) for i in c["public"]]}
+                  for c in self.commitments]
+        pedersen = (one(SETUP_PEDERSEN_G), one(SETUP_PEDERSEN_G_ROOT_SIGMA_NEG)) if k else None
+        return VerifyingKey(self.ctx, self.n_public, one(SETUP_G1_ALPHA), one(SETUP_G2_BETA), one(SETUP_G2_GAMMA), one(SETUP_G2_DELTA),
+                            self.read(SETUP_IC), commitments=hashed, pedersen=pedersen)
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            dll.nlx_bn254_groth16_setup_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def setup(ctx, log_n, n_wires, n_public, n_constraints, r1cs, trapdoor=None, commitments=None):
+    """gnark's groth16.Setup(r1cs) on the device: (ProvingKey, VerifyingKey, SetupArrays).  trapdoor: a Trapdoor (drawn from
+    `secrets` when not given, and then gone with this call: nothing returned can forge).  The rules are recalled from gnark v0.9
+    and unpinned (tools/groth16_model.py rule 3, tools/groth16_commit_model.py rule 1)."""
+    s = Setup(ctx, log_n, n_wires, n_public, n_constraints, r1cs, Trapdoor.random() if trapdoor is None else trapdoor, commitments)
+    try:
+        return s.key(), s.verifying_key(), s.arrays()
+    finally:
+        s.close()

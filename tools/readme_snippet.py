@@ -38,4 +38,7 @@ key = G.ProvingKey(ctx, 1, 2, 1, 1, inf8[None][:0], inf8[None][:0], inf16[None][
 groth16_proof = G.proof_bytes(*G.prove(key, G.fr_pack([1, 1])))
 print("groth16", len(groth16_proof))
 G.VerifyingKey(ctx, 1, inf8, inf16, inf16, inf16, inf8[None]).verify(groth16_proof).raise_if_rejected()   # the matching key of points at infinity: e(alpha, beta) = 1
+spk, svk, _ = G.setup(ctx, 1, 2, 1, 1, r1cs)        # an honest key of the same circuit, from a trapdoor drawn and dropped
+svk.verify(G.proof_bytes(*G.prove(spk, G.fr_pack([1, 1])))).raise_if_rejected()
+print("groth16 setup -> prove -> verify")
 print("hash_to_field", hex(nlx.bn254_plonk.hash_to_field_native(b"abc")) == hex(nlx.bn254_plonk.hash_to_field(b"abc")))   # the PLONK prover's host hash (ResidentKey / prove_resident: DESIGN.md section 23)
