@@ -595,6 +595,78 @@ typedef struct {
 int32_t nlx_bn254_plonk_check_witness(nlx_ctx* ctx, nlx_bn254_plonk_key* key, const uint64_t* l, const uint64_t* r, const uint64_t* o,
                                       const uint64_t* public_inputs, uint64_t n_public, const uint64_t* commit_blinding, uint32_t what,
                                       nlx_bn254_plonk_witness_report* report);
+/* gnark's plonk.Setup(spr, srs) on the device, from the constraints (csrc/bn254_plonk_setup.hip).  The
+ * rules are those of tools/gnark_plonk_setup_model.py, the place of record - recalled from gnark v0.9 backend/plonk/bn254
+ * setup.go, UNPINNED like the rest of the PLONK half: parity with gnark-produced keys is not claimed.  With N = n_public +
+ * n_constraints and n = 2^log_n >= N:
+ *   rows         row i < n_public: ql = -1, the other selectors 0, cells L = variable i, R = O = variable 0; row n_public + c is
+ *                constraint c: selectors coeffs[ql[c]] .., cells (xa[c], xb[c], xc[c]); rows N .. n - 1: selectors 0, cells variable 0.
+ *                qk holds the constraints' constants only: public inputs enter at proof time.
+ *   commitments  commitment j names committed CONSTRAINT indices (ascending) and one commitment constraint; the key's rows are
+ *                those indices + n_public, qcp_j is 1 on j's committed rows, last_row = N - 1.  The constraints' own selectors
+ *                (ql = -1 on those rows) are the circuit's business.
+ *   permutation  over positions p = col * n + row (col 0 1 2 = L R O): walking p upward, perm[p] = the previous position holding
+ *                the same variable; a variable's first position takes its last one; a variable seen once maps to itself.
+ *   sigma        s_col(w^row) = id[perm[col * n + row]], id[c * n + i] = (1, k1, k2)[c] * w^i (gnark: k1 = u, k2 = u^2).
+ * The descriptor:
+ *   log_n        0: the smallest log_n >= 3 with 2^log_n >= N; else 3 .. 26
+ *   xa xb xc     n_constraints variable ids each; ql qr qm qo qk: n_constraints coefficient ids each (host or device)
+ *   coeffs       n_coeffs x 4 Montgomery words (host or device); k1, k2, coset_shift: HOST, four Montgomery words each
+ *   n_commit     k <= NLX_BN254_PLONK_MAX_COMMIT; n_committed: k counts, committed: the k sets of constraint indices
+ *                concatenated, commit_constraint: k constraint indices (host or device)
+ * Refused on the host before anything is allocated on the device, the message naming the cause and the index - NLX_E_RANGE:
+ * flags other than NLX_BN254_MONTGOMERY, log_n outside 3 .. 26 or too small for N, n_variables = 0 or < n_public, a variable id
+ * >= n_variables, a coefficient id >= n_coeffs, a coefficient, k1, k2 or coset_shift not below r, n_commit > 4, a committed or
+ * commitment constraint index >= n_constraints, a set that does not ascend; NLX_E_INVAL: a NULL array that is needed.
+ * The result keeps on the device the trace on H (ql qr qm qo qk s1 s2 s3 qcp_j by values), the 3 n cells as variable ids and
+ * the permutation; it belongs to its context and must be destroyed before it.  Kernel-timing names: bn254_plonk_setup_rows,
+ * _sort, _perm, _sigma; bn254_plonk_setup_wires; bn254_kzg_srs_powers.
+ * (The type is known by its struct tag only: the name is the entry point's.) */
+struct nlx_bn254_plonk_setup;
+typedef struct {
+    uint32_t log_n;
+    uint32_t flags;                     /* NLX_BN254_MONTGOMERY */
+    uint64_t n_variables, n_public, n_constraints;
+    const uint32_t *xa, *xb, *xc;
+    const uint32_t *ql, *qr, *qm, *qo, *qk;
+    const uint64_t* coeffs; uint64_t n_coeffs;
+    const uint64_t *k1, *k2, *coset_shift;
+    uint32_t n_commit;
+    const uint64_t* n_committed;
+    const uint32_t* committed;
+    const uint32_t* commit_constraint;
+} nlx_bn254_plonk_setup_desc;
+int32_t nlx_bn254_plonk_setup(nlx_ctx* ctx, const nlx_bn254_plonk_setup_desc* desc, struct nlx_bn254_plonk_setup** out);
+void nlx_bn254_plonk_setup_destroy(struct nlx_bn254_plonk_setup* setup);
+/* out[0] = n, out[1] = log_n, out[2] = k, out[3] = N, out[4] = the variables that occur in a cell, out[5] = the cells of the
+ * variable that occurs most often (the longest cycle of the permutation). */
+#define NLX_BN254_PLONK_SETUP_INFO_WORDS 6
+int32_t nlx_bn254_plonk_setup_info(const struct nlx_bn254_plonk_setup* setup, uint64_t out[NLX_BN254_PLONK_SETUP_INFO_WORDS]);
+/* One array of the result copied to `out` (host or device).  The polynomials: n x 4 Montgomery words, NLX_PLONK_SETUP_QCP0 + j
+ * for j < k; CELLS: 3 n variable ids (uint32, L then R then O); PERMUTATION: 3 n positions; SIGMA_CELLS: the permutation in the
+ * witness checker's encoding, col << 30 | row.  NLX_E_RANGE: an unknown `which`. */
+enum {
+    NLX_PLONK_SETUP_QL = 0, NLX_PLONK_SETUP_QR = 1, NLX_PLONK_SETUP_QM = 2, NLX_PLONK_SETUP_QO = 3, NLX_PLONK_SETUP_QK = 4,
+    NLX_PLONK_SETUP_S1 = 5, NLX_PLONK_SETUP_S2 = 6, NLX_PLONK_SETUP_S3 = 7, NLX_PLONK_SETUP_QCP0 = 8,
+    NLX_PLONK_SETUP_CELLS = 12, NLX_PLONK_SETUP_PERMUTATION = 13, NLX_PLONK_SETUP_SIGMA_CELLS = 14
+};
+int32_t nlx_bn254_plonk_setup_read(const struct nlx_bn254_plonk_setup* setup, uint32_t which, void* out);
+/* The resident proving key of this setup: a nlx_bn254_plonk_key_desc of device pointers through nlx_bn254_plonk_key_create (the
+ * one creation path; srs, n_srs and what it refuses as there), key_flags = 0 or NLX_BN254_PLONK_KEY_COSET.  The key then receives
+ * the decoded permutation: its first NLX_BN254_PLONK_CHECK_COPIES reports cache_bytes = 12 n and runs no decode.  The key is the
+ * caller's, independent of `setup`. */
+int32_t nlx_bn254_plonk_setup_key(const struct nlx_bn254_plonk_setup* setup, const uint64_t* srs, uint64_t n_srs, uint32_t key_flags,
+                                  nlx_bn254_plonk_key** out);
+/* The solver's last step: l[row] = values[cell of (L, row)], r and o likewise.  values: n_variables x 4 words (host or device;
+ * the public inputs are the first n_public); l, r, o: n x 4 words each, host or device.  A `values` shorter than n_variables
+ * cannot be detected: only NULL is refused (NLX_E_INVAL). */
+int32_t nlx_bn254_plonk_setup_wires(nlx_ctx* ctx, const struct nlx_bn254_plonk_setup* setup, const uint64_t* values, uint64_t* l, uint64_t* r,
+                                    uint64_t* o);
+/* A TEST SRS from its trapdoor (gnark-crypto kzg.NewSRS(size, tau); whoever knows tau forges openings): g1_out[i] = [tau^i]_1 for
+ * i < n (n x 8 words, host or device), g2_out = [1]_2, [tau]_2 (2 x 16 words, HOST, may be NULL).  tau: HOST, four Montgomery
+ * words.  The powers are computed on the device (lane i from a table of tau^(2^b)), then one fixed-base pass per group.
+ * NLX_E_RANGE: tau = 0, tau not below r, n = 0 or n > 2^27. */
+int32_t nlx_bn254_kzg_srs(nlx_ctx* ctx, const uint64_t* tau, uint64_t n, uint64_t* g1_out, uint64_t* g2_out);
 /* n_polys <= 16 polynomials at ONE point in one pass: polys = host array of pointers to lens[i] x 4 words (coefficients, natural
  * order, host or device; 1 <= lens[i] <= 2^28, the lengths may differ), point: host; out: host, n_polys x 4 words.  Kernel-timing
  * name "bn254_fr_eval_many". */

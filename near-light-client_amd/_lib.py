@@ -124,6 +124,13 @@ SIGNATURES = {
     "nlx_bn254_plonk_prove": (ctypes.c_int32, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                                        ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "nlx_bn254_plonk_check_witness": (ctypes.c_int32, [ctypes.c_void_p] * 6 + [ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "nlx_bn254_plonk_setup": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
+    "nlx_bn254_plonk_setup_destroy": (None, [ctypes.c_void_p]),
+    "nlx_bn254_plonk_setup_info": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_bn254_plonk_setup_read": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "nlx_bn254_plonk_setup_key": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, c_void_pp]),
+    "nlx_bn254_plonk_setup_wires": (ctypes.c_int32, [ctypes.c_void_p] * 6),
+    "nlx_bn254_kzg_srs": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_bn254_fr_eval_many": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
     "nlx_bn254_hash_to_field": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),

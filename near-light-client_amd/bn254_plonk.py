@@ -528,6 +528,19 @@ class ResidentKey:
         ctx._adopt(self)
         self.proof_bytes = dll.nlx_bn254_plonk_proof_bytes(h)
 
+    @classmethod
+    def _from_handle(cls, ctx, handle, log_n, k1, k2, commitments=()):
+        """adopt a key the library built itself (nlx_bn254_plonk_setup_key)"""
+        from ._lib import dll
+        self = cls.__new__(cls)
+        self.ctx, self.handle = ctx, handle
+        self.log_n, self.n, self.k1, self.k2 = int(log_n), 1 << int(log_n), int(k1), int(k2)
+        self.bsb22 = [{"committed": [int(i) for i in c["committed"]], "row": int(c["row"]), "last_row": int(c["last_row"])} for c in commitments]
+        self.k = len(self.bsb22)
+        ctx._adopt(self)
+        self.proof_bytes = dll.nlx_bn254_plonk_proof_bytes(handle)
+        return self
+
     def info(self):
         """dict: resident bytes, n, k, the committed rows of all sets, whether the coset values are resident"""
         from ._lib import dll
@@ -691,6 +704,177 @@ def check_resident(key, l=None, r=None, o=None, public_inputs=(), commit_blindin
     if not rep:
         rep.message = dll.nlx_last_error(key.ctx.handle).decode()
     return rep
+
+
+# ---- gnark's plonk.Setup on the device, from the constraints (csrc/bn254_plonk_setup.hip; the rules:
+# tools/gnark_plonk_setup_model.py - recalled from gnark v0.9 and UNPINNED, parity with gnark-produced keys is not claimed) ----
+SETUP_INFO_WORDS = 6
+SETUP_ARRAYS = {"ql": 0, "qr": 1, "qm": 2, "qo": 3, "qk": 4, "s1": 5, "s2": 6, "s3": 7, "qcp0": 8, "qcp1": 9, "qcp2": 10, "qcp3": 11,
+                "cells": 12, "permutation": 13, "sigma_cells": 14}
+
+
+class _PlonkSetupDesc(ctypes.Structure):
+    """nlx_bn254_plonk_setup_desc (include/nlx.h)"""
+    _fields_ = ([("log_n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_variables", ctypes.c_uint64), ("n_public", ctypes.c_uint64),
+                 ("n_constraints", ctypes.c_uint64)]
+                + [(k, ctypes.c_void_p) for k in ("xa", "xb", "xc", "ql", "qr", "qm", "qo", "qk", "coeffs")]
+                + [("n_coeffs", ctypes.c_uint64)]
+                + [(k, ctypes.c_void_p) for k in ("k1", "k2", "coset_shift")]
+                + [("n_commit", ctypes.c_uint32), ("n_committed", ctypes.c_void_p), ("committed", ctypes.c_void_p),
+                   ("commit_constraint", ctypes.c_void_p)])
+
+
+def _element_words(x):
+    """an integer as fr.Element words; r <= x < 2^256 is no residue: its words go as they are and the library refuses them"""
+    x = int(x)
+    if not 0 <= x < (1 << 256):
+        raise ValueError("a field element does not fit four words")
+    return B._fr_words(_to_mont(x) if x < R else x)
+
+
+class Setup:
+    """struct nlx_bn254_plonk_setup: gnark's plonk.Setup(spr, srs) from a sparse constraint system, resident on the device (owns
+    the handle).  constraints: one (xa, xb, xc, ql, qr, qm, qo, qk) per constraint - three variable ids and five ids into
+    `coeffs` - as a list or an (m, 8) array; coeffs: integers below r, or (c, 4) uint64 fr.Element words; commitments: one
+    {"committed": ascending constraint indices, "constraint": the commitment's own constraint} per Bsb22 commitment; log_n = 0
+    takes the smallest domain of at least 8 rows that holds n_public + m rows.  coset_shift defaults to k1 (gnark: k1 = u,
+    k2 = u^2)."""
+
+    def __init__(self, ctx, n_variables, n_public, constraints, coeffs, k1=5, k2=25, coset_shift=None, commitments=(), log_n=0, flags=1):
+        from ._lib import dll
+        self.ctx, self.handle = ctx, None
+        self.n_variables, self.n_public, self.k1, self.k2 = int(n_variables), int(n_public), int(k1), int(k2)
+        self.sets = [{"committed": [int(i) for i in c["committed"]], "constraint": int(c["constraint"])} for c in commitments]
+        cons = np.ascontiguousarray(np.asarray(constraints, dtype=np.int64).reshape(-1, 8))
+        if cons.size and (cons.min() < 0 or cons.max() >= 1 << 32):
+            raise ValueError("variable and coefficient ids are 32-bit")
+        cols = np.ascontiguousarray(cons.T.astype(np.uint32))          # (8, m): xa xb xc ql qr qm qo qk
+        self.n_constraints = cons.shape[0]
+        if isinstance(coeffs, np.ndarray) and coeffs.dtype == np.uint64:
+            cw = np.ascontiguousarray(coeffs).reshape(-1, 4)
+        else:
+            cw = np.stack([_element_words(x) for x in coeffs]) if len(coeffs) else np.zeros((0, 4), dtype=np.uint64)
+        sc = [_element_words(x) for x in (self.k1, self.k2, self.k1 if coset_shift is None else coset_shift)]
+        d = _PlonkSetupDesc()
+        d.log_n, d.flags = int(log_n), int(flags)
+        d.n_variables, d.n_public, d.n_constraints = self.n_variables, self.n_public, self.n_constraints
+        if self.n_constraints:
+            for i, name in enumerate(("xa", "xb", "xc", "ql", "qr", "qm", "qo", "qk")):
+                setattr(d, name, cols[i].ctypes.data)
+        d.coeffs, d.n_coeffs = (cw.ctypes.data if len(cw) else None), len(cw)
+        d.k1, d.k2, d.coset_shift = (x.ctypes.data for x in sc)
+        d.n_commit = len(self.sets)
+        ids = [i for c in self.sets for i in c["committed"]] + [c["constraint"] for c in self.sets]
+        if any(not 0 <= i < 1 << 32 for i in ids):
+            raise ValueError("constraint indices are 32-bit")
+        counts = np.array([len(c["committed"]) for c in self.sets], dtype=np.uint64)
+        committed = np.array([i for c in self.sets for i in c["committed"]] + [0], dtype=np.uint32)
+        own = np.array([c["constraint"] for c in self.sets], dtype=np.uint32)
+        if self.sets:
+            d.n_committed, d.committed, d.commit_constraint = counts.ctypes.data, committed.ctypes.data, own.ctypes.data
+        h = ctypes.c_void_p()
+        ctx.check(dll.nlx_bn254_plonk_setup(ctx.handle, ctypes.byref(d), ctypes.byref(h)))
+        self.handle = h
+        ctx._adopt(self)
+        i = self.info()
+        self.n, self.log_n, self.k = i["n"], i["log_n"], i["k"]
+
+    def info(self):
+        """dict: n, log_n, k, the rows in use (n_public + constraints), the variables that occur, the longest class"""
+        from ._lib import dll
+        out = np.zeros(SETUP_INFO_WORDS, dtype=np.uint64)
+        self.ctx.check(dll.nlx_bn254_plonk_setup_info(self.handle, out.ctypes.data))
+        return {k: int(out[i]) for i, k in enumerate(("n", "log_n", "k", "rows_used", "variables_used", "longest_class"))}
+
+    def read(self, name, device=None):
+        """one array by name (SETUP_ARRAYS): a polynomial as (n, 4) fr.Element words, "cells" / "permutation" / "sigma_cells" as
+        3 n uint32 - numpy, or with device="cuda:k" a device tensor (int64 / int32 bit patterns)"""
+        from ._lib import dll
+        which = SETUP_ARRAYS[name]
+        poly = which < 12
+        if device is not None:
+            import torch
+            out = torch.empty((self.n, 4) if poly else (3 * self.n,), dtype=torch.int64 if poly else torch.int32, device=device)
+            self.ctx.check(dll.nlx_bn254_plonk_setup_read(self.handle, which, out.data_ptr()))
+            return out
+        out = np.zeros((self.n, 4) if poly else (3 * self.n,), dtype=np.uint64 if poly else np.uint32)
+        self.ctx.check(dll.nlx_bn254_plonk_setup_read(self.handle, which, out.ctypes.data))
+        return out
+
+    def values(self):
+        """the fixed polynomials by values on H as integers, in Instance.key_values()'s shape: ql .. s3, qcp0 .."""
+        names = list(ResidentKey.NAMES) + ["qcp%d" % j for j in range(self.k)]
+        return {name: [_from_words_mont(w) for w in self.read(name)] for name in names}
+
+    def commitment_info(self):
+        """the commitments as ResidentKey describes them: rows of H"""
+        last = self.n_public + self.n_constraints - 1
+        return [{"committed": [i + self.n_public for i in c["committed"]], "row": c["constraint"] + self.n_public, "last_row": last}
+                for c in self.sets]
+
+    def key(self, srs, coset=False):
+        """nlx_bn254_plonk_setup_key: the ResidentKey of this setup, built from the device arrays, its permutation already
+        decoded for the witness checker.  srs: (>= n + 3, 8) G1Affine words, numpy or a device tensor."""
+        from ._lib import dll
+        srs = srs if hasattr(srs, "data_ptr") else np.ascontiguousarray(srs, dtype=np.uint64)
+        h = ctypes.c_void_p()
+        rc = dll.nlx_bn254_plonk_setup_key(self.handle, _ptr(srs), srs.shape[0], NLX_BN254_PLONK_KEY_COSET if coset else 0, ctypes.byref(h))
+        if rc:
+            _raise(self.ctx, rc)
+        return ResidentKey._from_handle(self.ctx, h, self.log_n, self.k1, self.k2, self.commitment_info())
+
+    def wires(self, values, device="cuda:0"):
+        """nlx_bn254_plonk_setup_wires, the solver's last step: the solved variable vector (n_variables integers, (n_variables, 4)
+        fr.Element words or a device tensor of them) -> l, r, o as (n, 4) device tensors"""
+        import torch
+        from ._lib import dll
+        v = _wire_words(values)
+        if v.shape[0] != self.n_variables:
+            raise ValueError("expected %d variable values" % self.n_variables)
+        out = [torch.empty((self.n, 4), dtype=torch.int64, device=device) for _ in range(3)]
+        self.ctx.check(dll.nlx_bn254_plonk_setup_wires(self.ctx.handle, self.handle, _ptr(v), *(t.data_ptr() for t in out)))
+        return tuple(out)
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            from ._lib import dll
+            dll.nlx_bn254_plonk_setup_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def kzg_srs(ctx, tau, n, device=None):
+    """A TEST SRS from its trapdoor (nlx_bn254_kzg_srs; gnark-crypto kzg.NewSRS(n, tau)): ([tau^i]_1 for i < n as (n, 8) G1Affine
+    words - numpy, or an int64 device tensor with device="cuda:k" -, [1]_2 and [tau]_2 as 16 words each).  Whoever knows tau
+    forges openings."""
+    from ._lib import dll
+    t = _element_words(tau)
+    g2 = np.zeros((2, 16), dtype=np.uint64)
+    if device is not None:
+        import torch
+        g1 = torch.empty((int(n), 8), dtype=torch.int64, device=device)
+        ctx.check(dll.nlx_bn254_kzg_srs(ctx.handle, t.ctypes.data, int(n), g1.data_ptr(), g2.ctypes.data))
+    else:
+        g1 = np.zeros((int(n), 8), dtype=np.uint64)
+        ctx.check(dll.nlx_bn254_kzg_srs(ctx.handle, t.ctypes.data, int(n), g1.ctypes.data, g2.ctypes.data))
+    return g1, g2[0], g2[1]
+
+
+def setup(ctx, n_variables, n_public, constraints, coeffs, srs, k1=5, k2=25, coset_shift=None, commitments=(), log_n=0, coset=False):
+    """gnark's plonk.Setup(spr, srs) in one call: (ResidentKey, Setup).  The Setup stays open for .wires(values) - the solver's
+    last step - and .read(); close it when the witnesses are done.  The rules are recalled from gnark v0.9 and unpinned
+    (tools/gnark_plonk_setup_model.py)."""
+    s = Setup(ctx, n_variables, n_public, constraints, coeffs, k1, k2, coset_shift, commitments, log_n)
+    try:
+        return s.key(srs, coset), s
+    except Exception:
+        s.close()
+        raise
 
 
 def eval_many(ctx, polys, point):

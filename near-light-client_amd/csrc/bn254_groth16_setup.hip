@@ -333,12 +333,8 @@ int32_t upload(nlx_ctx* ctx, Scratch& scratch, const std::vector<T>& v, const T*
 }
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
-const uint64_t G1_GEN[8] = {0xd35d438dc58f0d9dull, 0x0a78eb28f5c70b3dull, 0x666ea36f7879462cull, 0x0e0a77c19a07df2full,     // (1, 2)
-                            0xa6ba871b8b1e1b3aull, 0x14f1d651eb8e167bull, 0xccdd46def0f28c58ull, 0x1c14ef83340fbe5eull};
-const uint64_t G2_GEN[16] = {0x8e83b5d102bc2026ull, 0xdceb1935497b0172ull, 0xfbb8264797811adfull, 0x19573841af96503bull,    // gnark-crypto's g2Gen
-                             0xafb4737da84c6140ull, 0x6043dd5a5802d8c4ull, 0x09e950fc52a02f86ull, 0x14fef0833aea7b6bull,
-                             0x619dfa9d886be9f6ull, 0xfe7fd297f59e9b78ull, 0xff9e1a62231b7dfeull, 0x28fd7eebae9e4206ull,
-                             0x64095b56c71856eeull, 0xdc57f922327d3cbbull, 0x55f935be33351076ull, 0x0da4a0e693fd6482ull};
+using fixed_base::G1_GEN;
+using fixed_base::G2_GEN;
 
 void push_words(std::vector<uint64_t>& v, const Fr& x) {
     uint64_t w[4];

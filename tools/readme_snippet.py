@@ -42,3 +42,9 @@ spk, svk, _ = G.setup(ctx, 1, 2, 1, 1, r1cs)        # an honest key of the same 
 svk.verify(G.proof_bytes(*G.prove(spk, G.fr_pack([1, 1])))).raise_if_rejected()
 print("groth16 setup -> prove -> verify")
 print("hash_to_field", hex(nlx.bn254_plonk.hash_to_field_native(b"abc")) == hex(nlx.bn254_plonk.hash_to_field(b"abc")))   # the PLONK prover's host hash (ResidentKey / prove_resident: DESIGN.md section 23)
+P = nlx.bn254_plonk
+srs, g2, g2_tau = P.kzg_srs(ctx, 12345, 8 + 3)      # a TEST SRS from its trapdoor: whoever knows 12345 forges openings
+pkey, ps = P.setup(ctx, 3, 1, [(1, 1, 2, 0, 0, 1, 2, 0)], [0, 1, P.R - 1], srs)   # x * x = y on the variables (public, x, y): qm = 1, qo = -1
+l, r, o = ps.wires([9, 3, 9])                        # the solver's last step: variables -> wire columns on the device
+P.VerifyingKey.from_resident(pkey, g2, g2_tau, 1).verify(P.prove_resident(pkey, l, r, o, [9]), [9]).raise_if_rejected()
+print("plonk setup -> prove -> verify")
