@@ -115,6 +115,12 @@ class _Fold:
         self.k += 1
 
 
+# {program: parts whose kernel is held to three waves per SIMD (at most 168 registers)}: the parts HORNER_SEGMENTS sized for three
+# waves.  hipcc's scheduler otherwise trades the third wave for instruction-level parallelism when a segment's pressure moves by a
+# few registers (parts 1 and 2 of sha512_tagged came out at 197 with the 14-instruction field multiply; held, they take 166 and
+# no more scratch: profiles/field_mul14_resource_usage.txt).
+THREE_WAVE_PARTS = {"sha512_tagged": (1, 2)}
+
 SCHED_EVERY = 4
 
 
@@ -305,7 +311,7 @@ def generate_sources(name, words):
             out.append("")
         out += [
             "// the interpreter's prologue and epilogue (csrc/stark.hip k_air_quotient), the program between them as a switch on the segment",
-            "__global__ __launch_bounds__(AIRGEN_BLOCK) void kernel(AirParams p) {",
+            "__global__ __launch_bounds__(AIRGEN_BLOCK%s) void kernel(AirParams p) {" % (", 3" if pi in THREE_WAVE_PARTS.get(name, ()) else ""),
             "    const uint32_t sg = blockIdx.y;",
             "    const uint32_t first = p.n_seg > 1 ? p.seg[2 * sg] : 0u;",
             "    if (%s) return;   // another part's segment" % " && ".join("first != %du" % lo for lo, _ in part),

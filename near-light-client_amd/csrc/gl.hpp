@@ -136,34 +136,84 @@ GL_HD uint64_t reduce128_loose(uint64_t lo, uint64_t hi) {
 }
 GL_HD uint64_t reduce128(uint64_t lo, uint64_t hi) { return canon(reduce128_loose(lo, hi)); }
 
-#if defined(__HIP_DEVICE_COMPILE__)
-// 64x64 -> 128 product and Goldilocks reduction (16 instructions; hipcc's u64 code needs 29).  See gl32.hpp for the measurements
-// behind this.  The product is a chain of five multiply-adds none of which can overflow
-//   p0 = a0 b0;  p1 = a0 b1 + hi(p0);  p2 = a1 b0 + lo(p1);  p3 = a1 b1 + hi(p1) + hi(p2)   (w0 = lo(p0), w1 = lo(p2), (w3:w2) = p3)
-// - the three zero-extended addends cost a v_mov each, which issues at half the price of the add-with-carry instructions the
-// four-product form needed (round 4: the Poseidon micro-benchmark 2.56 -> 2.76 G/s on this change alone).
-__device__ __forceinline__ uint64_t mul_loose_asm(uint64_t a, uint64_t b) {
-    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
-    // plain C++ for the four products: hipcc selects exactly v_mad_u64_u32 with a (value : 0) register pair for each addend and
-    // spaces nothing (between asm statements it puts an s_nop); the last addition as x * 1 + c saves the pair
+#if defined(__HIP__)
+// ---- the ONE product chain and the ONE reduction of the device code ----------------------------------------------------------
+// 64x64 -> 128 product and Goldilocks reduction in 14 vector instructions (16 up to round 4; hipcc's u64 code needs 29; see
+// gl32.hpp for the measurements behind counting instructions and DESIGN §38 for this form).  The product is a chain of four
+// multiply-adds, the third of which is ALLOWED to overflow:
+//   p0 = a0 b0;  p1 = a0 b1 + hi(p0);  p2 = a1 b0 + p1 [carry k -> an SGPR pair];  p3 = a1 b1 + hi(p2)
+//   a b = w0 + 2^32 w1 + 2^64 (w3:w2) + 2^96 k     (w0 = lo(p0), w1 = lo(p2), (w3:w2) = p3; w3 + k <= 2^32 - 1)
+// p1 is a whole 64-bit addend, so only the two zero-extended high words cost a v_mov.  2^96 = -1 (mod p): k is the borrow-in of
+// the reduction's first subtraction and costs no instruction.  -DNLX_FIELD_MUL_PARENT builds the form of round 4 for A/B runs:
+// five multiply-adds none of which can overflow (p2 = a1 b0 + lo(p1), p3 = a1 b1 + hi(p1) + hi(p2)), three moves, no k.
+#if defined(NLX_FIELD_MUL_PARENT)
+constexpr bool MUL_HAS_K = false;
+#else
+constexpr bool MUL_HAS_K = true;
+#endif
+struct Wide128 {
+    uint32_t w0, w1;
+    uint64_t w32;  // limbs 2 and 3
+    uint64_t k;    // lane mask of the carry of weight 2^96 that is NOT in w32 (meaningful when MUL_HAS_K)
+};
+__device__ __forceinline__ Wide128 mul_chain(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) {
+    // plain C++ where it can be: hipcc selects exactly v_mad_u64_u32 with a (value : 0) register pair for each addend and spaces
+    // nothing (between asm statements it puts an s_nop)
     const uint64_t p0 = (uint64_t)a0 * b0;
     const uint64_t p1 = (uint64_t)a0 * b1 + (p0 >> 32);
+#if defined(NLX_FIELD_MUL_PARENT)
     const uint64_t p2 = (uint64_t)a1 * b0 + (uint32_t)p1;
     uint64_t p3 = (uint64_t)a1 * b1 + (p1 >> 32), sink;
-    asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(p3), "=s"(sink) : "v"((uint32_t)(p2 >> 32)), "v"(p3));
-    // r = (w1:w0) - w3 [borrow -> -EPS]
+    asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(p3), "=s"(sink) : "v"((uint32_t)(p2 >> 32)), "v"(p3));   // x * 1 + c saves the pair
+    return Wide128{(uint32_t)p0, (uint32_t)p2, p3, 0};
+#else
+    uint64_t p2, k;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(p2), "=&s"(k) : "v"(a1), "v"(b0), "v"(p1));
+    const uint64_t p3 = (uint64_t)a1 * b1 + (p2 >> 32);   // cannot overflow: (2^32 - 1)^2 + 2^32 - 1 < 2^64
+    return Wide128{(uint32_t)p0, (uint32_t)p2, p3, k};
+#endif
+}
+// the product with k folded into limb 3 (one add-with-carry), for callers that add products as integers
+__device__ __forceinline__ Wide128 fold_k(Wide128 x) {
+#if !defined(NLX_FIELD_MUL_PARENT)
+    uint32_t w3;
+    uint64_t sink;
+    asm("v_addc_co_u32_e64 %0, %1, 0, %2, %3" : "=v"(w3), "=&s"(sink) : "v"((uint32_t)(x.w32 >> 32)), "s"(x.k));
+    x.w32 = ((uint64_t)w3 << 32) | (uint32_t)x.w32;
+#endif
+    return x;
+}
+
+// (w3 : w2 : w1 : w0) - 2^96 k mod p, any four 32-bit limbs (k: a lane mask with w3 + k <= 2^32 - 1, read only when HAS_K) -> loose
+//   r = (w1:w0) - w3 - k [borrow b -> -EPS] + w2 EPS [carry -> +EPS]        2^64 = EPS, 2^96 = -1 (mod p)
+// Eight instructions: three for the subtraction's borrow repair; w2 EPS is ONE multiply-add (carry-out in VCC), carry -> mask,
+// mask * 1 + r (on gfx950 every VCC-chained add issues as slowly as a multiply, profiles/r02_valu_ubench.txt).
+// -DNLX_FIELD_REDUCE7: seven.  The repair is worth b P = b (2^64 - EPS), so (w2 - b) EPS + r is the same value - except when
+// w2 = 0 with a borrow (e.g. 2^63 * 2^33): m = w2 - b wraps to 2^32 - 1 and the sum is short by exactly 1.  That borrow-out
+// (`bad`, an SGPR pair) is the carry-in of the final + EPS, which is then two add-with-carry instead of a multiply-add.
+// No carry crosses an asm statement in VCC: k and bad are SGPR-pair operands.
+#define NLX_GL_SUB_W3_K "v_subb_co_u32_e64 %[r0], vcc, %[w0], %[w3], %[k]\n\t"
+#define NLX_GL_SUB_W3 "v_sub_co_u32 %[r0], vcc, %[w0], %[w3]\n\t"
+template <bool HAS_K>
+__device__ __forceinline__ uint64_t reduce128_core(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint64_t k) {
+#if !defined(NLX_FIELD_REDUCE7)
+#define NLX_GL_REPAIR                                \
+    "v_subbrev_co_u32 %[r1], vcc, 0, %[w1], vcc\n\t" \
+    "v_cndmask_b32_e64 %[t0], 0, -1, vcc\n\t"        \
+    "v_sub_co_u32 %[r0], vcc, %[r0], %[t0]\n\t"      \
+    "v_subbrev_co_u32 %[r1], vcc, 0, %[r1], vcc"
     uint32_t r0, r1, t0;
-    const uint32_t w2 = (uint32_t)p3;
-    asm("v_sub_co_u32 %[r0], vcc, %[w0], %[w3]\n\t"
-        "v_subbrev_co_u32 %[r1], vcc, 0, %[w1], vcc\n\t"
-        "v_cndmask_b32_e64 %[t0], 0, -1, vcc\n\t"
-        "v_sub_co_u32 %[r0], vcc, %[r0], %[t0]\n\t"
-        "v_subbrev_co_u32 %[r1], vcc, 0, %[r1], vcc"
-        : [r0] "=&v"(r0), [r1] "=&v"(r1), [t0] "=&v"(t0)
-        : [w0] "v"((uint32_t)p0), [w1] "v"((uint32_t)p2), [w3] "v"((uint32_t)(p3 >> 32))
-        : "vcc");
-    // + w2 * EPS [carry -> +EPS]: ONE multiply-add (carry-out in VCC), carry -> mask, mask * 1 + r.  On gfx950 every
-    // VCC-chained add issues as slowly as a multiply (profiles/r02_valu_ubench.txt), so these three replace seven.
+    if constexpr (HAS_K)
+        asm(NLX_GL_SUB_W3_K NLX_GL_REPAIR
+            : [r0] "=&v"(r0), [r1] "=&v"(r1), [t0] "=&v"(t0)
+            : [w0] "v"(w0), [w1] "v"(w1), [w3] "v"(w3), [k] "s"(k)
+            : "vcc");
+    else
+        asm(NLX_GL_SUB_W3 NLX_GL_REPAIR
+            : [r0] "=&v"(r0), [r1] "=&v"(r1), [t0] "=&v"(t0)
+            : [w0] "v"(w0), [w1] "v"(w1), [w3] "v"(w3)
+            : "vcc");
+#undef NLX_GL_REPAIR
     const uint64_t base = ((uint64_t)r1 << 32) | r0;
     uint64_t r;
     uint32_t tm;
@@ -174,34 +224,55 @@ __device__ __forceinline__ uint64_t mul_loose_asm(uint64_t a, uint64_t b) {
         : [w2] "v"(w2), [base] "v"(base)
         : "vcc");
     return r;
-}
+#else
+#define NLX_GL_REPAIR                                \
+    "v_subbrev_co_u32 %[r1], vcc, 0, %[w1], vcc\n\t" \
+    "v_subbrev_co_u32_e64 %[m], %[bad], 0, %[w2], vcc"
+    uint32_t r0, r1, m;
+    uint64_t bad;
+    if constexpr (HAS_K)
+        asm(NLX_GL_SUB_W3_K NLX_GL_REPAIR
+            : [r0] "=&v"(r0), [r1] "=&v"(r1), [m] "=&v"(m), [bad] "=&s"(bad)
+            : [w0] "v"(w0), [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3), [k] "s"(k)
+            : "vcc");
+    else
+        asm(NLX_GL_SUB_W3 NLX_GL_REPAIR
+            : [r0] "=&v"(r0), [r1] "=&v"(r1), [m] "=&v"(m), [bad] "=&s"(bad)
+            : [w0] "v"(w0), [w1] "v"(w1), [w2] "v"(w2), [w3] "v"(w3)
+            : "vcc");
+#undef NLX_GL_REPAIR
+    const uint64_t base = ((uint64_t)r1 << 32) | r0;
+    uint64_t u;
+    uint32_t t, lo, hi;
+    asm("v_mad_u64_u32 %[u], vcc, %[m], -1, %[base]\n\t"
+        "v_cndmask_b32_e64 %[t], 0, -1, vcc"
+        : [u] "=&v"(u), [t] "=&v"(t)
+        : [m] "v"(m), [base] "v"(base)
+        : "vcc");
+    asm("v_addc_co_u32_e64 %[lo], vcc, %[u0], %[t], %[bad]\n\t"
+        "v_addc_co_u32 %[hi], vcc, 0, %[u1], vcc"
+        : [lo] "=&v"(lo), [hi] "=v"(hi)
+        : [u0] "v"((uint32_t)u), [u1] "v"((uint32_t)(u >> 32)), [t] "v"(t), [bad] "s"(bad)
+        : "vcc");
+    return ((uint64_t)hi << 32) | lo;
 #endif
+}
+#undef NLX_GL_SUB_W3_K
+#undef NLX_GL_SUB_W3
 
-#if defined(__HIP__)
-// (w4 : w3 : w2 : w1 : w0) mod p, any five 32-bit limbs -> canonical.  2^64 = EPS, 2^96 = -1, 2^128 = -2^32:
-//   (w1:w0) - w3 [borrow -> -EPS] + w2 EPS [carry -> +EPS], made canonical, minus w4 2^32 (canonical for every w4: at most P - 1).
+// loose * loose -> loose
+__device__ __forceinline__ uint64_t mul_loose_asm(uint64_t a, uint64_t b) {
+    const Wide128 x = mul_chain((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+    return reduce128_core<MUL_HAS_K>(x.w0, x.w1, (uint32_t)x.w32, (uint32_t)(x.w32 >> 32), x.k);
+}
+
+// (w4 : w3 : w2 : w1 : w0) - 2^96 k mod p, any five 32-bit limbs -> canonical.  2^128 = -2^32:
+//   the four low limbs by reduce128_core, made canonical, minus w4 2^32 (canonical for every w4: at most P - 1).
 // One reduction for a whole sum of products: GateAcc's columns (prover_kernels.hip) and the extension product below.
 // reduce160_loose skips the canonical step: sub takes any u64 on its left, and the result is any u64 congruent to the value.
-template <bool CANON>
-__device__ __forceinline__ uint64_t reduce160_impl(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4) {
-    uint32_t r0, r1, t0;
-    asm("v_sub_co_u32 %[r0], vcc, %[w0], %[w3]\n\t"
-        "v_subbrev_co_u32 %[r1], vcc, 0, %[w1], vcc\n\t"
-        "v_cndmask_b32_e64 %[t0], 0, -1, vcc\n\t"
-        "v_sub_co_u32 %[r0], vcc, %[r0], %[t0]\n\t"
-        "v_subbrev_co_u32 %[r1], vcc, 0, %[r1], vcc"
-        : [r0] "=&v"(r0), [r1] "=&v"(r1), [t0] "=&v"(t0)
-        : [w0] "v"(w0), [w1] "v"(w1), [w3] "v"(w3)
-        : "vcc");
-    const uint64_t base = ((uint64_t)r1 << 32) | r0;
-    uint64_t r;
-    uint32_t tm;
-    asm("v_mad_u64_u32 %[r], vcc, %[w2], -1, %[base]\n\t"
-        "v_cndmask_b32_e64 %[t], 0, -1, vcc\n\t"
-        "v_mad_u64_u32 %[r], vcc, %[t], 1, %[r]"
-        : [r] "=&v"(r), [t] "=&v"(tm)
-        : [w2] "v"(w2), [base] "v"(base)
-        : "vcc");
+template <bool CANON, bool HAS_K = false>
+__device__ __forceinline__ uint64_t reduce160_impl(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4, uint64_t k = 0) {
+    const uint64_t r = reduce128_core<HAS_K>(w0, w1, w2, w3, k);
     return sub(CANON ? canon(r) : r, (uint64_t)w4 << 32);
 }
 __device__ __forceinline__ uint64_t reduce160(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4) {
@@ -210,19 +281,10 @@ __device__ __forceinline__ uint64_t reduce160(uint32_t w0, uint32_t w1, uint32_t
 __device__ __forceinline__ uint64_t reduce160_loose(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, uint32_t w4) {
     return reduce160_impl<false>(w0, w1, w2, w3, w4);
 }
-// the full 128-bit product (w32 : w1 : w0), by mul_loose_asm's chain of five multiply-adds
-struct Wide128 {
-    uint32_t w0, w1;
-    uint64_t w32;  // limbs 2 and 3
-};
+// the full 128-bit product (w32 : w1 : w0) + 2^96 k; a caller that reduces the product (or a sum it is part of) right away hands
+// k to the reduction, which takes one k for nothing; any further product's k goes into its limb 3 by fold_k (7 instructions, 8 before)
 __device__ __forceinline__ Wide128 mul_wide(uint64_t a, uint64_t b) {
-    const uint32_t a0 = (uint32_t)a, a1 = (uint32_t)(a >> 32), b0 = (uint32_t)b, b1 = (uint32_t)(b >> 32);
-    const uint64_t p0 = (uint64_t)a0 * b0;
-    const uint64_t p1 = (uint64_t)a0 * b1 + (p0 >> 32);
-    const uint64_t p2 = (uint64_t)a1 * b0 + (uint32_t)p1;
-    uint64_t p3 = (uint64_t)a1 * b1 + (p1 >> 32), sink;
-    asm("v_mad_u64_u32 %0, %1, %2, 1, %3" : "=v"(p3), "=s"(sink) : "v"((uint32_t)(p2 >> 32)), "v"(p3));
-    return Wide128{(uint32_t)p0, (uint32_t)p2, p3};
+    return mul_chain((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
 }
 #endif
 
@@ -281,7 +343,7 @@ GL_HD Ext sub(Ext x, Ext y) { return Ext{sub(x.a, y.a), sub(x.b, y.b)}; }
 // product by 7 rides on the addition: limb_i * 7 + q_i + carry <= 8 (2^32 - 1) + 7 fits 64 bits, so the chain never overflows.
 template <bool CANON>
 __device__ __forceinline__ Ext mul_impl(Ext x, Ext y) {
-    const Wide128 ab = mul_wide(x.a, y.b), ba = mul_wide(x.b, y.a);
+    const Wide128 ab = mul_wide(x.a, y.b), ba = fold_k(mul_wide(x.b, y.a));   // ab's k: the reduction's borrow-in
     uint32_t s0, s1, s2, s3, s4;
     asm("v_add_co_u32 %[s0], vcc, %[x0], %[y0]\n\t"
         "v_addc_co_u32 %[s1], vcc, %[x1], %[y1], vcc\n\t"
@@ -292,15 +354,15 @@ __device__ __forceinline__ Ext mul_impl(Ext x, Ext y) {
         : [x0] "v"(ab.w0), [x1] "v"(ab.w1), [x2] "v"((uint32_t)ab.w32), [x3] "v"((uint32_t)(ab.w32 >> 32)), [y0] "v"(ba.w0),
           [y1] "v"(ba.w1), [y2] "v"((uint32_t)ba.w32), [y3] "v"((uint32_t)(ba.w32 >> 32))
         : "vcc");
-    const uint64_t c1 = reduce160_impl<CANON>(s0, s1, s2, s3, s4);
+    const uint64_t c1 = reduce160_impl<CANON, MUL_HAS_K>(s0, s1, s2, s3, s4, ab.k);
     // one component at a time: with all four products in flight a caller holds 16 more registers (k_fri_fold lost a wave)
     __builtin_amdgcn_sched_barrier(0);
-    const Wide128 aa = mul_wide(x.a, y.a), bb = mul_wide(x.b, y.b);
+    const Wide128 aa = mul_wide(x.a, y.a), bb = fold_k(mul_wide(x.b, y.b));   // bb's k would weigh 7 * 2^96: into its limb 3
     const uint64_t t0 = (uint64_t)bb.w0 * (uint32_t)W + aa.w0;
     const uint64_t t1 = (uint64_t)bb.w1 * (uint32_t)W + (((uint64_t)aa.w1) + (t0 >> 32));
     const uint64_t t2 = (uint64_t)(uint32_t)bb.w32 * (uint32_t)W + ((aa.w32 & EPS) + (t1 >> 32));
     const uint64_t t3 = (uint64_t)(uint32_t)(bb.w32 >> 32) * (uint32_t)W + ((aa.w32 >> 32) + (t2 >> 32));
-    const uint64_t c0 = reduce160_impl<CANON>((uint32_t)t0, (uint32_t)t1, (uint32_t)t2, (uint32_t)t3, (uint32_t)(t3 >> 32));
+    const uint64_t c0 = reduce160_impl<CANON, MUL_HAS_K>((uint32_t)t0, (uint32_t)t1, (uint32_t)t2, (uint32_t)t3, (uint32_t)(t3 >> 32), aa.k);
     return Ext{c0, c1};
 }
 __device__ __forceinline__ Ext mul(Ext x, Ext y) { return mul_impl<true>(x, y); }

@@ -6,8 +6,9 @@
 // field multiply therefore costs its INSTRUCTION COUNT x 2 ns, whatever the instructions are, and a multiply-add that
 // replaces several carry-chain instructions is a straight win: `r = base + w2 * (2^32 - 1)` is ONE v_mad_u64_u32 (its
 // carry-out lands in VCC) instead of four add / subtract-with-carry instructions, and `r += carry ? 2^32 - 1 : 0` is a
-// v_cndmask + one more v_mad_u64_u32 (mask * 1 + r) instead of three.  Multiply + reduction: 16 instructions (20 in
-// round 1, ~29 from hipcc's u64 code); the fold of an MDS accumulator pair: 4 (9 in round 1).
+// v_cndmask + one more v_mad_u64_u32 (mask * 1 + r) instead of three.  Multiply + reduction: 14 instructions (16 in round 4,
+// 20 in round 1, ~29 from hipcc's u64 code; gl::mul_chain / gl::reduce128_core); the fold of an MDS accumulator pair: 4 (9 in
+// round 1).
 #pragma once
 #include "gl.hpp"
 #include "poseidon_blocks.inc"   // generated tables of the fused partial rounds (tools/gen_poseidon_blocks.py)
@@ -35,27 +36,15 @@ __device__ __forceinline__ F add_w2_eps(uint64_t base, uint32_t w2) {
     return from_u64(r);
 }
 
-// (w3:w2:w1:w0) mod p -> loose
-//   r = (w1:w0) - w3 [borrow -> -EPS] + (w2 * EPS) [carry -> +EPS]
+// (w3:w2:w1:w0) mod p -> loose: gl::reduce128_core, the one reduction of the device code
 __device__ __forceinline__ F reduce128(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
-    uint32_t r0, r1, t0;
-    asm("v_sub_co_u32 %[r0], vcc, %[w0], %[w3]\n\t"
-        "v_subbrev_co_u32 %[r1], vcc, 0, %[w1], vcc\n\t"
-        "v_cndmask_b32_e64 %[t0], 0, -1, vcc\n\t"
-        "v_sub_co_u32 %[r0], vcc, %[r0], %[t0]\n\t"
-        "v_subbrev_co_u32 %[r1], vcc, 0, %[r1], vcc"
-        : [r0] "=&v"(r0), [r1] "=&v"(r1), [t0] "=&v"(t0)
-        : [w0] "v"(w0), [w1] "v"(w1), [w3] "v"(w3)
-        : "vcc");
-    return add_w2_eps(((uint64_t)r1 << 32) | r0, w2);
+    return from_u64(gl::reduce128_core<false>(w0, w1, w2, w3, 0));
 }
 
 __device__ __forceinline__ uint64_t mad_u64_one(uint32_t a, uint64_t c);
 
-// loose * loose -> loose.  The 128-bit product as a chain of five multiply-adds none of which can overflow
-//   p0 = al bl;  p1 = al bh + hi(p0);  p2 = ah bl + lo(p1);  p3 = ah bh + hi(p1) + hi(p2)   (w0 = lo(p0), w1 = lo(p2), (w3:w2) = p3)
-// instead of four products and four carry-chain additions: the three zero-extended addends cost a v_mov each, which issues at
-// half the price of an add-with-carry (profiles/r04_valu_issue_rates_v1.txt).
+// loose * loose -> loose: gl::mul_chain and gl::reduce128_core on the limb pairs, 14 vector instructions (gl.hpp; 16 with
+// -DNLX_FIELD_MUL_PARENT).  -DNLX_GL32_MUL_CARRY_CHAINS keeps round 3's four products and carry-chain additions for A/B runs.
 __device__ __forceinline__ F mul(F a, F b) {
 #ifdef NLX_GL32_MUL_CARRY_CHAINS
     uint64_t t = (uint64_t)a.lo * b.lo;
@@ -85,14 +74,8 @@ __device__ __forceinline__ F mul(F a, F b) {
         : "vcc");
     return add_w2_eps(((uint64_t)r1 << 32) | r0, w2);
 #else
-    // plain C++ for the four products: hipcc selects exactly v_mad_u64_u32 with a (value : 0) register pair for each addend
-    // and spaces nothing (between asm statements it puts an s_nop); the last addition as x * 1 + c saves the pair
-    const uint64_t p0 = (uint64_t)a.lo * b.lo;
-    const uint64_t p1 = (uint64_t)a.lo * b.hi + (p0 >> 32);
-    const uint64_t p2 = (uint64_t)a.hi * b.lo + (uint32_t)p1;
-    uint64_t p3 = (uint64_t)a.hi * b.hi + (p1 >> 32);
-    p3 = mad_u64_one((uint32_t)(p2 >> 32), p3);
-    return reduce128((uint32_t)p0, (uint32_t)p2, (uint32_t)p3, (uint32_t)(p3 >> 32));
+    const gl::Wide128 x = gl::mul_chain(a.lo, a.hi, b.lo, b.hi);
+    return from_u64(gl::reduce128_core<gl::MUL_HAS_K>(x.w0, x.w1, (uint32_t)x.w32, (uint32_t)(x.w32 >> 32), x.k));
 #endif
 }
 

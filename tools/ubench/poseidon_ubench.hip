@@ -1,7 +1,10 @@
 // Development micro-benchmark: instruction issue rates on gfx950 and Poseidon permutation variants.
-// Build: hipcc -O3 --offload-arch=gfx950 -I near-light-client_amd/csrc tools/ubench/poseidon_ubench.hip -o /tmp/pub
+// Build: hipcc -O3 --offload-arch=gfx950 -I include -I near-light-client_amd/csrc tools/ubench/poseidon_ubench.hip -o /tmp/pub
+// The field multiply has three forms chosen at compile time (csrc/gl.hpp): build this file once per form - as it is (14
+// instructions), with -DNLX_FIELD_MUL_PARENT (16) and with -DNLX_FIELD_REDUCE7 (13) - and run `pub mul` for the multiply's rate alone.
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 #include "poseidon.hpp"
 #include "gl32.hpp"
@@ -496,9 +499,51 @@ int bench_perm(const char* name, uint64_t* d_states, size_t n, std::vector<uint6
     return 0;
 }
 
-int main() {
+// ---- the field multiply in the form this file was built with: four independent S-box chains per lane (16 multiplies per
+// iteration), 8 waves per SIMD ----
+#if defined(NLX_FIELD_MUL_PARENT)
+#define PUB_MUL_FORM "parent: 5 multiply-adds, 3 moves, 8-instruction reduction (16)"
+#elif defined(NLX_FIELD_REDUCE7)
+#define PUB_MUL_FORM "4 multiply-adds, carry k to the reduction, 7-instruction reduction (13)"
+#else
+#define PUB_MUL_FORM "4 multiply-adds, carry k to the reduction, 8-instruction reduction (14)"
+#endif
+__global__ __launch_bounds__(256) void k_mul_rate(uint64_t* out, int iters) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    gl32::F x0 = gl32::from_u64(t * 0x9E3779B97F4A7C15ull), x1 = gl32::from_u64(~x0.lo * 0xD1B54A32D192ED03ull),
+            x2 = gl32::from_u64(t ^ 0xFFFFFFFF00000002ull), x3 = gl32::from_u64(0xFFFFFFFFFFFFFFFFull - t);
+    for (int i = 0; i < iters; i++) {
+        x0 = gl32::sbox7(x0); x1 = gl32::sbox7(x1); x2 = gl32::sbox7(x2); x3 = gl32::sbox7(x3);
+    }
+    out[t] = gl::canon(gl32::to_u64(x0)) ^ gl::canon(gl32::to_u64(x1)) ^ gl::canon(gl32::to_u64(x2)) ^ gl::canon(gl32::to_u64(x3));
+}
+int bench_mul(uint64_t* d_out64) {
+    const int iters = 2048, blocks = 256 * 8, threads = 256;
+    hipEvent_t e0, e1;
+    CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    hipLaunchKernelGGL(k_mul_rate, dim3(blocks), dim3(threads), 0, 0, d_out64, 16);
+    for (int rep = 0; rep < 3; rep++) {
+        CK(hipEventRecord(e0));
+        hipLaunchKernelGGL(k_mul_rate, dim3(blocks), dim3(threads), 0, 0, d_out64, iters);
+        CK(hipEventRecord(e1));
+        CK(hipEventSynchronize(e1));
+        float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+        const double wave_muls = (double)blocks * (threads / 64) * iters * 16;
+        printf("field multiply [%s]: %.3f ms -> %.2f ns per wave-multiply per SIMD, %.1f G multiplies/s\n", PUB_MUL_FORM, ms,
+               ms * 1e6 / (wave_muls / 1024.0), wave_muls * 64 / ms / 1e6);
+    }
+    uint64_t h[4];
+    CK(hipMemcpy(h, d_out64, sizeof h, hipMemcpyDeviceToHost));
+    printf("field multiply checksum (equal for the three forms): %016llx %016llx %016llx %016llx\n", (unsigned long long)h[0],
+           (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3]);
+    return 0;
+}
+
+int main(int argc, char** argv) {
     uint32_t* d_out;
-    CK(hipMalloc(&d_out, 256 * 8 * 256 * 4));
+    CK(hipMalloc(&d_out, 256 * 8 * 256 * 8));
+    if (bench_mul((uint64_t*)d_out)) return 1;
+    if (argc > 1 && !strcmp(argv[1], "mul")) return 0;
     rate<4>("v_add_u32", d_out);
     rate<0>("v_mad_u32_u24", d_out);
     rate<7>("v_mul_u32_u24", d_out);
