@@ -787,6 +787,38 @@ int32_t nlx_bn254_plonk_verify(const nlx_bn254_plonk_vk* vk, const uint8_t* proo
 int32_t nlx_bn254_plonk_verify_batch(const nlx_bn254_plonk_vk* vk, const uint8_t* const* proofs, const size_t* lens, size_t n_proofs,
                                      const uint64_t* public_inputs, nlx_bn254_verdict* verdicts);
 
+/* ---- f.4: gnark-crypto's point bytes, decoded and encoded on the device (csrc/bn254_codec.hpp / .hip).
+ * What kzg.SRS.WriteTo and groth16.ProvingKey.WriteTo / WriteRawTo are made of: G1Affine.Bytes() (32 bytes) and G2Affine.Bytes()
+ * (64) with flags = NLX_BN254_POINTS_COMPRESSED, RawBytes() (64 and 128) with NLX_BN254_POINTS_RAW; exactly one of the two must
+ * be set, else NLX_E_RANGE.  The place of record for every byte rule is tools/gnark_bytes_model.py; the rules are recalled from
+ * gnark v0.9 / gnark-crypto and UNPINNED like the rest of f.4.  In short: coordinates are big-endian canonical integers below q,
+ * G2 as X.A1 || X.A0 (|| Y.A1 || Y.A0); the top two bits of the first byte are 00 (raw), 10 / 11 (compressed, the smaller / larger
+ * y: y > (q - 1) / 2, over Fq2 decided on A1, on A0 when A1 is zero) or 01: the point at infinity, 0x40 and zeros in both modes
+ * and (0, 0) in words.  Words are G1Affine (8) / G2Affine (16: X.A0 X.A1 Y.A0 Y.A1), Montgomery.
+ * Pointers may be host or device; input and output must not overlap (NLX_E_INVAL).  n = 0: NLX_OK, nothing is written; n <= 2^28.
+ * Decode: one lane per point - the flag for the mode, every coordinate below q, compressed: y = (x^3 + b)^((q + 1) / 4) and its
+ * check (over Fq2 two such chains), raw: the curve equation; G2: the subgroup test of nlx_bn254_pairing unless
+ * NLX_BN254_POINTS_NO_SUBGROUP.  A point gets the first status that applies (NLX_BN254_POINT_*: BAD_INFINITY = flag 01 with any
+ * other bit set; OFF_CURVE = no square root, or a raw point off the curve) and a bad point all-zero words.  If any point is bad
+ * the call returns NLX_E_INVAL, the message naming the lowest bad index and its reason; points_out and status_out (n words, may
+ * be NULL) are written all the same.
+ * Encode: does not test the curve (gnark does not); a coordinate that is not below q: NLX_E_RANGE naming the lowest such index
+ * (its bytes are zero).
+ * Kernel-timing names "bn254_g1_decode", "bn254_g2_decode", "bn254_g1_encode", "bn254_g2_encode"; units: points. */
+#define NLX_BN254_POINTS_COMPRESSED 1u
+#define NLX_BN254_POINTS_RAW 2u
+#define NLX_BN254_POINTS_NO_SUBGROUP 4u /* nlx_bn254_g2_decode only */
+#define NLX_BN254_POINT_OK 0u
+#define NLX_BN254_POINT_BAD_FLAG 1u
+#define NLX_BN254_POINT_RANGE 2u
+#define NLX_BN254_POINT_BAD_INFINITY 3u
+#define NLX_BN254_POINT_OFF_CURVE 4u
+#define NLX_BN254_POINT_NOT_IN_SUBGROUP 5u
+int32_t nlx_bn254_g1_decode(nlx_ctx* ctx, const uint8_t* bytes, uint64_t n, uint32_t flags, uint64_t* points_out, uint32_t* status_out);
+int32_t nlx_bn254_g2_decode(nlx_ctx* ctx, const uint8_t* bytes, uint64_t n, uint32_t flags, uint64_t* points_out, uint32_t* status_out);
+int32_t nlx_bn254_g1_encode(nlx_ctx* ctx, const uint64_t* points, uint64_t n, uint32_t flags, uint8_t* bytes_out);
+int32_t nlx_bn254_g2_encode(nlx_ctx* ctx, const uint64_t* points, uint64_t n, uint32_t flags, uint8_t* bytes_out);
+
 /* ---- a3: plonky2::fri::oracle::PolynomialBatch::{from_values, from_coeffs} ----
  * values / coeffs: n_cols x 2^log_n column-major, natural order.  The coset shift is the
  * field's multiplicative generator (plonky2 F::coset_shift()).  blinding / salting is not

@@ -10,6 +10,9 @@ gnark-produced bytes unpinned: DESIGN.md section 19).
                          .verify(proof_bytes, public) / .verify_many(proofs, publics) -> Verdict
   setup(ctx, ..., r1cs)  nlx_bn254_groth16_setup: gnark's groth16.Setup from a trapdoor on the device -> (ProvingKey,
                          VerifyingKey, SetupArrays); Setup is the resident result itself
+  Setup.proving_key_bytes(raw) / ProvingKey.from_bytes(ctx, data, r1cs=, commitments=)
+                         gnark's ProvingKey.WriteTo / WriteRawTo and ReadFrom, the points through the device codec
+                         (bn254_codec.py; layout: tools/gnark_bytes_model.py)
 Keys with k Bsb22 / Pedersen commitments (rules: tools/groth16_commit_model.py):
   ProvingKey(ctx, ..., commitments=[...])   nlx_bn254_groth16_key_create_committed: the Pedersen bases resident next to the key
   commit(pk, j, w)                          nlx_bn254_groth16_commit: C_j, the call a solver's hint makes
@@ -26,7 +29,7 @@ import numpy as np
 
 from . import batch as B
 from ._lib import NlxError, dll, ptr
-from .bn254_plonk import fr_bytes, g1_marshal, hash_to_field
+from .bn254_plonk import fr_bytes, g1_marshal, hash_to_field, root_of_unity
 
 R, Q = B.BN254_R, B.BN254_Q
 _MONT = (1 << 256) % R
@@ -76,6 +79,16 @@ def fr_unpack(words):
     minv = pow(_MONT, R - 2, R)
     a = np.asarray(words, dtype=np.uint64).reshape(-1, 4)
     return [sum(int(a[i, w]) << (64 * w) for w in range(4)) * minv % R for i in range(a.shape[0])]
+
+
+DOMAIN_BYTES = 8 + 5 * 32
+
+
+def domain_bytes(log_n):
+    """fft.Domain.WriteTo as a ProvingKey carries it: the cardinality (uint64), then CardinalityInv, Generator, GeneratorInv,
+    FrMultiplicativeGen (5) and FrMultiplicativeGenInv as 32-byte big-endian canonical integers"""
+    n, w = 1 << log_n, root_of_unity(log_n)
+    return n.to_bytes(8, "big") + b"".join(v.to_bytes(32, "big") for v in (pow(n, R - 2, R), w, pow(w, R - 2, R), 5, pow(5, R - 2, R)))
 
 
 def _buf(a, dtype, width=None, size=None):
@@ -193,6 +206,55 @@ class ProvingKey:
         self.has_r1cs = True
         ctx._adopt(self)
         return self
+
+    @classmethod
+    def from_bytes(cls, ctx, data, r1cs, commitments=None):
+        """gnark's groth16.ProvingKey.ReadFrom, the result resident: `data` is what ProvingKey.WriteTo or WriteRawTo wrote (the
+        mode is read off G1.Alpha's flag bits; layout: tools/gnark_bytes_model.py rule 10, recalled and unpinned).  The R1CS and
+        the commitments' wire sets live in gnark's constraint system, not in the key, so they stay arguments: r1cs as for the
+        constructor; commitments: one dict per commitment key with "private", "public", "wire" (Basis and BasisExpSigma come from
+        the bytes).  n_constraints is the matrices' row count; n_public follows from the sizes: the wires that are neither in
+        G1.K nor committed nor a commitment's.  Every point goes through the device codec, each slice in one call and the big
+        ones without leaving the device; NlxError (NLX_E_INVAL) names the section for short or trailing data, for a count that
+        disagrees with the sizes, and section and index for a bad point."""
+        from . import bn254_codec as C
+        rd = C.Reader(ctx, data, C.container_is_raw(data, [("domain", DOMAIN_BYTES)], "G1.Alpha"), "cuda:%d" % ctx.device)
+        n = rd.u64("domain")
+        if n == 0 or n & (n - 1) or n > 1 << 28:
+            raise NlxError(NLX_E_INVAL, "domain: the cardinality %d is no power of two up to 2^28" % n)
+        log_n = n.bit_length() - 1
+        if bytes(rd.take(DOMAIN_BYTES - 8, "domain")) != domain_bytes(log_n)[8:]:
+            raise NlxError(NLX_E_INVAL, "domain: not the domain of cardinality %d" % n)
+        single = {k: rd.point(False, "G1." + k[3:].capitalize()) for k in ("g1_alpha", "g1_beta", "g1_delta")}
+        big = {k: rd.points(False, "G1." + k[3:].upper(), device=True) for k in ("g1_a", "g1_b", "g1_z", "g1_k")}
+        single["g2_beta"], single["g2_delta"] = rd.point(True, "G2.Beta"), rd.point(True, "G2.Delta")
+        big["g2_b"] = rd.points(True, "G2.B", device=True)
+        n_wires, nb_a, nb_b = rd.u64("nbWires"), rd.u64("NbInfinityA"), rd.u64("NbInfinityB")
+        inf_a, inf_b = rd.bools("InfinityA"), rd.bools("InfinityB")
+        for name, mask, nb, pts in (("A", inf_a, nb_a, big["g1_a"]), ("B", inf_b, nb_b, big["g1_b"])):
+            if len(mask) != n_wires or int(mask.sum()) != nb or len(pts) != n_wires - nb:
+                raise NlxError(NLX_E_INVAL, "Infinity%s: %d flags, %d set, NbInfinity%s %d, %d wires, %d points in G1.%s"
+                               % (name, len(mask), int(mask.sum()), name, nb, n_wires, len(pts), name))
+        if len(big["g2_b"]) != len(big["g1_b"]):
+            raise NlxError(NLX_E_INVAL, "G2.B: %d points, G1.B has %d" % (len(big["g2_b"]), len(big["g1_b"])))
+        if len(big["g1_z"]) != n - 1:
+            raise NlxError(NLX_E_INVAL, "G1.Z: %d points, the domain wants %d" % (len(big["g1_z"]), n - 1))
+        k = rd.u32("commitment keys count")
+        sets = [] if commitments is None else [dict(c) for c in commitments]
+        if k != len(sets):
+            raise NlxError(NLX_E_INVAL, "commitment keys count: the key holds %d, %d wire sets were given" % (k, len(sets)))
+        for j, c in enumerate(sets):
+            c["basis"], c["basis_exp_sigma"] = rd.points(False, "commitment key %d Basis" % j), rd.points(False, "commitment key %d BasisExpSigma" % j)
+            for name, pts in (("Basis", c["basis"]), ("BasisExpSigma", c["basis_exp_sigma"])):
+                if len(pts) != len(c["private"]):
+                    raise NlxError(NLX_E_INVAL, "commitment key %d %s: %d points, %d committed wires" % (j, name, len(pts), len(c["private"])))
+        rd.end("proving key")
+        n_public = n_wires - len(big["g1_k"]) - sum(len(c["private"]) for c in sets) - k
+        if n_public < 1:
+            raise NlxError(NLX_E_INVAL, "G1.K: %d points leave no public wire among %d" % (len(big["g1_k"]), n_wires))
+        return cls(ctx, log_n, n_wires, n_public, len(r1cs["A"][0]) - 1, big["g1_a"], big["g1_b"], big["g2_b"], big["g1_k"], big["g1_z"], inf_a, inf_b,
+                   single["g1_alpha"], single["g1_beta"], single["g1_delta"], single["g2_beta"], single["g2_delta"], r1cs=r1cs,
+                   commitments=sets if commitments is not None else None)
 
     def info(self):
         """what the key reports: resident bytes, and the SpMV's row split"""
@@ -611,6 +673,30 @@ class Setup:
         a["pedersen_g"] = self.read(SETUP_PEDERSEN_G)[0] if k else None
         a["pedersen_g_root_sigma_neg"] = self.read(SETUP_PEDERSEN_G_ROOT_SIGMA_NEG)[0] if k else None
         return SetupArrays(**a)
+
+    def proving_key_bytes(self, raw=False):
+        """gnark's groth16.ProvingKey.WriteTo (raw: WriteRawTo) of this setup's proving key: the domain, G1 Alpha Beta Delta and
+        the slices A B Z K, G2 Beta Delta and the slice B, nbWires NbInfinityA NbInfinityB and the two masks, the commitment keys
+        (tools/gnark_bytes_model.py rule 10, recalled and unpinned).  Each slice is read on the device and encoded there in one
+        call; only the bytes come to the host."""
+        from . import bn254_codec as C
+        dev = "cuda:%d" % self.ctx.device
+        one = lambda which: self.read(which)
+        out = [domain_bytes(self.log_n)]
+        out += [C.bn254_g1_encode(self.ctx, one(w), raw) for w in (SETUP_G1_ALPHA, SETUP_G1_BETA, SETUP_G1_DELTA)]
+        out += [C.slice_bytes(self.ctx, False, self.read(w, device=dev), raw) for w in (SETUP_G1_A, SETUP_G1_B, SETUP_G1_Z, SETUP_G1_K)]
+        out += [C.bn254_g2_encode(self.ctx, one(w), raw) for w in (SETUP_G2_BETA, SETUP_G2_DELTA)]
+        out.append(C.slice_bytes(self.ctx, True, self.read(SETUP_G2_B, device=dev), raw))
+        inf_a, inf_b = self.read(SETUP_INFINITY_A), self.read(SETUP_INFINITY_B)
+        out += [C.u64(self.n_wires), C.u64(int((inf_a != 0).sum())), C.u64(int((inf_b != 0).sum()))]
+        out += [C.u32(len(m)) + (m != 0).astype(np.uint8).tobytes() for m in (inf_a, inf_b)]
+        out.append(C.u32(len(self.commitments)))
+        basis, sigma, at = self.read(SETUP_BASIS), self.read(SETUP_BASIS_EXP_SIGMA), 0
+        for c in self.commitments:
+            m = len(c["private"])
+            out += [C.slice_bytes(self.ctx, False, basis[at:at + m], raw), C.slice_bytes(self.ctx, False, sigma[at:at + m], raw)]
+            at += m
+        return b"".join(out)
 
     def key(self):
         """nlx_bn254_groth16_setup_key: the resident ProvingKey, built from the device arrays"""

@@ -865,6 +865,41 @@ def kzg_srs(ctx, tau, n, device=None):
     return g1, g2[0], g2[1]
 
 
+def srs_to_bytes(ctx, g1, g2_one, g2_tau, raw=False):
+    """kzg.SRS.WriteTo (raw: WriteRawTo) of an SRS as kzg_srs returns it: the slice Pk.G1, Vk.G2[0], Vk.G2[1], Vk.G1 (= g1[0]); the
+    points through the device codec, the slice in one call.  Layout: tools/gnark_bytes_model.py rule 9, recalled and unpinned."""
+    from . import bn254_codec as C
+    if hasattr(g1, "data_ptr"):
+        first = g1[:1].cpu().numpy().view(np.uint64)
+    else:
+        g1 = np.ascontiguousarray(g1, dtype=np.uint64).reshape(-1, 8)
+        first = g1[:1]
+    if not len(first):
+        raise ValueError("an SRS holds at least one G1 point")
+    g2 = np.stack([np.ascontiguousarray(g2_one, dtype=np.uint64).reshape(16), np.ascontiguousarray(g2_tau, dtype=np.uint64).reshape(16)])
+    return C.slice_bytes(ctx, False, g1, raw) + C.bn254_g2_encode(ctx, g2, raw) + C.bn254_g1_encode(ctx, first, raw)
+
+
+def srs_from_bytes(ctx, data, device=None):
+    """kzg.SRS.ReadFrom: (g1, g2_0, g2_1), the tuple kzg_srs returns and setup takes - g1 numpy words, or an int64 device tensor
+    with device="cuda:k".  The mode (compressed or raw) is read off the first point's flag bits.  Every point goes through the
+    device codec (range, curve, for G2 the subgroup); NlxError (NLX_E_INVAL) names the section for short or trailing data and the
+    section and index for a bad point."""
+    from . import bn254_codec as C
+    from ._lib import NlxError
+    if len(data) >= 4 and not any(data[:4]):
+        raise NlxError(C.NLX_E_INVAL, "Pk.G1 is empty")
+    rd = C.Reader(ctx, data, C.container_is_raw(data, [("Pk.G1 count", 4)], "Pk.G1"), device)
+    g1 = rd.points(False, "Pk.G1", device=True)
+    g2_0, g2_1 = rd.point(True, "Vk.G2[0]"), rd.point(True, "Vk.G2[1]")
+    vk_g1 = rd.point(False, "Vk.G1")
+    rd.end("SRS")
+    first = g1[0].cpu().numpy().view(np.uint64) if hasattr(g1, "data_ptr") else g1[0]
+    if not np.array_equal(vk_g1, first):
+        raise NlxError(C.NLX_E_INVAL, "Vk.G1 is not Pk.G1[0]")
+    return g1, g2_0, g2_1
+
+
 def setup(ctx, n_variables, n_public, constraints, coeffs, srs, k1=5, k2=25, coset_shift=None, commitments=(), log_n=0, coset=False):
     """gnark's plonk.Setup(spr, srs) in one call: (ResidentKey, Setup).  The Setup stays open for .wires(values) - the solver's
     last step - and .read(); close it when the witnesses are done.  The rules are recalled from gnark v0.9 and unpinned

@@ -48,3 +48,10 @@ pkey, ps = P.setup(ctx, 3, 1, [(1, 1, 2, 0, 0, 1, 2, 0)], [0, 1, P.R - 1], srs) 
 l, r, o = ps.wires([9, 3, 9])                        # the solver's last step: variables -> wire columns on the device
 P.VerifyingKey.from_resident(pkey, g2, g2_tau, 1).verify(P.prove_resident(pkey, l, r, o, [9]), [9]).raise_if_rejected()
 print("plonk setup -> prove -> verify")
+ss = G.Setup(ctx, 1, 2, 1, 1, r1cs, G.Trapdoor.random())
+key_file = ss.proving_key_bytes()                    # gnark's ProvingKey.WriteTo: the points through the device codec
+read_key = G.ProvingKey.from_bytes(ctx, key_file, r1cs=r1cs)
+ss.verifying_key().verify(G.proof_bytes(*G.prove(read_key, G.fr_pack([1, 1])))).raise_if_rejected()
+print("groth16 key bytes", len(key_file))
+srs_file = P.srs_to_bytes(ctx, srs, g2, g2_tau)      # kzg.SRS.WriteTo; raw=True for WriteRawTo's uncompressed points
+print("srs bytes", len(srs_file), np.array_equal(P.srs_from_bytes(ctx, srs_file)[0], srs), nlx.bn254_g1_encode(ctx, nlx.bn254_g1_decode(ctx, srs_file[4:36])) == srs_file[4:36])
