@@ -662,6 +662,89 @@ int32_t nlx_bn254_plonk_setup_key(const struct nlx_bn254_plonk_setup* setup, con
  * cannot be detected: only NULL is refused (NLX_E_INVAL). */
 int32_t nlx_bn254_plonk_setup_wires(nlx_ctx* ctx, const struct nlx_bn254_plonk_setup* setup, const uint64_t* values, uint64_t* l, uint64_t* r,
                                     uint64_t* o);
+/* gnark's witness solver on the device, by levels (csrc/bn254_plonk_solve.hpp and .hip): from the public
+ * and secret inputs of a setup's constraint system to the whole variable vector that nlx_bn254_plonk_setup_wires takes.  The
+ * rules are those of tools/gnark_plonk_solve_model.py, the place of record - recalled from gnark v0.9 (constraint/bn254/solver.go)
+ * and UNPINNED: parity with gnark's solver is not claimed.
+ *   given        variables [0, n_public + n_secret)
+ *   counting     a cell counts only where its coefficient can determine it: L when ql != 0 or qm != 0, R when qr != 0 or
+ *                qm != 0, O when qo != 0
+ *   skipped      the committed constraints of every commitment and each commitment's own constraint
+ *   constraints  in index order: with no unassigned counting variable a check (ql l + qr r + qm l r + qo o + qk == 0), with one
+ *                (in one cell) it is solved: l = -(qr r + qo o + qk) / (ql + qm r), r likewise, o = -(ql l + qr r + qm l r + qk) / qo
+ *   hints        hint i runs in front of constraint hint_before[i] (non-descending); inputs hint_in[hint_in_off[i] ..
+ *                hint_in_off[i + 1]), outputs hint_out[hint_out_off[i] .. hint_out_off[i + 1]) (variable ids; the offset arrays hold
+ *                n_hints + 1 entries).  NLX_PLONK_HINT_INV_ZERO: 1 in, 1 out, x^-1 or 0 for 0.  _N_BITS: 1 in, 1 .. 256 outs, out
+ *                i = bit i of the canonical integer.  _QUO_REM64: 1 in, hint_param[i] = m in [1, 2^64), outs q, r with
+ *                canonical(x) = q m + r, 0 <= r < m.  The commitments' hints (c_j onto the L variable of commitment j's own
+ *                constraint, in front of that constraint) are implied by the setup and are not listed.
+ * Create makes the schedule on the host - per constraint its form (NLX_PLONK_SOLVE_FORM_*), its level (1 + the highest level
+ * among the assigners of its operands; inputs are level 0) and the variable it assigns - and refuses, before anything is
+ * allocated on the device, NLX_E_INVAL with a message naming the constraint or hint: two unassigned counting variables in one
+ * constraint; the unassigned variable in two counting cells; a hint input not assigned by `before`; a hint output that is given
+ * or assigned twice; `before` descending or > n_constraints; NLX_E_RANGE: flags other than NLX_BN254_MONTGOMERY, n_public +
+ * n_secret > n_variables, an unknown hint kind or a variable id out of range.  A variable nothing assigns stays 0 and is counted.
+ * All arrays of the descriptor are HOST arrays.  The solver keeps its own copies of all it needs: it is independent of `setup`
+ * once created, belongs to the setup's context and must be destroyed before it.  NLX_BN254_PLONK_SOLVER_NO_FUSE: one launch per
+ * level (the A/B run and the parity test); by default a run of consecutive levels of at most NLX_BN254_PLONK_SOLVER_FUSE items
+ * each executes in one launch of one workgroup, with a workgroup barrier between levels. */
+struct nlx_bn254_plonk_solver;
+#define NLX_PLONK_HINT_INV_ZERO 4u
+#define NLX_PLONK_HINT_N_BITS 5u
+#define NLX_PLONK_HINT_QUO_REM64 6u
+#define NLX_PLONK_SOLVE_FORM_CHECK 0u
+#define NLX_PLONK_SOLVE_FORM_L 1u
+#define NLX_PLONK_SOLVE_FORM_R 2u
+#define NLX_PLONK_SOLVE_FORM_O 3u
+#define NLX_PLONK_SOLVE_FORM_SKIPPED 8u
+#define NLX_BN254_PLONK_SOLVER_NO_FUSE 0x800u
+#define NLX_BN254_PLONK_SOLVER_FUSE 1024u
+typedef struct {
+    uint64_t n_secret;
+    uint32_t flags, n_hints;            /* NLX_BN254_MONTGOMERY, optionally | NLX_BN254_PLONK_SOLVER_NO_FUSE */
+    const uint32_t *hint_kind, *hint_before;
+    const uint64_t *hint_param;
+    const uint64_t *hint_in_off, *hint_out_off;
+    const uint32_t *hint_in, *hint_out;
+} nlx_bn254_plonk_solver_desc;
+int32_t nlx_bn254_plonk_solver_create(nlx_ctx* ctx, const struct nlx_bn254_plonk_setup* setup, const nlx_bn254_plonk_solver_desc* desc,
+                                      struct nlx_bn254_plonk_solver** out);
+void nlx_bn254_plonk_solver_destroy(struct nlx_bn254_plonk_solver* solver);
+/* out[0] = levels, [1] = the widest level's items, [2] = launches per solve (level and fused kernels; a commitment's hint adds
+ * its scatter and the commit call), [3] = fused runs, [4 .. 11] = items per form (check, solve L, R, O, INV_ZERO, N_BITS,
+ * QUO_REM64, COMMIT), [12] = constant divisors (inverted once, at creation), [13] = value-dependent divisors (inverted in-lane,
+ * per solve), [14] = variables left unassigned, [15] = resident bytes. */
+#define NLX_BN254_PLONK_SOLVER_INFO_WORDS 16
+int32_t nlx_bn254_plonk_solver_info(const struct nlx_bn254_plonk_solver* solver, uint64_t out[NLX_BN254_PLONK_SOLVER_INFO_WORDS]);
+/* The schedule per constraint, n_constraints uint32 to a HOST array: the level (0 where skipped), the form, or the variable it
+ * assigns (0xFFFFFFFF where none).  NLX_E_RANGE: an unknown `which`. */
+enum { NLX_PLONK_SOLVER_LEVEL = 0, NLX_PLONK_SOLVER_FORM = 1, NLX_PLONK_SOLVER_ASSIGNS = 2 };
+int32_t nlx_bn254_plonk_solver_read(const struct nlx_bn254_plonk_solver* solver, uint32_t which, void* out);
+#define NLX_PLONK_SOLVE_DIV_ZERO 1u      /* the divisor of a solving constraint is 0, whatever the numerator */
+#define NLX_PLONK_SOLVE_UNSATISFIED 2u   /* a check-only constraint is nonzero */
+typedef struct {
+    uint32_t solved;               /* 1: every item ran and nothing failed */
+    uint32_t kind;                 /* 0, or NLX_PLONK_SOLVE_* of the failing constraint of lowest index */
+    uint32_t constraint, level;    /* that constraint and its level */
+    uint64_t value[4];             /* the numerator (DIV_ZERO) or the constraint's value (UNSATISFIED), CANONICAL words */
+    uint64_t failures;             /* constraints that failed on clean operands */
+    uint64_t poisoned_variables;   /* variables downstream of a failure: not computed */
+    uint32_t levels_run, launches;
+} nlx_bn254_plonk_solve_report;
+/* One solve.  inputs: (n_public + n_secret) x 4 Montgomery words, host or device, each below r (else NLX_E_RANGE, nothing
+ * written).  key: the setup's resident key, required exactly when the setup carries commitments (k > 0), else NLX_E_INVAL; it
+ * must belong to the same n.  commit_blinding: HOST, 2 k elements (commitment j: [2 j] on its row, [2 j + 1] on last_row), the
+ * ones the proof will use; NULL exactly when k = 0.  values_out: n_variables x 4 words, host or device - what
+ * nlx_bn254_plonk_setup_wires takes; poisoned and unassigned variables come as 0.  commit_points_out: HOST, k x 8 words, the
+ * [PI2_j] (may be NULL).  Nothing in the call draws randomness.
+ * A failing constraint poisons the variable it would assign; an item with a poisoned operand fails nothing and poisons what it
+ * would assign (a commitment with a poisoned input is skipped), so the reported failure is the one a sequential solver stops
+ * at, however the levels interleave.  Returns NLX_OK whenever the solve ran - the verdict is in *report (zero-filled first);
+ * with report->solved == 0 nlx_last_error holds one line naming the constraint.  Kernel-timing names:
+ * bn254_plonk_solve_levels, _fused, _commit. */
+int32_t nlx_bn254_plonk_solver_solve(nlx_ctx* ctx, const struct nlx_bn254_plonk_solver* solver, const uint64_t* inputs,
+                                     const nlx_bn254_plonk_key* key, const uint64_t* commit_blinding, uint64_t* values_out,
+                                     uint64_t* commit_points_out, nlx_bn254_plonk_solve_report* report);
 /* A TEST SRS from its trapdoor (gnark-crypto kzg.NewSRS(size, tau); whoever knows tau forges openings): g1_out[i] = [tau^i]_1 for
  * i < n (n x 8 words, host or device), g2_out = [1]_2, [tau]_2 (2 x 16 words, HOST, may be NULL).  tau: HOST, four Montgomery
  * words.  The powers are computed on the device (lane i from a table of tau^(2^b)), then one fixed-base pass per group.

@@ -130,6 +130,11 @@ SIGNATURES = {
     "nlx_bn254_plonk_setup_read": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "nlx_bn254_plonk_setup_key": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, c_void_pp]),
     "nlx_bn254_plonk_setup_wires": (ctypes.c_int32, [ctypes.c_void_p] * 6),
+    "nlx_bn254_plonk_solver_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_void_pp]),
+    "nlx_bn254_plonk_solver_destroy": (None, [ctypes.c_void_p]),
+    "nlx_bn254_plonk_solver_info": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
+    "nlx_bn254_plonk_solver_read": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "nlx_bn254_plonk_solver_solve": (ctypes.c_int32, [ctypes.c_void_p] * 8),
     "nlx_bn254_kzg_srs": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
     "nlx_bn254_fr_eval_many": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p]),

@@ -835,10 +835,155 @@ class Setup:
         self.ctx.check(dll.nlx_bn254_plonk_setup_wires(self.ctx.handle, self.handle, _ptr(v), *(t.data_ptr() for t in out)))
         return tuple(out)
 
+    def solver(self, n_secret, hints=(), fuse=True):
+        """nlx_bn254_plonk_solver_create: the witness solver of this constraint system (Solver).  Variables [0, n_public +
+        n_secret) are the inputs; hints: ("inv_zero", before, x, y), ("n_bits", before, x, outs), ("quo_rem64", before, x, m, q, r)
+        with `before` = the constraint in front of which the hint runs, non-descending; the commitments' hints are implied.
+        fuse=False: one launch per level.  ValueError where the schedule refuses (the message names the constraint or hint)."""
+        return Solver(self, n_secret, hints, fuse)
+
     def close(self):
         if self.handle and self.ctx.handle:
             from ._lib import dll
             dll.nlx_bn254_plonk_setup_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- gnark's witness solver on the device, by levels (csrc/bn254_plonk_solve.hip, DESIGN.md section 40; the rules:
+# tools/gnark_plonk_solve_model.py - recalled from gnark v0.9 and UNPINNED) ----
+SOLVER_INFO_WORDS = 16
+SOLVER_NO_FUSE = 0x800
+SOLVER_FUSE = 1024
+HINT_KINDS = {"inv_zero": 4, "n_bits": 5, "quo_rem64": 6}
+SOLVE_KINDS = {0: "", 1: "DIV_ZERO", 2: "UNSATISFIED"}
+SOLVER_INFO_NAMES = ("levels", "widest_level", "launches", "fused_runs", "checks", "solve_l", "solve_r", "solve_o", "inv_zero", "n_bits", "quo_rem64",
+                     "commits", "constant_divisors", "value_divisors", "unassigned", "resident_bytes")
+
+
+class _PlonkSolverDesc(ctypes.Structure):
+    """nlx_bn254_plonk_solver_desc (include/nlx.h)"""
+    _fields_ = ([("n_secret", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("n_hints", ctypes.c_uint32)]
+                + [(k, ctypes.c_void_p) for k in ("hint_kind", "hint_before", "hint_param", "hint_in_off", "hint_out_off", "hint_in", "hint_out")])
+
+
+class SolveReport(ctypes.Structure):
+    """nlx_bn254_plonk_solve_report (include/nlx.h); `message` is the library's line, .value_int the canonical integer"""
+    _fields_ = [("solved", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("constraint", ctypes.c_uint32), ("level", ctypes.c_uint32),
+                ("value", ctypes.c_uint64 * 4), ("failures", ctypes.c_uint64), ("poisoned_variables", ctypes.c_uint64),
+                ("levels_run", ctypes.c_uint32), ("launches", ctypes.c_uint32)]
+    message = ""
+    commit_points = None          # (k, 8) G1Affine words: the [PI2_j]
+
+    @property
+    def value_int(self):
+        return sum(int(w) << (64 * i) for i, w in enumerate(self.value))
+
+    @property
+    def kind_name(self):
+        return SOLVE_KINDS.get(int(self.kind), "?")
+
+    def __bool__(self):
+        return self.solved == 1
+
+    def __str__(self):
+        return self.message if not self else "solved: %d levels in %d launches" % (self.levels_run, self.launches)
+
+    def raise_if_unsolved(self):
+        if not self:
+            raise ValueError(self.message)
+        return self
+
+
+class Solver:
+    """struct nlx_bn254_plonk_solver (owns the handle); made by Setup.solver.  It keeps its own copies and is independent of the
+    Setup once made; it belongs to the Setup's context."""
+
+    def __init__(self, setup, n_secret, hints=(), fuse=True):
+        from ._lib import dll
+        ctx = self.ctx = setup.ctx
+        self.handle = None
+        self.n_variables, self.n_public, self.n_secret, self.n_constraints, self.k = setup.n_variables, setup.n_public, int(n_secret), setup.n_constraints, setup.k
+        kinds, befores, params, ins, outs, in_off, out_off = [], [], [], [], [], [0], [0]
+        for t in hints:
+            kind = HINT_KINDS[t[0]]
+            o = [t[3]] if kind == 4 else list(t[3]) if kind == 5 else [t[4], t[5]]
+            m = int(t[3]) if kind == 6 else 0
+            if not 0 <= m < 1 << 64:
+                raise ValueError("quo_rem64 takes 1 <= m < 2^64")
+            kinds.append(kind), befores.append(int(t[1])), params.append(m), ins.append(int(t[2])), outs.extend(int(v) for v in o)
+            in_off.append(len(ins)), out_off.append(len(outs))
+        if any(not 0 <= v < 1 << 32 for v in befores + ins + outs):
+            raise ValueError("variable and constraint ids are 32-bit")
+        keep = [np.array(kinds + [0], dtype=np.uint32), np.array(befores + [0], dtype=np.uint32), np.array(params + [0], dtype=np.uint64),
+                np.array(in_off, dtype=np.uint64), np.array(out_off, dtype=np.uint64), np.array(ins + [0], dtype=np.uint32), np.array(outs + [0], dtype=np.uint32)]
+        d = _PlonkSolverDesc()
+        d.n_secret, d.flags, d.n_hints = self.n_secret, 1 | (0 if fuse else SOLVER_NO_FUSE), len(kinds)
+        for name, a in zip(("hint_kind", "hint_before", "hint_param", "hint_in_off", "hint_out_off", "hint_in", "hint_out"), keep):
+            setattr(d, name, a.ctypes.data)
+        h = ctypes.c_void_p()
+        rc = dll.nlx_bn254_plonk_solver_create(ctx.handle, setup.handle, ctypes.byref(d), ctypes.byref(h))
+        if rc:
+            _raise(ctx, rc)
+        self.handle = h
+        ctx._adopt(self)
+
+    def info(self):
+        """dict by SOLVER_INFO_NAMES: levels, the widest level, launches per solve, fused runs, items per form, constant and
+        value-dependent divisors, variables left unassigned, resident bytes"""
+        from ._lib import dll
+        out = np.zeros(SOLVER_INFO_WORDS, dtype=np.uint64)
+        self.ctx.check(dll.nlx_bn254_plonk_solver_info(self.handle, out.ctypes.data))
+        return {k: int(out[i]) for i, k in enumerate(SOLVER_INFO_NAMES)}
+
+    def read(self, name):
+        """the schedule per constraint as uint32: "level" (0 where skipped), "form" (0 check, 1 2 3 solve L R O, 8 skipped),
+        "assigns" (0xFFFFFFFF where none)"""
+        from ._lib import dll
+        out = np.zeros(self.n_constraints, dtype=np.uint32)
+        self.ctx.check(dll.nlx_bn254_plonk_solver_read(self.handle, {"level": 0, "form": 1, "assigns": 2}[name], out.ctypes.data))
+        return out
+
+    def solve(self, inputs, key=None, commit_blinding=None, device="cuda:0"):
+        """nlx_bn254_plonk_solver_solve: inputs = the n_public + n_secret given values (integers, (m, 4) fr.Element words or a
+        device tensor of them); key: the ResidentKey, required exactly when the setup carries commitments; commit_blinding: the
+        2 k scalars the proof will use.  -> (values, SolveReport): values as an (n_variables, 4) device tensor - what
+        Setup.wires takes -, or a numpy array with device=None.  A failing witness still returns: see the report."""
+        from ._lib import dll
+        v = _wire_words(inputs)
+        if v.shape[0] != self.n_public + self.n_secret:
+            raise ValueError("expected %d input values" % (self.n_public + self.n_secret))
+        k = self.k
+        cb = None
+        if commit_blinding is not None:
+            if len(commit_blinding) != 2 * k:
+                raise ValueError("two blinding scalars per Bsb22 commitment")
+            cb = np.stack([B._fr_words(_to_mont(int(x) % R)) for x in commit_blinding]) if k else None
+        if device is not None:
+            import torch
+            out = torch.empty((self.n_variables, 4), dtype=torch.int64, device=device)
+        else:
+            out = np.zeros((self.n_variables, 4), dtype=np.uint64)
+        points = np.zeros((max(k, 1), 8), dtype=np.uint64)
+        rep = SolveReport()
+        rc = dll.nlx_bn254_plonk_solver_solve(self.ctx.handle, self.handle, _ptr(v), key.handle if key is not None else None,
+                                              cb.ctypes.data if cb is not None else None, _ptr(out), points.ctypes.data, ctypes.addressof(rep))
+        if rc:
+            _raise(self.ctx, rc)
+        rep.commit_points = points[:k]
+        if not rep:
+            rep.message = dll.nlx_last_error(self.ctx.handle).decode()
+        return out, rep
+
+    def close(self):
+        if self.handle and self.ctx.handle:
+            from ._lib import dll
+            dll.nlx_bn254_plonk_solver_destroy(self.handle)
         self.handle = None
 
     def __del__(self):

@@ -26,6 +26,7 @@
 #include "bn254_fixed_base.hpp"
 #include "bn254_fp.hpp"
 #include "bn254_plonk_key.hpp"
+#include "bn254_plonk_setup.hpp"
 #include "ctx.hpp"
 #include "transcript.hpp"
 #include "../../include/nlx.h"
@@ -193,18 +194,6 @@ __global__ __launch_bounds__(256) void k_pls_tau_powers(const uint64_t* __restri
 using namespace nlx;
 using pls::Fr;
 
-// The result: one device block [vals (8 + k) n x 32 B | cells | perm | sigma_cells, 3 n words each] and what the key's creation
-// needs on the host.
-struct nlx_bn254_plonk_setup {
-    nlx_ctx* ctx = nullptr;
-    uint32_t log_n = 0, k = 0;
-    uint64_t n_variables = 0, n_public = 0, n_constraints = 0, occurring = 0, longest = 0;
-    uint64_t* vals = nullptr;
-    uint32_t *cells = nullptr, *perm = nullptr, *sigma_cells = nullptr;
-    uint64_t k1[4], k2[4], shift[4];
-    std::vector<uint64_t> counts;
-    std::vector<uint32_t> committed_rows, commit_rows;
-};
 typedef struct nlx_bn254_plonk_setup PSetup;   // the plain name is the entry point's
 
 namespace {
@@ -471,6 +460,11 @@ extern "C" int32_t nlx_bn254_plonk_setup(nlx_ctx* ctx, const nlx_bn254_plonk_set
         rc = scratch.finish(setup_body(ctx, scratch, desc, checked, *s));
     }
     if (rc) return rc;   // setup_free gives the block back
+    s->nonzero.assign((size_t)s->n_constraints, 0);
+    for (int i = 0; i < 5; i++)
+        for (size_t t = 0; t < s->nonzero.size(); t++)
+            s->nonzero[t] |= (uint8_t)((bnf::is_zero(bnf::load_words<bnf::RP>(&checked.coeffs[4 * (size_t)checked.sel[i][t]])) ? 0 : 1) << i);
+    for (int i = 0; i < 3; i++) s->x[i] = std::move(checked.x[i]);
     *out = s.release();
     return NLX_OK;
 } NLX_CATCH(ctx)

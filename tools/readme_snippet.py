@@ -48,6 +48,11 @@ pkey, ps = P.setup(ctx, 3, 1, [(1, 1, 2, 0, 0, 1, 2, 0)], [0, 1, P.R - 1], srs) 
 l, r, o = ps.wires([9, 3, 9])                        # the solver's last step: variables -> wire columns on the device
 P.VerifyingKey.from_resident(pkey, g2, g2_tau, 1).verify(P.prove_resident(pkey, l, r, o, [9]), [9]).raise_if_rejected()
 print("plonk setup -> prove -> verify")
+values, report = ps.solver(1).solve([9, 3])          # gnark's witness solver: the inputs (public, x) in, every variable out - y = 9 from x * x = y
+report.raise_if_unsolved()
+l, r, o = ps.wires(values)
+P.VerifyingKey.from_resident(pkey, g2, g2_tau, 1).verify(P.prove_resident(pkey, l, r, o, [9]), [9]).raise_if_rejected()
+print("plonk setup -> solve -> prove -> verify:", report)
 ss = G.Setup(ctx, 1, 2, 1, 1, r1cs, G.Trapdoor.random())
 key_file = ss.proving_key_bytes()                    # gnark's ProvingKey.WriteTo: the points through the device codec
 read_key = G.ProvingKey.from_bytes(ctx, key_file, r1cs=r1cs)
